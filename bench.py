@@ -12,7 +12,12 @@ inside the timed region, SURVEY.md section 8d "pcm on host -> token ids on host"
 the same pass with the batch already in HBM.  Decode length is forced to
 N_dec = 128 tokens per clip (EOS ignored) so the work is deterministic -- SURVEY.md section 8(d).
 
-Launch:  python bench.py [--gpus 1]            or, for N > 1 (one rank per GPU, RCCL):
+A plain run sets up, warms up, times the K steps of the headline leg, writes the last step's token ids if
+--dump-outputs DIR is given, and prints the result line.  --full adds the side measurements: the strictly serial and
+HBM-resident legs, the kernel probes and the roofline object, b=1 / b=8, the MLX-4bit engine, passes in flight, the
+Omnilingual legs and the CPU baseline.
+
+Launch:  python bench.py [--gpus 1] [--full]     or, for N > 1 (one rank per GPU, RCCL):
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
                 --master-port P bench.py --gpus N --steps K --warmup W
 Rank 0 prints ONE JSON line.
@@ -249,6 +254,15 @@ def run_leg(model, clips, n_dec, steps, warmup, world, gathered, inclusive, pipe
     return dt
 
 
+def dump_outputs(out_dir, gathered, n_dec):
+    """What the caller of the timed path received from its last step: the token ids of every clip of every rank ([world * B, n_dec],
+    rank-major, all n_dec forced tokens), as float32 (ids < 2^24: exact)."""
+    os.makedirs(out_dir, exist_ok=True)
+    tokens = gathered[:, :n_dec].cpu().numpy().astype(np.float32)
+    np.save(os.path.join(out_dir, "tokens.npy"), tokens)
+    log(f"wrote {out_dir}/tokens.npy {tokens.shape}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -259,10 +273,15 @@ def main():
     ap.add_argument("--decode-tokens", type=int, default=128)
     ap.add_argument("--bits", type=int, default=16, choices=[16, 8, 4],
                     help="weights of the HEADLINE engine: 16 = bf16 (BASELINE's config), 4 / 8 = MLX-quantised decoder")
-    ap.add_argument("--lanes", type=int, default=3, help="passes in flight on the GPU in the side leg `passes_in_flight` (qasr_dp_submit; 1: 5650, 2: 7440, 3: 7880, 4: 7260 audio-s/s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the b=1 / b=8, MLX-4bit and Omnilingual legs (profiling runs)")
-    ap.add_argument("--omnilingual", default="300M,7B", help="comma-separated Omnilingual-ASR-CTC variants for the configs[3] legs ('' = none)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements: serial / HBM-resident legs, kernel probes + roofline, b=1 / b=8, MLX-4bit, passes in flight, "
+                         "Omnilingual legs, CPU baseline (off: the headline leg alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (token ids of every clip, float32) as DIR/<name>.npy")
+    ap.add_argument("--lanes", type=int, default=3, help="passes in flight on the GPU in the side leg `passes_in_flight` (--full; qasr_dp_submit; 1: 5650, 2: 7440, 3: 7880, 4: 7260 audio-s/s)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the b=1 / b=8, MLX-4bit, passes-in-flight and Omnilingual legs (profiling runs)")
+    ap.add_argument("--omnilingual", default="300M,7B", help="with --full: comma-separated Omnilingual-ASR-CTC variants for the configs[3] legs ('' = none)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -308,17 +327,20 @@ def main():
     dt = run_leg(model, clips, n_dec, args.steps, args.warmup, world, gathered, inclusive=True, pipelined=True)
     log(f"timed {args.steps} steps in {dt * 1e3:.1f} ms")
     stage_ms, steps_done = model.batch_timings()
-    # the same passes strictly one after the other (staging + H2D + planning exposed in front of every pass)
-    dt_serial = run_leg(model, clips, n_dec, args.steps, 1, world, gathered, inclusive=True)
-    # the same passes with the batch already resident in HBM (no staging copy / H2D / planning in the timed region)
-    dt_res = run_leg(model, clips, n_dec, args.steps, 1, world, gathered, inclusive=False)
-    probe = {name: model.kernel_probe(which, 20) for which, name in ((0, "layer_gemv"), (1, "decode_attn"), (2, "lm_head"))}
-    # how the step of this batch is launched: with fused_qa a layer's q|k|v projection and attention are ONE launch (csrc/dec_qa.hip), which
-    # probe 1 then times (K / V rows + the q|k|v weights), and probe 0 is the three linears left
-    fused_qa, chain_mode, launches_per_layer = model.decode_structure()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, gathered, n_dec)
+    if args.full:
+        # the same passes strictly one after the other (staging + H2D + planning exposed in front of every pass)
+        dt_serial = run_leg(model, clips, n_dec, args.steps, 1, world, gathered, inclusive=True)
+        # the same passes with the batch already resident in HBM (no staging copy / H2D / planning in the timed region)
+        dt_res = run_leg(model, clips, n_dec, args.steps, 1, world, gathered, inclusive=False)
+        probe = {name: model.kernel_probe(which, 20) for which, name in ((0, "layer_gemv"), (1, "decode_attn"), (2, "lm_head"))}
+        # how the step of this batch is launched: with fused_qa a layer's q|k|v projection and attention are ONE launch (csrc/dec_qa.hip), which
+        # probe 1 then times (K / V rows + the q|k|v weights), and probe 0 is the three linears left
+        fused_qa, chain_mode, launches_per_layer = model.decode_structure()
 
     extras = {}
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         # BASELINE's metric is quoted at batch {1, 8, 32}: the smaller batches on the same engine, same timed region
         for b in (1, 8):
             if b < B:
@@ -332,6 +354,36 @@ def main():
     if rank == 0:
         audio_s = world * B * args.seconds * args.steps
         ms_step = dt / args.steps * 1e3
+        wname = "bf16" if args.bits == 16 else f"MLX {args.bits}-bit decoder (packed in HBM), bf16 activations"
+        out = {
+            "metric": "audio-seconds/sec (RTF^-1) Qwen3-ASR-0.6B, 30 s@16 kHz, b=32 per GPU",
+            "value": round(audio_s / dt, 1),
+            "unit": "audio-seconds/sec",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_step, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "bf16", "data": "synthetic",
+            "config": {"workload": f"Qwen3-ASR-0.6B geometry ({wname}), {B} clips x {args.seconds:.0f} s per GPU "
+                                   f"(BASELINE metric's b=32; x8 GPUs = configs[2]), timed region = pcm in host memory -> "
+                                   f"mel + encoder + prompt pass + {n_dec} forced greedy tokens -> token ids in host memory, "
+                                   f"tokens gathered over RCCL",
+                       "clips_per_gpu": B, "clip_seconds": args.seconds, "decode_tokens": n_dec, "weights": wname,
+                       "sharding": f"dp{world} (independent clips, weights replicated)"},
+            "rtf": round(dt / audio_s, 7),
+            "stage_ms": {"mel": round(stage_ms[0], 3), "encoder": round(stage_ms[1], 3),
+                         "prompt_pass": round(stage_ms[2], 3), "decode": round(stage_ms[3], 3),
+                         "decode_steps": steps_done},
+            "timed_region": "K consecutive passes pipelined like a serving loop: the next pass's host -> pinned -> HBM staging runs under the "
+                            "current pass's kernels (qasr_batch_stage); each pass = host pcm -> mel + encoder + prompt pass + decode -> host tokens",
+            "stage_roofline": stage_roofline(B, args.seconds, n_dec, stage_ms, steps_done, args.bits),
+        }
+    if rank == 0 and args.full:
+        out.update({
+            "serial_inclusive_value": round(audio_s / dt_serial, 1),
+            "serial_inclusive_note": "the same passes one strictly after the other: staging copy + H2D + planning exposed in front of every pass",
+            "resident_value": round(audio_s / dt_res, 1),
+            "resident_note": "same passes with the batch already in HBM (qasr_batch_rewind): no staging copy / H2D / planning timed",
+        })
         # dominant kernel by GPU time (profiles/*_bench_kernel_stats.csv): decode_attention_mfma_kernel
         dom_ms, dom_bytes = probe["decode_attn"]
         traffic, traffic_note = None, None
@@ -377,33 +429,6 @@ def main():
                        "frac": round(gemv_bytes / gemv_ms / 1e6 / HBM_PEAK_GBS, 4), "bytes_per_layer": gemv_bytes,
                        "avg_ms_per_layer": round(gemv_ms, 5), "avg_ms_per_launch": round(gemv_ms / n_gemv, 5),
                        "share_of_gpu_time": round(share_gemv, 3)}
-        wname = "bf16" if args.bits == 16 else f"MLX {args.bits}-bit decoder (packed in HBM), bf16 activations"
-        out = {
-            "metric": "audio-seconds/sec (RTF^-1) Qwen3-ASR-0.6B, 30 s@16 kHz, b=32 per GPU",
-            "value": round(audio_s / dt, 1),
-            "unit": "audio-seconds/sec",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_step, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "bf16", "data": "synthetic",
-            "config": {"workload": f"Qwen3-ASR-0.6B geometry ({wname}), {B} clips x {args.seconds:.0f} s per GPU "
-                                   f"(BASELINE metric's b=32; x8 GPUs = configs[2]), timed region = pcm in host memory -> "
-                                   f"mel + encoder + prompt pass + {n_dec} forced greedy tokens -> token ids in host memory, "
-                                   f"tokens gathered over RCCL",
-                       "clips_per_gpu": B, "clip_seconds": args.seconds, "decode_tokens": n_dec, "weights": wname,
-                       "sharding": f"dp{world} (independent clips, weights replicated)"},
-            "rtf": round(dt / audio_s, 7),
-            "stage_ms": {"mel": round(stage_ms[0], 3), "encoder": round(stage_ms[1], 3),
-                         "prompt_pass": round(stage_ms[2], 3), "decode": round(stage_ms[3], 3),
-                         "decode_steps": steps_done},
-            "timed_region": "K consecutive passes pipelined like a serving loop: the next pass's host -> pinned -> HBM staging runs under the "
-                            "current pass's kernels (qasr_batch_stage); each pass = host pcm -> mel + encoder + prompt pass + decode -> host tokens",
-            "serial_inclusive_value": round(audio_s / dt_serial, 1),
-            "serial_inclusive_note": "the same passes one strictly after the other: staging copy + H2D + planning exposed in front of every pass",
-            "resident_value": round(audio_s / dt_res, 1),
-            "resident_note": "same passes with the batch already in HBM (qasr_batch_rewind): no staging copy / H2D / planning timed",
-            "stage_roofline": stage_roofline(B, args.seconds, n_dec, stage_ms, steps_done, args.bits),
-        }
         attn_obj = {"bound": "hbm",
                     "kernel": ("decode_qa_kernel (one launch = one decoder layer's q|k|v projection AND attention for all batch rows: the K and V "
                                "rows of every row's context and the 8.39 MB of q|k|v weights are streamed once; the stream is requested while the "
@@ -443,7 +468,7 @@ def main():
         if extras:
             out["batches"] = extras
     model.close()
-    if rank == 0 and world == 1 and not args.no_extras and args.bits == 16:
+    if rank == 0 and args.full and world == 1 and not args.no_extras and args.bits == 16:
         # the reference's shipped checkpoints are MLX 4-bit: same workload on a synthetic 4-bit checkpoint,
         # packed weights in HBM (csrc/dec_quant.hip).  Reported beside the bf16 headline, never as `value`.
         log("building the MLX-4bit engine ...")
@@ -462,7 +487,7 @@ def main():
                            "note": "synthetic weights quantised with mlx's affine scheme (group 64); decode-step products in the "
                                    "reference's f32-dequantised form, prompt pass on bf16(scale*q+bias) like its many-row kernel"}
         m4.close()
-    if rank == 0 and world == 1 and not args.no_extras and args.bits == 16:
+    if rank == 0 and args.full and world == 1 and not args.no_extras and args.bits == 16:
         try:
             out["passes_in_flight"] = lanes_leg(sd, clips, n_dec, max(args.steps, 3 * args.lanes), args.seconds, cap, args.lanes)
             log(f"{args.lanes} passes in flight: {out['passes_in_flight']['value']} audio-s/s")
@@ -472,7 +497,7 @@ def main():
             log(f"{args.lanes} passes in flight, MLX 4-bit: {q['value']} audio-s/s")
         except Exception as ex:          # noqa: BLE001 -- a failed side leg must not lose the headline line
             out["passes_in_flight"] = {"error": str(ex)}
-    if rank == 0 and world == 1 and not args.no_extras and args.omnilingual:
+    if rank == 0 and args.full and world == 1 and not args.no_extras and args.omnilingual:
         # BASELINE configs[3]: the wav2vec2-CTC family at the same batch x clip length, one engine at a time (the Qwen3 engines are closed)
         out["omnilingual"] = {}
         for variant in [v for v in args.omnilingual.split(",") if v]:
@@ -482,7 +507,7 @@ def main():
             except Exception as ex:      # noqa: BLE001 -- a failed side leg must not lose the headline line
                 out["omnilingual"][variant] = {"error": str(ex)}
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sd, clips[0], n_dec)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -1,11 +1,12 @@
 #!/bin/bash
 # SQ counters of the prompt / decode attention kernels in one short pass of the bench workload
 cd "$GRAFT_REPO_ROOT"
+mkdir -p scratch/tmp
 export TMPDIR=/tmp
-rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d gpurun_out/pmc_attn -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --decode-tokens 8 > gpurun_out/pmc_attn.log 2>&1 || tail -5 gpurun_out/pmc_attn.log
+rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d scratch/tmp/pmc_attn -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --decode-tokens 8 > scratch/tmp/pmc_attn.log 2>&1 || tail -5 scratch/tmp/pmc_attn.log
 python3 - <<'PY'
 import csv, glob, collections, os
-f = sorted(glob.glob('gpurun_out/pmc_attn/**/*counter_collection.csv', recursive=True), key=os.path.getmtime)[-1]
+f = sorted(glob.glob('scratch/tmp/pmc_attn/**/*counter_collection.csv', recursive=True), key=os.path.getmtime)[-1]
 rows = list(csv.DictReader(open(f)))
 agg = collections.defaultdict(lambda: collections.defaultdict(lambda: [0, 0.0]))
 dur = collections.defaultdict(lambda: [0, 0.0])
