@@ -20,6 +20,8 @@
  *   StreamingMelPreprocessor.extract / extractRaw / extractStreaming, TDTGreedyDecoder.decode, RNNTGreedyDecoder.decode,
  *   ParakeetVocabulary / NemotronVocabulary, StreamingSession.pushAudio   (file:line at each declaration)
  *        -> qasr_nemo_mel_*, qasr_tdt_greedy_decode, qasr_rnnt_greedy_decode, qasr_sp_vocab_*, qasr_stream_chunker_*
+ *   SileroVADModel (Sources/SpeechVAD/SileroVAD.swift, SileroModel.swift) and the speech-core VAD vtable (VoicePipeline.swift:470-492)
+ *        -> qasr_vad_* (file:line at the declarations)
  *   Stage entry points (no reference counterpart; they expose R1-R8 of SURVEY.md section 8a so
  *   each kernel can be diffed against the oracle in isolation): qasr_mel, qasr_encode,
  *   qasr_prefill_logits, qasr_decode_forced.
@@ -261,6 +263,8 @@ int qasr_set_tuning(const char* key, int value);
  * other inside the launch (csrc/dec_qa.hip: q|k|v projection + attention in one launch; every wait is bounded and ends in QASR_ERR_HIP,
  * never in a hang).  Such a launch needs its whole grid resident at once: an engine that runs concurrently with OTHER engines on the same
  * GPU (qasr_dp_* with a device listed more than once sets this itself) must be marked shared = 1 and then keeps to ordinary launches.
+ * A Silero VAD created with order_with = this engine (qasr_vad_create) runs on the engine's stream, between its launches, and needs no
+ * mark; a VAD with a stream of its own on the same GPU is another user like a second engine.
  * No reference counterpart (the reference runs one model instance per process). */
 int qasr_set_shared_device(qasr_engine* engine, int shared);
 int qasr_get_tuning(const char* key, int* value);
@@ -415,6 +419,63 @@ int qasr_nemo_mel_extract(qasr_nemo_mel* m, int variant, const float* const* pcm
 int qasr_nemo_mel_reset_stats(qasr_nemo_mel* m, int stream);        /* resetRunningStats; stream < 0: every stream */
 /* device time of the last extract in ms (HIP events: H2D + kernels + D2H) and whether it replayed the captured graph */
 int qasr_nemo_mel_timing(const qasr_nemo_mel* m, float* ms, int* was_graph);
+
+/* ---- Silero VAD v5 (csrc/vad_silero.hip, csrc/api_vad.cpp) ------------------------------------------------------------------
+ * SileroVADModel (Sources/SpeechVAD/SileroVAD.swift:39-321) with its MLX network (SileroModel.swift:1-186), rebuilt as two HIP launches
+ * per call: a parallel front end (STFT magnitudes, four convolutions, LSTM input projection) and a per-stream recurrence.  One object
+ * holds max_streams independent streams (LSTM h, c and the 64-sample context in HBM), each one the state of one reference instance.
+ *   SileroVADModel.fromPretrained (:229-305, MLX engine; SileroWeightLoading.swift)  -> qasr_vad_create (model_dir/model.safetensors)
+ *   processChunk (:108-130) / resetState (:148-157)                                   -> qasr_vad_process (B streams at once) / qasr_vad_reset
+ *   detectSpeech (:168-220)                                                            -> qasr_vad_detect_speech (stream 0), qasr_vad_probs
+ *   VADPipeline.binarize + filterDurations (Sources/SpeechVAD/VADPipeline.swift:117-181) -> qasr_vad_binarize
+ *   StreamingVADProvider / VoiceActivityDetectionModel conformances (:308-321)        -> sc_vad_vtable_t via qasr_vad_vtable
+ * Sharing a GPU with an engine: pass it as order_with and every VAD call is issued on that engine's stream, so it never runs while the
+ * engine's fused decode launch needs all its workgroups resident (see qasr_set_shared_device).  The engine must outlive the VAD, and the
+ * two are driven from one thread at a time, like the engine itself.  Without order_with the VAD has a stream of its own and then counts
+ * as another user of the GPU for qasr_set_shared_device.  The same threading rule as the engine: one object, one thread at a time. */
+typedef struct qasr_vad qasr_vad;
+/* VADConfig.sileroDefault (Sources/SpeechVAD/Configuration.swift:84-91); windowDuration / stepRatio are set by detectSpeech itself */
+typedef struct qasr_vad_config {
+    float onset, offset, min_speech_duration, min_silence_duration;
+} qasr_vad_config;
+/* speech-core VAD vtable, field order as built at Sources/SpeechCore/VoicePipeline.swift:470-492 (its C header is not in the reference
+ * tree; the types follow the Swift closures).  process_chunk takes exactly 512 samples at 16 kHz; on any failure it answers 0 (the
+ * reference's CoreML path: `(try? ...) ?? 0.0`) with the message in qasr_vad_last_error. */
+typedef struct sc_vad_vtable_t {
+    void* context;
+    float (*process_chunk)(void* ctx, const float* samples, size_t length);
+    void (*reset)(void* ctx);
+    int32_t (*input_sample_rate)(void* ctx);
+    size_t (*chunk_size)(void* ctx);
+} sc_vad_vtable_t;
+int qasr_vad_default_config(qasr_vad_config* out);
+/* Loads and checks every key and shape of model_dir/model.safetensors (f32, f16 or bf16 on disk, widened to f32) before any HIP call:
+ * missing file or key -> QASR_ERR_IO, wrong shape or dtype -> QASR_ERR_INVALID, the key named in qasr_vad_last_error(NULL).
+ * order_with: an engine on `device` whose stream orders the VAD's work, or NULL. */
+int qasr_vad_create(int device, const char* model_dir, int max_streams, qasr_engine* order_with, qasr_vad** out);
+void qasr_vad_destroy(qasr_vad* v);
+const char* qasr_vad_last_error(const qasr_vad* v);                 /* v may be NULL: last create() failure */
+int qasr_vad_reset(qasr_vad* v, int stream);                        /* resetState; stream < 0: every stream */
+/* processChunk of B distinct streams at once: chunks [B][512] -> probs [B], each stream's state advanced.  stream_ids NULL = row index.
+ * Replays one captured graph per B (H2D, two kernels, D2H). */
+int qasr_vad_process(qasr_vad* v, const float* chunks, const int32_t* stream_ids, size_t B, float* probs);
+/* detectSpeech's probability loop for B whole buffers (distinct streams, B <= max_streams): each row's stream is reset, walked in
+ * 512-sample chunks (the last one zero-padded) and keeps its final state.  probs [B][stride] (zero past a row's chunks),
+ * n_chunks[b] = ceil(n[b] / 512) (may be NULL).  Bit-identical to feeding the same chunks through qasr_vad_process. */
+int qasr_vad_probs(qasr_vad* v, const float* const* pcm, const size_t* n, size_t B, const int32_t* stream_ids, float* probs, size_t stride,
+                   int32_t* n_chunks);
+/* VADPipeline.binarize with detectSpeech's frame duration (f32: (n * 0.032) / n per frame).  Pure CPU.  segments [cap][2] = start, end
+ * in seconds; returns the segment count (only the first cap written) or -status.  cfg NULL = sileroDefault. */
+int qasr_vad_binarize(const float* probs, size_t n, const qasr_vad_config* cfg, float* segments, size_t cap);
+/* detectSpeech on stream 0: count of segments (as qasr_vad_binarize) or -status; sample_rate != 16000 -> -QASR_ERR_UNSUPPORTED
+ * (the reference resamples with AVAudioConverter). */
+int qasr_vad_detect_speech(qasr_vad* v, const float* pcm, size_t n, int sample_rate, const qasr_vad_config* cfg, float* segments,
+                           size_t cap);
+int qasr_vad_vtable(qasr_vad* v, int stream, sc_vad_vtable_t* out);  /* context owned by v, valid until qasr_vad_destroy */
+/* device time of the last process / probs call in ms (HIP events on the work stream: H2D + kernels + D2H) and whether it was a graph */
+int qasr_vad_timing(const qasr_vad* v, float* ms, int* was_graph);
+/* a stream's LSTM h [128], c [128] and context [64] (any pointer may be NULL); no reference counterpart (tests) */
+int qasr_vad_state(qasr_vad* v, int stream, float* h, float* c, float* context);
 
 /* transducer greedy loops (pure CPU).  The caller owns the networks and their state:
  *   decoder_step(ctx, token)  advance the prediction network with `token` (the loops prime it with the blank id where the reference does)

@@ -77,6 +77,20 @@ class ScSttVtable(C.Structure):
                 ("end_stream", C.c_void_p), ("cancel_stream", C.c_void_p)]
 
 
+class QasrVadConfig(C.Structure):
+    _fields_ = [("onset", C.c_float), ("offset", C.c_float), ("min_speech_duration", C.c_float), ("min_silence_duration", C.c_float)]
+
+
+VAD_PROCESS_FN = C.CFUNCTYPE(C.c_float, C.c_void_p, C.POINTER(C.c_float), C.c_size_t)
+VAD_RESET_FN = C.CFUNCTYPE(None, C.c_void_p)
+VAD_CHUNK_FN = C.CFUNCTYPE(C.c_size_t, C.c_void_p)
+
+
+class ScVadVtable(C.Structure):
+    _fields_ = [("context", C.c_void_p), ("process_chunk", VAD_PROCESS_FN), ("reset", VAD_RESET_FN),
+                ("input_sample_rate", SC_RATE_FN), ("chunk_size", VAD_CHUNK_FN)]
+
+
 _P = C.POINTER
 _F = _P(C.c_float)
 _I = _P(C.c_int32)
@@ -171,6 +185,18 @@ SIGNATURES = {
     "qasr_nemo_mel_extract": (C.c_int, [_E, C.c_int, _P(_F), _P(C.c_size_t), C.c_size_t, _I, _F, C.c_size_t, _I, C.c_int]),
     "qasr_nemo_mel_reset_stats": (C.c_int, [_E, C.c_int]),
     "qasr_nemo_mel_timing": (C.c_int, [_E, _F, _P(C.c_int)]),
+    "qasr_vad_default_config": (C.c_int, [_P(QasrVadConfig)]),
+    "qasr_vad_create": (C.c_int, [C.c_int, C.c_char_p, C.c_int, _E, _P(_E)]),
+    "qasr_vad_destroy": (None, [_E]),
+    "qasr_vad_last_error": (C.c_char_p, [_E]),
+    "qasr_vad_reset": (C.c_int, [_E, C.c_int]),
+    "qasr_vad_process": (C.c_int, [_E, _F, _I, C.c_size_t, _F]),
+    "qasr_vad_probs": (C.c_int, [_E, _P(_F), _P(C.c_size_t), C.c_size_t, _I, _F, C.c_size_t, _I]),
+    "qasr_vad_binarize": (C.c_int, [_F, C.c_size_t, _P(QasrVadConfig), _F, C.c_size_t]),
+    "qasr_vad_detect_speech": (C.c_int, [_E, _F, C.c_size_t, C.c_int, _P(QasrVadConfig), _F, C.c_size_t]),
+    "qasr_vad_vtable": (C.c_int, [_E, C.c_int, _P(ScVadVtable)]),
+    "qasr_vad_timing": (C.c_int, [_E, _F, _P(C.c_int)]),
+    "qasr_vad_state": (C.c_int, [_E, C.c_int, _F, _F, _F]),
     "qasr_transducer_default_config": (C.c_int, [C.c_char_p, _P(QasrTransducerConfig)]),
     "qasr_tdt_greedy_decode": (C.c_int, [_P(QasrTransducerConfig), _P(QasrTransducerCallbacks), C.c_int32, _I, _F, C.c_int32, _F]),
     "qasr_rnnt_greedy_decode": (C.c_int, [_P(QasrTransducerConfig), _P(QasrTransducerCallbacks), C.c_int32, C.c_int32, _I, _F, C.c_int32, _I]),

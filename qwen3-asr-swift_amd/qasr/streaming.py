@@ -4,8 +4,8 @@ Reference: Sources/Qwen3ASR/StreamingASR.swift:7-277 (TranscriptionSegment, Stre
 longestCommonPrefix) and Sources/SpeechVAD/StreamingVADProcessor.swift:5-227 (VADEvent, four-state hysteresis machine),
 Sources/SpeechVAD/Configuration.swift:84-91 (VADConfig.sileroDefault).
 
-What is NOT here: the Silero VAD network itself (SpeechVAD/SileroVAD.swift -- a separate model, outside this repo's hot
-path).  `StreamingVADProcessor` therefore takes any `process_chunk(512 float32 samples) -> speech probability` callable
+The Silero VAD network itself (SpeechVAD/SileroVAD.swift) is `qasr.vad.SileroVADModel` on the device (`StreamingASR.with_vad`).
+`StreamingVADProcessor` takes any `process_chunk(512 float32 samples) -> speech probability` callable
 (the Swift shim keeps passing `SileroVADModel.processChunk`); everything downstream of the probability -- hysteresis,
 duration filtering, segment bookkeeping, force-splits, partial results, the calls into `transcribe` -- follows the
 reference line by line.
@@ -145,6 +145,21 @@ class StreamingASR:
 
     def __init__(self, asr_model, vad_process_chunk, vad_reset=None):
         self.asr, self.vad_process_chunk, self.vad_reset = asr_model, vad_process_chunk, vad_reset
+        self.vad_model = None
+
+    @classmethod
+    def with_vad(cls, asr_model, vad_model):
+        """StreamingASR with the device Silero VAD (qasr.vad.SileroVADModel, stream 0): `transcribe_stream` calls its process_chunk /
+        reset_state chunk by chunk like the reference; the batched forms get every probability of a buffer from one device call."""
+        s = cls(asr_model, vad_model.process_chunk, vad_model.reset_state)
+        s.vad_model = vad_model
+        return s
+
+    def _replay(self, probs):
+        """A process_chunk stand-in that hands out precomputed probabilities in order (the walk asks for exactly one per chunk, in the
+        order detectSpeech computes them; the device gives bit-identical values either way)."""
+        it = iter(np.asarray(probs, dtype=np.float32).tolist())
+        return lambda chunk: next(it)
 
     def _transcribe(self, samples, a, b, cfg):
         return self.asr.transcribe(samples[a:b], sample_rate=SAMPLE_RATE, language=cfg.language, max_tokens=cfg.max_tokens,
@@ -226,10 +241,40 @@ class StreamingASR:
         if cfg.emit_partial_results:
             raise ValueError("partial results need the sequential form (each one re-transcribes a growing span)")
         samples = np.ascontiguousarray(audio, dtype=np.float32)
-        spans = []
-        self._walk(samples, cfg, lambda kind, a, b, t0, t1: spans.append((kind, a, b, float(t0), float(t1))))
+        probs = self.vad_model.probs([samples], stream_ids=[0])[0] if self.vad_model is not None else None
+        spans = self._spans(samples, cfg, probs)
         if not spans:
             return []
+        return self._segments(spans, self._transcribe_spans([samples] * len(spans), spans, cfg))
+
+    def transcribe_streams_batched(self, audios, config: StreamingASRConfig = None):
+        """`transcribe_stream_batched` of many 16 kHz buffers at once (needs `with_vad`): the VAD of every buffer in one device call
+        (groups of max_streams rows), then every span of every buffer in ragged batches of <= max_batch.  -> one list per buffer,
+        equal to `transcribe_stream_batched` applied buffer by buffer."""
+        if self.vad_model is None:
+            raise ValueError("transcribe_streams_batched needs the device VAD (StreamingASR.with_vad)")
+        cfg = config or StreamingASRConfig()
+        if cfg.emit_partial_results:
+            raise ValueError("partial results need the sequential form (each one re-transcribes a growing span)")
+        bufs = [np.ascontiguousarray(a, dtype=np.float32) for a in audios]
+        probs = self.vad_model.probs(bufs)
+        spans = [self._spans(b, cfg, p) for b, p in zip(bufs, probs)]
+        flat_src = [bufs[i] for i, sp in enumerate(spans) for _ in sp]
+        flat = [s for sp in spans for s in sp]
+        texts = self._transcribe_spans(flat_src, flat, cfg) if flat else []
+        out, k = [], 0
+        for sp in spans:
+            out.append(self._segments(sp, texts[k:k + len(sp)]))
+            k += len(sp)
+        return out
+
+    def _spans(self, samples, cfg, probs=None):
+        spans = []
+        walker = self if probs is None else StreamingASR(self.asr, self._replay(probs))
+        walker._walk(samples, cfg, lambda kind, a, b, t0, t1: spans.append((kind, a, b, float(t0), float(t1))))
+        return spans
+
+    def _transcribe_spans(self, sources, spans, cfg):
         opts = {}
         if cfg.language:
             opts["language_ids"] = self.asr.encode_text("language " + cfg.language)
@@ -238,8 +283,13 @@ class StreamingASR:
         max_b = getattr(getattr(self.asr, "cfg", None), "max_batch", len(spans)) or len(spans)
         texts = []
         for i in range(0, len(spans), max_b):
-            toks = self.asr.transcribe_batch([samples[a:b] for _, a, b, _, _ in spans[i:i + max_b]], max_tokens=cfg.max_tokens, **opts)
+            clips = [src[a:b] for src, (_, a, b, _, _) in zip(sources[i:i + max_b], spans[i:i + max_b])]
+            toks = self.asr.transcribe_batch(clips, max_tokens=cfg.max_tokens, **opts)
             texts += [self.asr.detokenize(t).strip() for t in toks]
+        return texts
+
+    @staticmethod
+    def _segments(spans, texts):
         out, index = [], 0
         for (kind, _, _, t0, t1), text in zip(spans, texts):
             if text:

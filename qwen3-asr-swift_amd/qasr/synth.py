@@ -205,3 +205,81 @@ def synth_omnilingual_state_dict(cfg, seed=0, bits=0, dtype=torch.float32, sink=
     sd["encoder.layer_norm.bias"] = rnd(D, std=0.05)
     lin("final_proj", cfg.vocab, D)
     return sd
+
+
+# ---- Silero VAD v5 (Sources/SpeechVAD/SileroModel.swift; keys and MLX layouts of SileroWeightLoading.swift) -------------------------
+SILERO_SHAPES = {
+    "stft.weight": (258, 256, 1),
+    "encoder.0.weight": (128, 3, 129), "encoder.0.bias": (128,),
+    "encoder.1.weight": (64, 3, 128), "encoder.1.bias": (64,),
+    "encoder.2.weight": (64, 3, 64), "encoder.2.bias": (64,),
+    "encoder.3.weight": (128, 3, 64), "encoder.3.bias": (128,),
+    "lstm.Wx": (512, 128), "lstm.Wh": (512, 128), "lstm.bias": (512,),
+    "decoder.weight": (1, 1, 128), "decoder.bias": (1,),
+}
+
+
+def synth_silero_state_dict(seed: int = 0) -> dict:
+    """Seeded Silero-shaped weights (float32 numpy, reference key names and layouts: conv weights [out, k, in]).
+
+    stft.weight is a real Hann-windowed DFT basis (rows 0..128 cos, 129..257 -sin; scaled by 1/16), so the magnitudes behave like the
+    real model's.  The rest is fan-in scaled with a positive lean in the encoder, the g / o gates and the decoder, and negative biases,
+    so that silence gives a low probability and loud frames a high one (the hysteresis then has something to find)."""
+    rng = np.random.default_rng(77 + seed)
+    n = np.arange(256)
+    hann = 0.5 - 0.5 * np.cos(2 * np.pi * n / 256)
+    k = np.arange(129)[:, None]
+    ang = 2 * np.pi * k * n[None, :] / 256
+    stft = np.concatenate([hann * np.cos(ang), -hann * np.sin(ang)], 0) / 16.0
+    sd = {"stft.weight": stft[:, :, None]}
+    for i, (co, ci) in enumerate([(128, 129), (64, 128), (64, 64), (128, 64)]):
+        fan = 3 * ci
+        sd[f"encoder.{i}.weight"] = (rng.standard_normal((co, 3, ci)) + 0.35) / np.sqrt(fan)
+        sd[f"encoder.{i}.bias"] = -0.002 * np.abs(rng.standard_normal(co))
+    wx = rng.standard_normal((512, 128)) / np.sqrt(128)
+    wx[256:] += 0.6 / np.sqrt(128)                                     # g and o gates lean positive with the encoder output
+    sd["lstm.Wx"] = wx
+    sd["lstm.Wh"] = 0.5 * rng.standard_normal((512, 128)) / np.sqrt(128)
+    b = 0.1 * rng.standard_normal(512)
+    b[128:256] += 1.0                                                  # forget gate
+    b[256:384] -= 1.0                                                  # g: negative cell input in silence
+    sd["lstm.bias"] = b
+    sd["decoder.weight"] = (np.abs(rng.standard_normal((1, 1, 128))) * 0.6 / np.sqrt(128))
+    sd["decoder.bias"] = np.array([-2.0])
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in sd.items()}
+
+
+def write_silero_safetensors(sd: dict, model_dir: str, dtype: str = "F32", drop=(), reshape=None) -> str:
+    """Writes `sd` as model_dir/model.safetensors (dtype F32 | F16 | BF16).  `drop`: keys left out, `reshape`: {key: shape} written with a
+    wrong shape (both for the loader's error tests).  Returns the file path."""
+    import json
+    import os
+    os.makedirs(model_dir, exist_ok=True)
+    header, blobs, off = {}, [], 0
+    for key in sorted(sd):
+        if key in drop:
+            continue
+        a = np.asarray(sd[key], dtype=np.float32)
+        if reshape and key in reshape:
+            a = np.resize(a, reshape[key])
+        if dtype == "F32":
+            raw = a.astype("<f4").tobytes()
+        elif dtype == "F16":
+            raw = a.astype("<f2").tobytes()
+        elif dtype == "BF16":
+            u = a.astype("<f4").view("<u4")
+            raw = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype("<u2").tobytes()
+        else:
+            raise ValueError(dtype)
+        header[key] = {"dtype": dtype, "shape": list(a.shape), "data_offsets": [off, off + len(raw)]}
+        blobs.append(raw)
+        off += len(raw)
+    h = json.dumps(header).encode()
+    h += b" " * ((8 - len(h) % 8) % 8)
+    path = os.path.join(model_dir, "model.safetensors")
+    with open(path, "wb") as f:
+        f.write(len(h).to_bytes(8, "little"))
+        f.write(h)
+        for raw in blobs:
+            f.write(raw)
+    return path
