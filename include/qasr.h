@@ -22,6 +22,8 @@
  *        -> qasr_nemo_mel_*, qasr_tdt_greedy_decode, qasr_rnnt_greedy_decode, qasr_sp_vocab_*, qasr_stream_chunker_*
  *   SileroVADModel (Sources/SpeechVAD/SileroVAD.swift, SileroModel.swift) and the speech-core VAD vtable (VoicePipeline.swift:470-492)
  *        -> qasr_vad_* (file:line at the declarations)
+ *   WeSpeakerModel / SpeakerEmbeddingModel (Sources/SpeechVAD/WeSpeaker.swift, WeSpeakerModel.swift, MelFeatureExtractor.swift;
+ *   Sources/AudioCommon/Protocols.swift:249-256)  -> qasr_spk_* (file:line at the declarations)
  *   Stage entry points (no reference counterpart; they expose R1-R8 of SURVEY.md section 8a so
  *   each kernel can be diffed against the oracle in isolation): qasr_mel, qasr_encode,
  *   qasr_prefill_logits, qasr_decode_forced.
@@ -264,7 +266,8 @@ int qasr_set_tuning(const char* key, int value);
  * never in a hang).  Such a launch needs its whole grid resident at once: an engine that runs concurrently with OTHER engines on the same
  * GPU (qasr_dp_* with a device listed more than once sets this itself) must be marked shared = 1 and then keeps to ordinary launches.
  * A Silero VAD created with order_with = this engine (qasr_vad_create) runs on the engine's stream, between its launches, and needs no
- * mark; a VAD with a stream of its own on the same GPU is another user like a second engine.
+ * mark; a VAD with a stream of its own on the same GPU is another user like a second engine.  The same holds for a WeSpeaker model
+ * (qasr_spk_create): ordered on this engine it needs no mark, with a stream of its own it is another user of the GPU.
  * No reference counterpart (the reference runs one model instance per process). */
 int qasr_set_shared_device(qasr_engine* engine, int shared);
 int qasr_get_tuning(const char* key, int* value);
@@ -476,6 +479,48 @@ int qasr_vad_vtable(qasr_vad* v, int stream, sc_vad_vtable_t* out);  /* context 
 int qasr_vad_timing(const qasr_vad* v, float* ms, int* was_graph);
 /* a stream's LSTM h [128], c [128] and context [64] (any pointer may be NULL); no reference counterpart (tests) */
 int qasr_vad_state(qasr_vad* v, int stream, float* h, float* c, float* context);
+
+/* ---- WeSpeaker ResNet34 speaker embeddings (csrc/spk_wespeaker.hip, csrc/spk_conv.h, csrc/api_spk.cpp) ----------------------
+ * WeSpeakerModel (Sources/SpeechVAD/WeSpeaker.swift:37-231, MLX engine) with its network (WeSpeakerModel.swift:67-170) and front end
+ * (MelFeatureExtractor.swift:120-214), rebuilt as HIP launches over a ragged batch packed along the time axis:
+ *   WeSpeakerModel.fromPretrained (:97-171, MLX; WeSpeakerWeightLoading.swift:15-33) -> qasr_spk_create (model_dir/model.safetensors)
+ *   embed(audio:sampleRate:) (:178-213; SpeakerEmbeddingModel, Protocols.swift:249-256)   -> qasr_spk_embed, qasr_spk_embed_batch
+ *   cosineSimilarity (:217-229)                                                           -> qasr_spk_cosine_similarity
+ *   isLoaded / unload / memoryFootprint (WeSpeaker+Memory.swift:3-19)                     -> qasr_spk_is_loaded / _unload / _memory_footprint
+ *   embeddingDimension / inputSampleRate (:62, :65)                                      -> qasr_spk_embedding_dim / _input_sample_rate
+ * Sharing a GPU with an engine: as for the VAD, pass it as order_with and every call is issued on that engine's stream; without
+ * order_with the model has a stream of its own and counts as another user of the GPU for qasr_set_shared_device.  The engine must
+ * outlive the model.  One object, one thread at a time.
+ * Precision: bf16 MFMA operands (3x3 / shortcut weights, stored activations), f32 accumulation, epilogues, front end, pooling, linear
+ * and normalisation.  A clip's embedding is bit-identical alone or in any batch, and run to run. */
+typedef struct qasr_spk qasr_spk;
+/* fromPretrained from a local directory.  Every key, shape and dtype is checked before any HIP call: missing file or key ->
+ * QASR_ERR_IO, wrong shape or dtype or an unknown key (the reference loads with verify: .noUnusedKeys) -> QASR_ERR_INVALID, the key
+ * named in qasr_spk_last_error(NULL).  max_batch_samples: PCM samples one device pass holds (0 = 64 x 10 s); the workspace is sized
+ * from it.  order_with: an engine on `device` whose stream orders the model's work, or NULL. */
+int qasr_spk_create(int device, const char* model_dir, size_t max_batch_samples, qasr_engine* order_with, qasr_spk** out);
+void qasr_spk_destroy(qasr_spk* s);
+const char* qasr_spk_last_error(const qasr_spk* s);                 /* s may be NULL: last create() failure */
+int qasr_spk_is_loaded(const qasr_spk* s);                          /* isLoaded (WeSpeaker+Memory.swift:4) */
+int qasr_spk_unload(qasr_spk* s);                                   /* unload (:6-13): later calls return QASR_ERR_NOT_LOADED */
+size_t qasr_spk_memory_footprint(const qasr_spk* s);                /* memoryFootprint (:15-18): parameter bytes as stored, 0 unloaded */
+int qasr_spk_embedding_dim(void);                                   /* 256 (WeSpeaker.swift:62) */
+int qasr_spk_input_sample_rate(void);                               /* 16000 (WeSpeaker.swift:65) */
+/* embed(audio:sampleRate:) (WeSpeaker.swift:178-213): out[256], L2-normalised.  sample_rate != 16000 -> QASR_ERR_UNSUPPORTED (the
+ * reference resamples with AVAudioConverter); n == 0 -> QASR_ERR_EMPTY_AUDIO (the reference traps on an empty array). */
+int qasr_spk_embed(qasr_spk* s, const float* pcm, size_t n, int sample_rate, float* out);
+/* B clips of 16 kHz PCM in one call (DiarizationPipeline.swift:369-430 calls embed once per window and speaker): out [B][256].  A call
+ * larger than the workspace runs as several device passes; a single clip longer than max_batch_samples -> QASR_ERR_CAPACITY; an empty
+ * clip -> QASR_ERR_EMPTY_AUDIO.  Each row is bit-identical to qasr_spk_embed of the same clip. */
+int qasr_spk_embed_batch(qasr_spk* s, const float* const* pcm, const size_t* n, size_t B, float* out);
+/* stage entry point, no reference counterpart: MelFeatureExtractor.extractRaw (:120-214) after CMN, [T_b][80] per clip at
+ * feats + b * stride (stride >= 80 * T_b floats); n_frames[b] = T_b (may be NULL). */
+int qasr_spk_fbank(qasr_spk* s, const float* const* pcm, const size_t* n, size_t B, float* feats, size_t stride, int32_t* n_frames);
+int qasr_spk_num_frames(size_t n);                                  /* T = n / 160 + 1 (extractRaw's frame count) */
+/* cosineSimilarity (WeSpeaker.swift:217-229), pure CPU: 0 for empty input or a zero denominator */
+float qasr_spk_cosine_similarity(const float* a, const float* b, size_t n);
+/* device time of the last embed / fbank call in ms (HIP events on the work stream: H2D + kernels + D2H of every pass) */
+int qasr_spk_timing(const qasr_spk* s, float* ms);
 
 /* transducer greedy loops (pure CPU).  The caller owns the networks and their state:
  *   decoder_step(ctx, token)  advance the prediction network with `token` (the loops prime it with the blank id where the reference does)

@@ -197,6 +197,20 @@ SIGNATURES = {
     "qasr_vad_vtable": (C.c_int, [_E, C.c_int, _P(ScVadVtable)]),
     "qasr_vad_timing": (C.c_int, [_E, _F, _P(C.c_int)]),
     "qasr_vad_state": (C.c_int, [_E, C.c_int, _F, _F, _F]),
+    "qasr_spk_create": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t, _E, _P(_E)]),
+    "qasr_spk_destroy": (None, [_E]),
+    "qasr_spk_last_error": (C.c_char_p, [_E]),
+    "qasr_spk_is_loaded": (C.c_int, [_E]),
+    "qasr_spk_unload": (C.c_int, [_E]),
+    "qasr_spk_memory_footprint": (C.c_size_t, [_E]),
+    "qasr_spk_embedding_dim": (C.c_int, []),
+    "qasr_spk_input_sample_rate": (C.c_int, []),
+    "qasr_spk_embed": (C.c_int, [_E, _F, C.c_size_t, C.c_int, _F]),
+    "qasr_spk_embed_batch": (C.c_int, [_E, _P(_F), _P(C.c_size_t), C.c_size_t, _F]),
+    "qasr_spk_fbank": (C.c_int, [_E, _P(_F), _P(C.c_size_t), C.c_size_t, _F, C.c_size_t, _I]),
+    "qasr_spk_num_frames": (C.c_int, [C.c_size_t]),
+    "qasr_spk_cosine_similarity": (C.c_float, [_F, _F, C.c_size_t]),
+    "qasr_spk_timing": (C.c_int, [_E, _F]),
     "qasr_transducer_default_config": (C.c_int, [C.c_char_p, _P(QasrTransducerConfig)]),
     "qasr_tdt_greedy_decode": (C.c_int, [_P(QasrTransducerConfig), _P(QasrTransducerCallbacks), C.c_int32, _I, _F, C.c_int32, _F]),
     "qasr_rnnt_greedy_decode": (C.c_int, [_P(QasrTransducerConfig), _P(QasrTransducerCallbacks), C.c_int32, C.c_int32, _I, _F, C.c_int32, _I]),

@@ -252,6 +252,10 @@ def synth_silero_state_dict(seed: int = 0) -> dict:
 def write_silero_safetensors(sd: dict, model_dir: str, dtype: str = "F32", drop=(), reshape=None) -> str:
     """Writes `sd` as model_dir/model.safetensors (dtype F32 | F16 | BF16).  `drop`: keys left out, `reshape`: {key: shape} written with a
     wrong shape (both for the loader's error tests).  Returns the file path."""
+    return _write_safetensors(sd, model_dir, dtype, drop, reshape)
+
+
+def _write_safetensors(sd: dict, model_dir: str, dtype: str = "F32", drop=(), reshape=None) -> str:
     import json
     import os
     os.makedirs(model_dir, exist_ok=True)
@@ -269,6 +273,8 @@ def write_silero_safetensors(sd: dict, model_dir: str, dtype: str = "F32", drop=
         elif dtype == "BF16":
             u = a.astype("<f4").view("<u4")
             raw = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype("<u2").tobytes()
+        elif dtype == "F64":                                           # a dtype no loader accepts (error tests)
+            raw = a.astype("<f8").tobytes()
         else:
             raise ValueError(dtype)
         header[key] = {"dtype": dtype, "shape": list(a.shape), "data_offsets": [off, off + len(raw)]}
@@ -283,3 +289,60 @@ def write_silero_safetensors(sd: dict, model_dir: str, dtype: str = "F32", drop=
         for raw in blobs:
             f.write(raw)
     return path
+
+
+WESPEAKER_BLOCKS = (3, 4, 6, 3)
+
+
+def wespeaker_tensor_shapes() -> dict:
+    """key -> shape of every WeSpeaker ResNet34 tensor (WeSpeakerModel.swift; MLX conv layout [out, kH, kW, in])."""
+    s = {"conv1.weight": (32, 3, 3, 1), "conv1.bias": (32,)}
+    for st, nb in enumerate(WESPEAKER_BLOCKS):
+        C, Cp = 32 << st, (16 << st if st else 32)
+        for i in range(nb):
+            cin = Cp if i == 0 else C
+            p = f"layer{st + 1}.{i}."
+            s[p + "conv1.weight"], s[p + "conv1.bias"] = (C, 3, 3, cin), (C,)
+            s[p + "conv2.weight"], s[p + "conv2.bias"] = (C, 3, 3, C), (C,)
+            if st > 0 and i == 0:
+                s[p + "shortcut.weight"], s[p + "shortcut.bias"] = (C, 1, 1, Cp), (C,)
+    s["embedding.weight"], s["embedding.bias"] = (256, 5120), (256,)
+    return s
+
+
+def synth_wespeaker_state_dict(seed: int = 0) -> dict:
+    """Seeded WeSpeaker-shaped weights (float32 numpy, reference keys and layouts), shaped like a BN-fused ResNet34:
+    He-scaled 3x3 convs with a small negative bias after each (a fused BN's shift), the second conv of every block and the shortcut scaled
+    down so the 16 residual sums keep activations O(1); the embedding reads the pooled statistics with zero-mean rows over each
+    (mean | std) half so the shared positive level of post-ReLU statistics does not dominate and different inputs give clearly
+    different embeddings."""
+    rng = np.random.default_rng(4242 + seed)
+    sd = {}
+    for k, shp in wespeaker_tensor_shapes().items():
+        if k.endswith(".bias"):
+            continue
+        fan = int(np.prod(shp[1:]))
+        w = rng.standard_normal(shp) * np.sqrt(2.0 / fan)
+        if ".conv2." in k:
+            w *= 0.35
+        elif ".shortcut." in k:
+            w *= 0.7
+        sd[k] = w
+    for k, shp in wespeaker_tensor_shapes().items():
+        if k.endswith(".bias") and k != "embedding.bias":
+            sd[k] = -0.05 + 0.05 * rng.standard_normal(shp)
+    e = rng.standard_normal((256, 5120)) / np.sqrt(5120)
+    for h in (slice(0, 2560), slice(2560, 5120)):
+        e[:, h] -= e[:, h].mean(axis=1, keepdims=True)
+    sd["embedding.weight"] = e
+    sd["embedding.bias"] = 0.01 * rng.standard_normal(256)
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in sd.items()}
+
+
+def write_wespeaker_safetensors(sd: dict, model_dir: str, dtype: str = "F32", drop=(), extra=(), reshape=None) -> str:
+    """Writes `sd` as model_dir/model.safetensors (dtype F32 | F16 | BF16; F64 for the dtype error).  `drop`: keys left out, `extra`:
+    (key, array) pairs added (unknown keys), `reshape`: {key: shape} written with a wrong shape.  Returns the file path."""
+    d = dict(sd)
+    for k, v in (extra.items() if isinstance(extra, dict) else extra):
+        d[k] = np.asarray(v, dtype=np.float32)
+    return _write_safetensors(d, model_dir, dtype, drop, reshape)
