@@ -1,4 +1,5 @@
 // api.cpp -- extern "C" boundary (include/qasr.h).  Exceptions never cross it.
+#include "api_guard.h"
 #include "engine.h"
 #include "ctc_engine.h"
 #include <cstdlib>
@@ -8,24 +9,15 @@
 
 using qasr::Engine;
 
-static thread_local std::string g_create_error;
+// engine and Omnilingual handles keep their message in impl->last_error (api_dp.cpp and the bindings read it through qasr_last_error)
+// and share one create-error slot
+static std::string& error_slot(const qasr_engine* e) { return e && e->impl ? e->impl->last_error : create_error<qasr_engine>(); }
 
-static int fail(qasr_engine* e, int code, const std::string& msg) {
-    // a reported HIP failure must not stay behind as the runtime's sticky "last error" (a later launch check would blame itself for it)
-    if (code == QASR_ERR_HIP) (void)hipGetLastError();
-    if (e && e->impl) e->impl->last_error = msg; else g_create_error = msg;
-    return code;
-}
-
-// every guarded entry first makes the engine's device current for the calling thread (the HIP current device is per thread: an engine
+// a guarded engine entry first makes the engine's device current for the calling thread (the HIP current device is per thread: an engine
 // per GPU may be driven from any thread, e.g. the worker threads of qasr_dp_*)
-#define QASR_GUARD(e, body)                                                          \
-    try { (e)->impl->bind_device(); body; return QASR_OK; }                          \
-    catch (const qasr::HipError& ex) { return fail(e, QASR_ERR_HIP, ex.what()); }    \
-    catch (const qasr::NotLoaded& ex) { return fail(e, QASR_ERR_NOT_LOADED, ex.what()); } \
-    catch (const std::invalid_argument& ex) { return fail(e, QASR_ERR_INVALID, ex.what()); } \
-    catch (const std::length_error& ex) { return fail(e, QASR_ERR_CAPACITY, ex.what()); }    \
-    catch (const std::exception& ex) { return fail(e, QASR_ERR_INVALID, ex.what()); }
+template <class F> static int on_device(qasr_engine* e, F&& f) {
+    return guarded(e, [&] { e->impl->bind_device(); f(); });
+}
 
 static bool contains(const std::string& s, const char* sub) { return s.find(sub) != std::string::npos; }
 
@@ -85,26 +77,22 @@ int qasr_default_config(const char* preset, qasr_config* c) {
 int qasr_create(const char* model_dir, const qasr_config* cfg, qasr_engine** out) {
     if (!cfg || !out) return QASR_ERR_INVALID;
     *out = nullptr;
-    qasr_engine* e = new qasr_engine();
-    try {
+    return guarded_create(out, model_dir ? QASR_ERR_IO : QASR_ERR_INVALID, [&](qasr_engine* e) {
         e->impl.reset(new Engine(*cfg));
         if (model_dir) { e->impl->load_directory(model_dir); e->impl->finalize(); }
-    } catch (const qasr::HipError& ex) { g_create_error = ex.what(); delete e; (void)hipGetLastError(); return QASR_ERR_HIP; }
-    catch (const std::exception& ex) { g_create_error = ex.what(); delete e; return model_dir ? QASR_ERR_IO : QASR_ERR_INVALID; }
-    *out = e;
-    return QASR_OK;
+    });
 }
 
 int qasr_set_tensor(qasr_engine* e, const char* name, const void* host, int dtype, const int64_t* shape, int ndim) {
     if (!e || !name || !host || !shape || ndim <= 0) return QASR_ERR_INVALID;
-    QASR_GUARD(e, e->impl->set_tensor(name, host, dtype, shape, ndim));
+    return on_device(e, [&] { e->impl->set_tensor(name, host, dtype, shape, ndim); });
 }
-int qasr_finalize(qasr_engine* e) { if (!e) return QASR_ERR_INVALID; QASR_GUARD(e, e->impl->finalize()); }
+int qasr_finalize(qasr_engine* e) { if (!e) return QASR_ERR_INVALID; return on_device(e, [&] { e->impl->finalize(); }); }
 int qasr_is_loaded(const qasr_engine* e) { return e && e->impl->loaded(); }
-int qasr_unload(qasr_engine* e) { if (!e) return QASR_ERR_INVALID; QASR_GUARD(e, e->impl->unload()); }
+int qasr_unload(qasr_engine* e) { if (!e) return QASR_ERR_INVALID; return on_device(e, [&] { e->impl->unload(); }); }
 size_t qasr_memory_footprint(const qasr_engine* e) { return e ? e->impl->memory_footprint() : 0; }
 void qasr_destroy(qasr_engine* e) { delete e; }
-const char* qasr_last_error(const qasr_engine* e) { return e ? e->impl->last_error.c_str() : g_create_error.c_str(); }
+const char* qasr_last_error(const qasr_engine* e) { return error_slot(e).c_str(); }
 int qasr_input_sample_rate(const qasr_engine*) { return 16000; }
 
 int qasr_num_mel_frames(size_t n) { return qasr::mel_num_frames((long)n); }
@@ -112,7 +100,7 @@ int qasr_num_mel_frames(size_t n) { return qasr::mel_num_frames((long)n); }
 int qasr_mel(qasr_engine* e, const float* pcm, size_t n, float* out) {
     if (!e || !pcm || !out) return QASR_ERR_INVALID;
     if (n == 0) return fail(e, QASR_ERR_EMPTY_AUDIO, "empty clip");
-    QASR_GUARD(e, e->impl->mel_host(pcm, n, out));
+    return on_device(e, [&] { e->impl->mel_host(pcm, n, out); });
 }
 
 int qasr_num_audio_tokens(const qasr_engine* e, int n_frames) { return e ? e->impl->num_audio_tokens(n_frames) : -1; }
@@ -120,17 +108,17 @@ int qasr_num_audio_tokens(const qasr_engine* e, int n_frames) { return e ? e->im
 int qasr_encode(qasr_engine* e, const float* mel, int n_frames, float* out) {
     if (!e || !mel || !out) return QASR_ERR_INVALID;
     if (!e->impl->loaded()) return fail(e, QASR_ERR_NOT_LOADED, "weights not finalized");
-    QASR_GUARD(e, e->impl->encode_host(mel, n_frames, out));
+    return on_device(e, [&] { e->impl->encode_host(mel, n_frames, out); });
 }
 
 int qasr_set_vocab(qasr_engine* e, const int32_t* ids, const char* const* tokens, size_t n) {
     if (!e || !ids || !tokens) return QASR_ERR_INVALID;
-    QASR_GUARD(e, e->impl->set_vocab(ids, tokens, n));
+    return on_device(e, [&] { e->impl->set_vocab(ids, tokens, n); });
 }
 
 int qasr_set_merges(qasr_engine* e, const char* merges_txt) {
     if (!e || !merges_txt) return QASR_ERR_INVALID;
-    QASR_GUARD(e, e->impl->set_merges(merges_txt));
+    return on_device(e, [&] { e->impl->set_merges(merges_txt); });
 }
 
 int qasr_encode_text(qasr_engine* e, const char* utf8, int32_t* ids, int32_t cap) {
@@ -145,50 +133,48 @@ int qasr_encode_text(qasr_engine* e, const char* utf8, int32_t* ids, int32_t cap
 
 int qasr_detokenize(qasr_engine* e, const int32_t* tokens, int32_t n, char* buf, size_t cap) {
     if (!e || !tokens || !buf || cap == 0 || n < 0) return -1;
-    try {
-        std::string t = e->impl->detokenize(tokens, n, true);
-        if (t.size() + 1 > cap) { fail(e, QASR_ERR_CAPACITY, "detokenize: buffer too small"); return -1; }
-        std::memcpy(buf, t.c_str(), t.size() + 1);
-        return (int)t.size();
-    } catch (const std::exception& ex) { fail(e, QASR_ERR_INVALID, ex.what()); return -1; }
+    int len = -1;
+    if (guarded(e, [&] { len = copy_out(e->impl->detokenize(tokens, n, true), buf, cap); })) return -1;
+    if (len < 0) fail(e, QASR_ERR_CAPACITY, "detokenize: buffer too small");
+    return len;
 }
 
 int qasr_batch_begin(qasr_engine* e, const float* const* pcm, const size_t* n, size_t B, const qasr_options* opt) {
     if (!e || !pcm || !n) return QASR_ERR_INVALID;
     if (!e->impl->loaded()) return fail(e, QASR_ERR_NOT_LOADED, "weights not finalized");
     for (size_t b = 0; b < B; ++b) if (n[b] == 0 || !pcm[b]) return fail(e, QASR_ERR_EMPTY_AUDIO, "empty clip in batch");
-    QASR_GUARD(e, e->impl->batch_begin(pcm, n, B, opt));
+    return on_device(e, [&] { e->impl->batch_begin(pcm, n, B, opt); });
 }
 int qasr_batch_stage(qasr_engine* e, const float* const* pcm, const size_t* n, size_t B) {
     if (!e || !pcm || !n) return QASR_ERR_INVALID;
-    QASR_GUARD(e, e->impl->batch_stage(pcm, n, B));
+    return on_device(e, [&] { e->impl->batch_stage(pcm, n, B); });
 }
 int qasr_batch_begin_staged(qasr_engine* e, const qasr_options* opt) {
     if (!e) return QASR_ERR_INVALID;
-    QASR_GUARD(e, e->impl->batch_begin_staged(opt));
+    return on_device(e, [&] { e->impl->batch_begin_staged(opt); });
 }
-int qasr_batch_run(qasr_engine* e) { if (!e) return QASR_ERR_INVALID; QASR_GUARD(e, e->impl->batch_run()); }
-int qasr_batch_rewind(qasr_engine* e) { if (!e) return QASR_ERR_INVALID; QASR_GUARD(e, e->impl->batch_rewind()); }
-int qasr_batch_sync(qasr_engine* e) { if (!e) return QASR_ERR_INVALID; QASR_GUARD(e, e->impl->batch_sync()); }
+int qasr_batch_run(qasr_engine* e) { if (!e) return QASR_ERR_INVALID; return on_device(e, [&] { e->impl->batch_run(); }); }
+int qasr_batch_rewind(qasr_engine* e) { if (!e) return QASR_ERR_INVALID; return on_device(e, [&] { e->impl->batch_rewind(); }); }
+int qasr_batch_sync(qasr_engine* e) { if (!e) return QASR_ERR_INVALID; return on_device(e, [&] { e->impl->batch_sync(); }); }
 int qasr_batch_tokens(qasr_engine* e, int32_t* tokens, int32_t* lens) {
     if (!e || !tokens || !lens) return QASR_ERR_INVALID;
     if (!e->impl->loaded()) return fail(e, QASR_ERR_NOT_LOADED, "weights not finalized");
-    QASR_GUARD(e, e->impl->batch_tokens(tokens, lens));
+    return on_device(e, [&] { e->impl->batch_tokens(tokens, lens); });
 }
 int qasr_batch_timings(qasr_engine* e, float ms[5], int32_t* n_steps) {
     if (!e || !ms) return QASR_ERR_INVALID;
-    QASR_GUARD(e, e->impl->batch_timings(ms, n_steps));
+    return on_device(e, [&] { e->impl->batch_timings(ms, n_steps); });
 }
 int qasr_kernel_probe(qasr_engine* e, int which, int reps, float* avg_ms, double* bytes_per_launch) {
     if (!e || !avg_ms || !bytes_per_launch || reps <= 0 || which < 0 || which > 7) return QASR_ERR_INVALID;
-    QASR_GUARD(e, e->impl->kernel_probe(which, reps, avg_ms, bytes_per_launch));
+    return on_device(e, [&] { e->impl->kernel_probe(which, reps, avg_ms, bytes_per_launch); });
 }
 
 int qasr_gemm_probe(qasr_engine* e, const uint16_t* A, const uint16_t* W, const float* bias, int M, int N, int K, int form,
                     int reps, float* out, float* avg_ms) {
     if (!e || !A || !W || !out || M <= 0 || N <= 0 || K <= 0 || K % 8 || N % 4 || form < -1 || form > 2 || reps <= 0)
         return QASR_ERR_INVALID;
-    QASR_GUARD(e, e->impl->gemm_probe(A, W, bias, M, N, K, form, reps, out, avg_ms));
+    return on_device(e, [&] { e->impl->gemm_probe(A, W, bias, M, N, K, form, reps, out, avg_ms); });
 }
 
 int qasr_transcribe_batch(qasr_engine* e, const float* const* pcm, const size_t* n, size_t B, int sample_rate,
@@ -276,10 +262,12 @@ int qasr_find_trailing_plateau(const float* start_times, size_t n, float toleran
 }
 
 static int split_for(qasr_engine* e, const char* text, const char* language, std::vector<std::pair<std::string, std::string>>& pairs) {
-    if (qasr::aligner_needs_nl_tokenizer(language ? language : "English"))
-        return fail(e, QASR_ERR_UNSUPPORTED, "the reference splits this language with Apple's NLTokenizer: pass words to qasr_align_words");
-    pairs = qasr::aligner_split_word_pairs(text);
-    return QASR_OK;
+    try {
+        if (qasr::aligner_needs_nl_tokenizer(language ? language : "English"))
+            return fail(e, QASR_ERR_UNSUPPORTED, "the reference splits this language with Apple's NLTokenizer: pass words to qasr_align_words");
+        pairs = qasr::aligner_split_word_pairs(text);
+        return QASR_OK;
+    } catch (const std::exception& ex) { return fail(e, QASR_ERR_INVALID, ex.what()); }
 }
 
 int qasr_align_prepare(qasr_engine* e, const char* text, const char* language, int32_t* ids, int32_t ids_cap,
@@ -303,9 +291,8 @@ int qasr_align_raw(qasr_engine* e, const float* pcm, size_t n, const int32_t* sl
     if (!e || !pcm || !slotted_ids || !ts_positions || !raw_indices || n_ids < 0 || n_ts < 0) return QASR_ERR_INVALID;
     if (n == 0) return fail(e, QASR_ERR_EMPTY_AUDIO, "empty clip");
     if (!e->impl->loaded()) return fail(e, QASR_ERR_NOT_LOADED, "weights not finalized");
-    QASR_GUARD(e, {
+    return on_device(e, [&] {
         std::vector<std::vector<int32_t>> raw;
-        e->impl->bind_device();
         e->impl->align_forward(&pcm, &n, 1, {std::vector<int32_t>(slotted_ids, slotted_ids + n_ids)},
                                {std::vector<int32_t>(ts_positions, ts_positions + n_ts)}, raw, logits);
         if (!raw.empty()) std::memcpy(raw_indices, raw[0].data(), raw[0].size() * sizeof(int32_t));
@@ -318,9 +305,8 @@ static int align_common(qasr_engine* e, const float* pcm, size_t n, int sample_r
     if (sample_rate != 16000) return fail(e, QASR_ERR_INVALID, "input must be 16 kHz mono (no resampler: AVAudioConverter is not reproducible)");
     if (n == 0) return fail(e, QASR_ERR_EMPTY_AUDIO, "empty clip");
     if (!e->impl->loaded()) return fail(e, QASR_ERR_NOT_LOADED, "weights not finalized");
-    QASR_GUARD(e, {
+    return on_device(e, [&] {
         const std::string text = long_text ? long_text : "";
-        e->impl->bind_device();
         const int passes = e->impl->align_words(pcm, n, pairs, long_form, long_text ? &text : nullptr);
         out->words = e->impl->al_view.data();
         out->n_words = e->impl->al_view.size();
@@ -334,8 +320,7 @@ int qasr_align(qasr_engine* e, const float* pcm, size_t n, int sample_rate, cons
                qasr_alignment* out) {
     if (!e || !pcm || !text || !out) return QASR_ERR_INVALID;
     std::vector<std::pair<std::string, std::string>> pairs;
-    try { if (int rc = split_for(e, text, language, pairs)) return rc; }
-    catch (const std::exception& ex) { return fail(e, QASR_ERR_INVALID, ex.what()); }
+    if (int rc = split_for(e, text, language, pairs)) return rc;
     return align_common(e, pcm, n, sample_rate, pairs, false, out);
 }
 
@@ -343,8 +328,7 @@ int qasr_align_long(qasr_engine* e, const float* pcm, size_t n, int sample_rate,
                     qasr_alignment* out) {
     if (!e || !pcm || !text || !out) return QASR_ERR_INVALID;
     std::vector<std::pair<std::string, std::string>> pairs;
-    try { if (int rc = split_for(e, text, language, pairs)) return rc; }
-    catch (const std::exception& ex) { return fail(e, QASR_ERR_INVALID, ex.what()); }
+    if (int rc = split_for(e, text, language, pairs)) return rc;
     return align_common(e, pcm, n, sample_rate, pairs, true, out, text);
 }
 
@@ -357,11 +341,9 @@ int qasr_align_batch(qasr_engine* e, const float* const* pcm, const size_t* n, s
     for (size_t b = 0; b < B; ++b) {
         if (!pcm[b] || !texts[b]) return fail(e, QASR_ERR_INVALID, "align_batch: null clip or text");
         if (n[b] == 0) return fail(e, QASR_ERR_EMPTY_AUDIO, "empty clip");
-        try { if (int rc = split_for(e, texts[b], language, pairs[b])) return rc; }
-        catch (const std::exception& ex) { return fail(e, QASR_ERR_INVALID, ex.what()); }
+        if (int rc = split_for(e, texts[b], language, pairs[b])) return rc;
     }
-    QASR_GUARD(e, {
-        e->impl->bind_device();
+    return on_device(e, [&] {
         e->impl->align_batch(pcm, n, B, pairs);
         for (size_t b = 0; b < B; ++b) {
             auto& r = e->impl->al_batch[b];
@@ -416,12 +398,12 @@ int qasr_stt_vtable(qasr_engine* e, sc_stt_vtable_t* out) {
 
 int qasr_decode_structure(qasr_engine* e, int* fused_qa, int* chain, int* launches_per_layer) {
     if (!e || !fused_qa || !chain || !launches_per_layer) return QASR_ERR_INVALID;
-    QASR_GUARD(e, e->impl->decode_structure(fused_qa, chain, launches_per_layer));
+    return on_device(e, [&] { e->impl->decode_structure(fused_qa, chain, launches_per_layer); });
 }
 
 int qasr_set_shared_device(qasr_engine* e, int shared) {
     if (!e) return QASR_ERR_INVALID;
-    QASR_GUARD(e, e->impl->set_shared_device(shared != 0));
+    return on_device(e, [&] { e->impl->set_shared_device(shared != 0); });
 }
 
 int qasr_set_tuning(const char* key, int value) {
@@ -436,12 +418,12 @@ int qasr_get_tuning(const char* key, int* value) {
 int qasr_prefill_logits(qasr_engine* e, const float* audio_embeds, int n_audio, const qasr_options* opt, float* logits) {
     if (!e || !logits || (n_audio > 0 && !audio_embeds)) return QASR_ERR_INVALID;
     if (!e->impl->loaded()) return fail(e, QASR_ERR_NOT_LOADED, "weights not finalized");
-    QASR_GUARD(e, e->impl->prefill_logits_host(audio_embeds, n_audio, opt, logits));
+    return on_device(e, [&] { e->impl->prefill_logits_host(audio_embeds, n_audio, opt, logits); });
 }
 
 int qasr_decode_forced(qasr_engine* e, const int32_t* tokens, int n, float* logits) {
     if (!e || !tokens || !logits || n < 0) return QASR_ERR_INVALID;
-    QASR_GUARD(e, e->impl->decode_forced_host(tokens, n, logits));
+    return on_device(e, [&] { e->impl->decode_forced_host(tokens, n, logits); });
 }
 
 // ---- Omnilingual ASR (wav2vec2 + CTC) -------------------------------------------------------------------
@@ -450,18 +432,7 @@ int qasr_decode_forced(qasr_engine* e, const int32_t* tokens, int n, float* logi
 struct qasr_ctc_engine {
     std::unique_ptr<qasr::CtcEngine> impl;
 };
-static int cfail(qasr_ctc_engine* e, int code, const std::string& msg) {
-    if (code == QASR_ERR_HIP) (void)hipGetLastError();
-    if (e && e->impl) e->impl->last_error = msg; else g_create_error = msg;
-    return code;
-}
-#define QASR_CGUARD(e, body)                                                          \
-    try { body; return QASR_OK; }                                                     \
-    catch (const qasr::HipError& ex) { return cfail(e, QASR_ERR_HIP, ex.what()); }    \
-    catch (const qasr::NotLoaded& ex) { return cfail(e, QASR_ERR_NOT_LOADED, ex.what()); } \
-    catch (const std::invalid_argument& ex) { return cfail(e, QASR_ERR_INVALID, ex.what()); } \
-    catch (const std::length_error& ex) { return cfail(e, QASR_ERR_CAPACITY, ex.what()); }    \
-    catch (const std::exception& ex) { return cfail(e, QASR_ERR_INVALID, ex.what()); }
+static std::string& error_slot(const qasr_ctc_engine* e) { return e && e->impl ? e->impl->last_error : create_error<qasr_engine>(); }
 
 extern "C" {
 
@@ -491,45 +462,39 @@ int qasr_ctc_default_config(const char* variant, qasr_ctc_config* c) {
 int qasr_ctc_create(const char* model_dir, const qasr_ctc_config* cfg, qasr_ctc_engine** out) {
     if (!cfg || !out) return QASR_ERR_INVALID;
     *out = nullptr;
-    if (cfg->max_audio_seconds > 40 || cfg->max_audio_seconds <= 0 || cfg->max_batch <= 0) {
-        g_create_error = "omnilingual: max_audio_seconds must be in 1..40 (the reference's cap), max_batch positive";
-        return QASR_ERR_INVALID;
-    }
-    qasr_ctc_engine* e = new qasr_ctc_engine();
-    try {
+    if (cfg->max_audio_seconds > 40 || cfg->max_audio_seconds <= 0 || cfg->max_batch <= 0)
+        return fail<qasr_ctc_engine>(nullptr, QASR_ERR_INVALID, "omnilingual: max_audio_seconds must be in 1..40 (the reference's cap), max_batch positive");
+    return guarded_create(out, model_dir ? QASR_ERR_IO : QASR_ERR_INVALID, [&](qasr_ctc_engine* e) {
         e->impl.reset(new qasr::CtcEngine(*cfg));
         if (model_dir) { e->impl->load_directory(model_dir); e->impl->finalize(); }
-    } catch (const qasr::HipError& ex) { g_create_error = ex.what(); delete e; (void)hipGetLastError(); return QASR_ERR_HIP; }
-    catch (const std::exception& ex) { g_create_error = ex.what(); delete e; return model_dir ? QASR_ERR_IO : QASR_ERR_INVALID; }
-    *out = e;
-    return QASR_OK;
+    });
 }
 int qasr_ctc_set_tensor(qasr_ctc_engine* e, const char* name, const void* host, int dtype, const int64_t* shape, int ndim) {
     if (!e || !name || !host || !shape || ndim <= 0) return QASR_ERR_INVALID;
-    QASR_CGUARD(e, e->impl->set_tensor(name, host, dtype, shape, ndim));
+    return guarded(e, [&] { e->impl->set_tensor(name, host, dtype, shape, ndim); });
 }
-int qasr_ctc_finalize(qasr_ctc_engine* e) { if (!e) return QASR_ERR_INVALID; QASR_CGUARD(e, e->impl->finalize()); }
+int qasr_ctc_finalize(qasr_ctc_engine* e) { if (!e) return QASR_ERR_INVALID; return guarded(e, [&] { e->impl->finalize(); }); }
 int qasr_ctc_set_pieces(qasr_ctc_engine* e, const char* const* texts, const int32_t* types, size_t n) {
     if (!e || (!texts && n)) return QASR_ERR_INVALID;
-    QASR_CGUARD(e, e->impl->set_pieces(texts, types, n));
+    return guarded(e, [&] { e->impl->set_pieces(texts, types, n); });
 }
 int qasr_ctc_is_loaded(const qasr_ctc_engine* e) { return e && e->impl->loaded(); }
-int qasr_ctc_unload(qasr_ctc_engine* e) { if (!e) return QASR_ERR_INVALID; QASR_CGUARD(e, e->impl->unload()); }
+int qasr_ctc_unload(qasr_ctc_engine* e) { if (!e) return QASR_ERR_INVALID; return guarded(e, [&] { e->impl->unload(); }); }
 size_t qasr_ctc_memory_footprint(const qasr_ctc_engine* e) { return e ? e->impl->memory_footprint() : 0; }
 void qasr_ctc_destroy(qasr_ctc_engine* e) { delete e; }
-const char* qasr_ctc_last_error(const qasr_ctc_engine* e) { return e ? e->impl->last_error.c_str() : g_create_error.c_str(); }
+const char* qasr_ctc_last_error(const qasr_ctc_engine* e) { return error_slot(e).c_str(); }
 int qasr_ctc_num_frames(size_t n) { return qasr::CtcEngine::num_frames((long)n); }
 
 static int ctc_run(qasr_ctc_engine* e, const float* const* pcm, const size_t* n, size_t B, int sample_rate,
                    std::vector<std::vector<int32_t>>& collapsed, float* logits) {
-    if (sample_rate != 16000) return cfail(e, QASR_ERR_INVALID, "only 16 kHz input is supported (resampler is out of scope)");
-    if (!e->impl->loaded()) return cfail(e, QASR_ERR_NOT_LOADED, "weights not finalized");
+    if (sample_rate != 16000) return fail(e, QASR_ERR_INVALID, "only 16 kHz input is supported (resampler is out of scope)");
+    if (!e->impl->loaded()) return fail(e, QASR_ERR_NOT_LOADED, "weights not finalized");
     for (size_t b = 0; b < B; ++b) {
-        if (!pcm[b] || n[b] == 0) return cfail(e, QASR_ERR_EMPTY_AUDIO, "empty clip in batch");
+        if (!pcm[b] || n[b] == 0) return fail(e, QASR_ERR_EMPTY_AUDIO, "empty clip in batch");
         // OmnilingualMLXModel.swift:154-159: the 40 s cap is an error, not a truncation
-        if ((double)n[b] / 16000.0 > 40.0) return cfail(e, QASR_ERR_CAPACITY, "input exceeds the Omnilingual cap of 40 s");
+        if ((double)n[b] / 16000.0 > 40.0) return fail(e, QASR_ERR_CAPACITY, "input exceeds the Omnilingual cap of 40 s");
     }
-    QASR_CGUARD(e, {
+    return guarded(e, [&] {
         std::vector<std::vector<int32_t>> frames;
         e->impl->forward(pcm, n, B, frames, logits);
         collapsed.assign(B, {});
@@ -546,7 +511,7 @@ int qasr_ctc_transcribe_batch(qasr_ctc_engine* e, const float* const* pcm, const
     std::vector<std::vector<int32_t>> col;
     if (int rc = ctc_run(e, pcm, n, B, sample_rate, col, nullptr)) return rc;
     for (size_t b = 0; b < B; ++b) {
-        if (col[b].size() > stride) return cfail(e, QASR_ERR_CAPACITY, "ctc_transcribe_batch: id buffer stride too small");
+        if (col[b].size() > stride) return fail(e, QASR_ERR_CAPACITY, "ctc_transcribe_batch: id buffer stride too small");
         std::memcpy(ids + b * stride, col[b].data(), col[b].size() * sizeof(int32_t));
         lens[b] = (int32_t)col[b].size();
     }
@@ -560,9 +525,9 @@ int qasr_ctc_transcribe(qasr_ctc_engine* e, const float* pcm, size_t n, int samp
     std::vector<std::vector<int32_t>> col;
     if (int rc = ctc_run(e, &pcm, &n, 1, sample_rate, col, nullptr)) return rc;
     // no SentencePiece vocabulary: an error, not "" for every clip (the reference cannot exist without one, OmnilingualMLXModel.swift:86-98)
-    if (!e->impl->has_pieces()) return cfail(e, QASR_ERR_NOT_LOADED, "no SentencePiece vocabulary: load tokenizer.model or call qasr_ctc_set_pieces");
+    if (!e->impl->has_pieces()) return fail(e, QASR_ERR_NOT_LOADED, "no SentencePiece vocabulary: load tokenizer.model or call qasr_ctc_set_pieces");
     try { e->impl->result_text = e->impl->detokenize(col[0].data(), (int)col[0].size()); }
-    catch (const std::exception& ex) { return cfail(e, QASR_ERR_INVALID, ex.what()); }
+    catch (const std::exception& ex) { return fail(e, QASR_ERR_INVALID, ex.what()); }
     *text = e->impl->result_text.c_str();
     return QASR_OK;
 }
@@ -575,18 +540,16 @@ int qasr_ctc_logits(qasr_ctc_engine* e, const float* pcm, size_t n, float* logit
 
 int qasr_ctc_detokenize(qasr_ctc_engine* e, const int32_t* ids, int32_t n, char* buf, size_t cap) {
     if (!e || (!ids && n) || !buf || cap == 0 || n < 0) return -1;
-    if (!e->impl->has_pieces()) { cfail(e, QASR_ERR_NOT_LOADED, "no SentencePiece vocabulary"); return -1; }
-    try {
-        std::string t = e->impl->detokenize(ids, n);
-        if (t.size() + 1 > cap) { cfail(e, QASR_ERR_CAPACITY, "detokenize: buffer too small"); return -1; }
-        std::memcpy(buf, t.c_str(), t.size() + 1);
-        return (int)t.size();
-    } catch (const std::exception& ex) { cfail(e, QASR_ERR_INVALID, ex.what()); return -1; }
+    if (!e->impl->has_pieces()) { fail(e, QASR_ERR_NOT_LOADED, "no SentencePiece vocabulary"); return -1; }
+    int len = -1;
+    if (guarded(e, [&] { len = copy_out(e->impl->detokenize(ids, n), buf, cap); })) return -1;
+    if (len < 0) fail(e, QASR_ERR_CAPACITY, "detokenize: buffer too small");
+    return len;
 }
 
 int qasr_ctc_timings(qasr_ctc_engine* e, float ms[4]) {
     if (!e || !ms) return QASR_ERR_INVALID;
-    QASR_CGUARD(e, e->impl->timings(ms));
+    return guarded(e, [&] { e->impl->timings(ms); });
 }
 
 int qasr_ctc_greedy(const float* logits, int32_t T, int32_t V, int32_t valid_frames, int32_t* out) {

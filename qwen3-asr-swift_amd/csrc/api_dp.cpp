@@ -7,6 +7,7 @@
 // clip).  The only cross-device step is the gather of the decoded token streams: every engine copies its [rows, max_new_tokens + 1] int32
 // block device -> host straight into the caller's [B, max_new_tokens + 1] buffer (57 KB per GPU at 32 clips: a host-memory caller has no
 // use for a device-side all-gather; the multi-process form of the same partition, with the RCCL all_gather of that block, is bench.py).
+#include "api_guard.h"
 #include "engine.h"
 #include <algorithm>
 #include <chrono>
@@ -34,8 +35,6 @@ struct qasr_dp {
     std::string last_error;
 };
 
-static thread_local std::string g_dp_create_error;
-
 static void shard_bounds(size_t n_clips, size_t world, size_t rank, size_t* lo, size_t* hi) {      // qasr/dist.py: shard_bounds
     const size_t base = n_clips / world, extra = n_clips % world;
     *lo = rank * base + std::min(rank, extra);
@@ -55,7 +54,7 @@ int qasr_dp_create(const char* model_dir, const qasr_config* cfg, const int32_t*
         qasr_engine* e = nullptr;
         const int rc = qasr_create(model_dir, &c, &e);
         if (rc != QASR_OK) {
-            g_dp_create_error = std::string("device ") + std::to_string(devices[i]) + ": " + qasr_last_error(nullptr);
+            create_error<qasr_dp>() = std::string("device ") + std::to_string(devices[i]) + ": " + qasr_last_error(nullptr);
             for (qasr_engine* p : dp->engines) qasr_destroy(p);
             return rc;
         }
@@ -80,7 +79,7 @@ void qasr_dp_destroy(qasr_dp* dp) {
 
 int qasr_dp_n_devices(const qasr_dp* dp) { return dp ? (int)dp->engines.size() : 0; }
 qasr_engine* qasr_dp_engine(qasr_dp* dp, int32_t i) { return (dp && i >= 0 && (size_t)i < dp->engines.size()) ? dp->engines[(size_t)i] : nullptr; }
-const char* qasr_dp_last_error(const qasr_dp* dp) { return dp ? dp->last_error.c_str() : g_dp_create_error.c_str(); }
+const char* qasr_dp_last_error(const qasr_dp* dp) { return dp ? dp->last_error.c_str() : create_error<qasr_dp>().c_str(); }
 
 static int for_all(qasr_dp* dp, const char* what, int (*fn)(qasr_engine*, void*), void* arg) {
     for (size_t i = 0; i < dp->engines.size(); ++i) {

@@ -1,4 +1,5 @@
 // api_transducer.cpp -- extern "C" boundary of the Parakeet / Nemotron slice (include/qasr.h, last section).  Exceptions never cross it.
+#include "api_guard.h"
 #include "nemo_mel.h"
 #include "transducer.h"
 #include <cstring>
@@ -8,23 +9,11 @@
 
 struct qasr_nemo_mel {
     std::unique_ptr<qasr::NemoMel> impl;
-    std::string last_error;
+    mutable std::string last_error;
 };
+static std::string& error_slot(const qasr_nemo_mel* m) { return m ? m->last_error : create_error<qasr_nemo_mel>(); }
 struct qasr_sp_vocab { qasr::SpVocab v; };
 struct qasr_stream_chunker { qasr::StreamChunker c; };
-
-static thread_local std::string g_nemo_create_error;
-
-static int mfail(qasr_nemo_mel* m, int code, const std::string& msg) {
-    if (code == QASR_ERR_HIP) (void)hipGetLastError();
-    if (m) m->last_error = msg; else g_nemo_create_error = msg;
-    return code;
-}
-#define NEMO_GUARD(m, body)                                                                   \
-    try { body; return QASR_OK; }                                                             \
-    catch (const qasr::HipError& ex) { return mfail(m, QASR_ERR_HIP, ex.what()); }            \
-    catch (const std::length_error& ex) { return mfail(m, QASR_ERR_CAPACITY, ex.what()); }    \
-    catch (const std::exception& ex) { return mfail(m, QASR_ERR_INVALID, ex.what()); }
 
 static bool has(const std::string& s, const char* sub) { return s.find(sub) != std::string::npos; }
 
@@ -70,15 +59,12 @@ extern "C" {
 int qasr_nemo_mel_create(int device, int max_streams, size_t max_samples, float fft_scale, qasr_nemo_mel** out) {
     if (!out) return QASR_ERR_INVALID;
     *out = nullptr;
-    auto* m = new qasr_nemo_mel();
-    try { m->impl = std::make_unique<qasr::NemoMel>(device, max_streams, (long)max_samples, fft_scale); }
-    catch (const qasr::HipError& ex) { g_nemo_create_error = ex.what(); delete m; (void)hipGetLastError(); return QASR_ERR_HIP; }
-    catch (const std::exception& ex) { g_nemo_create_error = ex.what(); delete m; return QASR_ERR_INVALID; }
-    *out = m;
-    return QASR_OK;
+    return guarded_create(out, QASR_ERR_INVALID, [&](qasr_nemo_mel* m) {
+        m->impl = std::make_unique<qasr::NemoMel>(device, max_streams, (long)max_samples, fft_scale);
+    });
 }
 void qasr_nemo_mel_destroy(qasr_nemo_mel* m) { delete m; }
-const char* qasr_nemo_mel_last_error(const qasr_nemo_mel* m) { return m ? m->last_error.c_str() : g_nemo_create_error.c_str(); }
+const char* qasr_nemo_mel_last_error(const qasr_nemo_mel* m) { return error_slot(m).c_str(); }
 int qasr_nemo_mel_num_frames(size_t n) { return qasr::nemo_num_frames((long)n); }
 int qasr_nemo_mel_length(size_t n) { return qasr::nemo_mel_length((long)n); }
 
@@ -86,13 +72,13 @@ int qasr_nemo_mel_extract(qasr_nemo_mel* m, int variant, const float* const* pcm
                           float* out, size_t stride, int32_t* mel_len, int fit) {
     if (!m || !m->impl) return QASR_ERR_INVALID;
     if (B == 0) return QASR_OK;
-    if (!pcm || !n || !out) return mfail(m, QASR_ERR_INVALID, "nemo mel: null argument");
-    NEMO_GUARD(m, nemo_extract(m, variant, pcm, n, B, stream_ids, out, stride, mel_len, fit));
+    if (!pcm || !n || !out) return fail(m, QASR_ERR_INVALID, "nemo mel: null argument");
+    return guarded(m, [&] { nemo_extract(m, variant, pcm, n, B, stream_ids, out, stride, mel_len, fit); });
 }
 
 int qasr_nemo_mel_reset_stats(qasr_nemo_mel* m, int stream) {
     if (!m || !m->impl) return QASR_ERR_INVALID;
-    NEMO_GUARD(m, m->impl->reset_stats(stream));
+    return guarded(m, [&] { m->impl->reset_stats(stream); });
 }
 
 int qasr_nemo_mel_timing(const qasr_nemo_mel* m, float* ms, int* was_graph) {
@@ -192,12 +178,7 @@ int qasr_sp_vocab_count(const qasr_sp_vocab* v) { return v ? (int)v->v.table.siz
 
 int qasr_sp_vocab_decode(const qasr_sp_vocab* v, const int32_t* ids, int32_t n, char* buf, size_t cap) {
     if (!v || (!ids && n) || n < 0 || !buf || cap == 0) return -1;
-    try {
-        const std::string t = v->v.decode(ids, n);
-        if (t.size() + 1 > cap) return -1;
-        std::memcpy(buf, t.c_str(), t.size() + 1);
-        return (int)t.size();
-    } catch (...) { return -1; }
+    try { return copy_out(v->v.decode(ids, n), buf, cap); } catch (...) { return -1; }
 }
 
 int qasr_sp_vocab_decode_words(const qasr_sp_vocab* v, const int32_t* ids, int32_t n_ids, const float* log_probs, int32_t n_lp, char* buf,

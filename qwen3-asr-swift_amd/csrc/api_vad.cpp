@@ -1,4 +1,5 @@
 // api_vad.cpp -- extern "C" boundary of the Silero VAD (include/qasr.h, qasr_vad_*).  Exceptions never cross it.
+#include "api_guard.h"
 #include "vad_silero.h"
 #include <cstring>
 #include <memory>
@@ -8,7 +9,7 @@
 struct qasr_vad_vt_ctx;
 struct qasr_vad {
     std::unique_ptr<qasr::SileroVad> impl;
-    std::string last_error;
+    mutable std::string last_error;
     std::vector<std::unique_ptr<qasr_vad_vt_ctx>> vt;       // one vtable context per stream, made on demand
 };
 struct qasr_vad_vt_ctx {
@@ -16,18 +17,7 @@ struct qasr_vad_vt_ctx {
     int stream;
 };
 
-static thread_local std::string g_vad_create_error;
-
-static int vfail(qasr_vad* v, int code, const std::string& msg) {
-    if (code == QASR_ERR_HIP) (void)hipGetLastError();
-    if (v) v->last_error = msg; else g_vad_create_error = msg;
-    return code;
-}
-#define VAD_GUARD(v, body)                                                                   \
-    try { body; return QASR_OK; }                                                            \
-    catch (const qasr::HipError& ex) { return vfail(v, QASR_ERR_HIP, ex.what()); }           \
-    catch (const std::length_error& ex) { return vfail(v, QASR_ERR_CAPACITY, ex.what()); }   \
-    catch (const std::exception& ex) { return vfail(v, QASR_ERR_INVALID, ex.what()); }
+static std::string& error_slot(const qasr_vad* v) { return v ? v->last_error : create_error<qasr_vad>(); }
 
 static qasr::VadConfig vad_cfg(const qasr_vad_config* c) {
     qasr_vad_config d;
@@ -71,43 +61,40 @@ int qasr_vad_default_config(qasr_vad_config* out) {
 int qasr_vad_create(int device, const char* model_dir, int max_streams, qasr_engine* order_with, qasr_vad** out) {
     if (!out) return QASR_ERR_INVALID;
     *out = nullptr;
-    if (!model_dir) return vfail(nullptr, QASR_ERR_INVALID, "silero vad: model_dir is NULL");
-    if (max_streams <= 0 || max_streams > 4096) return vfail(nullptr, QASR_ERR_INVALID, "silero vad: max_streams in 1..4096");
+    if (!model_dir) return fail<qasr_vad>(nullptr, QASR_ERR_INVALID, "silero vad: model_dir is NULL");
+    if (max_streams <= 0 || max_streams > 4096) return fail<qasr_vad>(nullptr, QASR_ERR_INVALID, "silero vad: max_streams in 1..4096");
     if (order_with && (!order_with->impl || order_with->impl->config().device != device))
-        return vfail(nullptr, QASR_ERR_INVALID, "silero vad: order_with must be an engine on the same device");
-    qasr::SileroHostWeights w;
-    try { w = qasr::silero_load_weights(model_dir); }              // every key and shape checked before any HIP call
-    catch (const qasr::VadLoadError& ex) { return vfail(nullptr, ex.code, ex.what()); }
-    catch (const std::exception& ex) { return vfail(nullptr, QASR_ERR_IO, ex.what()); }
-    auto* v = new qasr_vad();
-    try { v->impl = std::make_unique<qasr::SileroVad>(device, w, max_streams, order_with ? order_with->impl->stream() : nullptr); }
-    catch (const qasr::HipError& ex) { g_vad_create_error = ex.what(); delete v; (void)hipGetLastError(); return QASR_ERR_HIP; }
-    catch (const std::exception& ex) { g_vad_create_error = ex.what(); delete v; return QASR_ERR_INVALID; }
-    *out = v;
-    return QASR_OK;
+        return fail<qasr_vad>(nullptr, QASR_ERR_INVALID, "silero vad: order_with must be an engine on the same device");
+    qasr::CheckedWeights w;
+    try { w = qasr::load_checked_f32(model_dir, "silero vad", qasr::silero_tensor_shapes(), false); }     // all checked before any HIP call
+    catch (const qasr::WeightLoadError& ex) { return fail<qasr_vad>(nullptr, ex.code, ex.what()); }
+    catch (const std::exception& ex) { return fail<qasr_vad>(nullptr, QASR_ERR_IO, ex.what()); }
+    return guarded_create(out, QASR_ERR_INVALID, [&](qasr_vad* v) {
+        v->impl = std::make_unique<qasr::SileroVad>(device, w, max_streams, order_with ? order_with->impl->stream() : nullptr);
+    });
 }
 
 void qasr_vad_destroy(qasr_vad* v) { delete v; }
-const char* qasr_vad_last_error(const qasr_vad* v) { return v ? v->last_error.c_str() : g_vad_create_error.c_str(); }
+const char* qasr_vad_last_error(const qasr_vad* v) { return error_slot(v).c_str(); }
 
 int qasr_vad_reset(qasr_vad* v, int stream) {
     if (!v || !v->impl) return QASR_ERR_INVALID;
-    VAD_GUARD(v, v->impl->reset(stream));
+    return guarded(v, [&] { v->impl->reset(stream); });
 }
 
 int qasr_vad_process(qasr_vad* v, const float* chunks, const int32_t* stream_ids, size_t B, float* probs) {
     if (!v || !v->impl) return QASR_ERR_INVALID;
     if (B == 0) return QASR_OK;
-    if (!chunks || !probs) return vfail(v, QASR_ERR_INVALID, "silero vad: null argument");
-    VAD_GUARD(v, v->impl->process(chunks, stream_ids, B, probs));
+    if (!chunks || !probs) return fail(v, QASR_ERR_INVALID, "silero vad: null argument");
+    return guarded(v, [&] { v->impl->process(chunks, stream_ids, B, probs); });
 }
 
 int qasr_vad_probs(qasr_vad* v, const float* const* pcm, const size_t* n, size_t B, const int32_t* stream_ids, float* probs, size_t stride,
                    int32_t* n_chunks) {
     if (!v || !v->impl) return QASR_ERR_INVALID;
     if (B == 0) return QASR_OK;
-    if (!pcm || !n || !probs) return vfail(v, QASR_ERR_INVALID, "silero vad: null argument");
-    VAD_GUARD(v, v->impl->probs(pcm, n, B, stream_ids, probs, stride, n_chunks));
+    if (!pcm || !n || !probs) return fail(v, QASR_ERR_INVALID, "silero vad: null argument");
+    return guarded(v, [&] { v->impl->probs(pcm, n, B, stream_ids, probs, stride, n_chunks); });
 }
 
 int qasr_vad_binarize(const float* probs, size_t n, const qasr_vad_config* cfg, float* segments, size_t cap) {
@@ -118,10 +105,10 @@ int qasr_vad_binarize(const float* probs, size_t n, const qasr_vad_config* cfg, 
 int qasr_vad_detect_speech(qasr_vad* v, const float* pcm, size_t n, int sample_rate, const qasr_vad_config* cfg, float* segments, size_t cap) {
     if (!v || !v->impl) return -QASR_ERR_INVALID;
     if (sample_rate != qasr::VAD_RATE) {
-        vfail(v, QASR_ERR_UNSUPPORTED, "silero vad: 16 kHz input only (the reference resamples with AVAudioConverter)");
+        fail(v, QASR_ERR_UNSUPPORTED, "silero vad: 16 kHz input only (the reference resamples with AVAudioConverter)");
         return -QASR_ERR_UNSUPPORTED;
     }
-    if ((!pcm && n) || (!segments && cap)) return -vfail(v, QASR_ERR_INVALID, "silero vad: null argument");
+    if ((!pcm && n) || (!segments && cap)) return -fail(v, QASR_ERR_INVALID, "silero vad: null argument");
     const size_t nc = (n + qasr::VAD_CHUNK - 1) / qasr::VAD_CHUNK;
     std::vector<float> p(nc ? nc : 1);
     const float* rows[1] = {pcm};
@@ -138,7 +125,7 @@ int qasr_vad_detect_speech(qasr_vad* v, const float* pcm, size_t n, int sample_r
 
 int qasr_vad_vtable(qasr_vad* v, int stream, sc_vad_vtable_t* out) {
     if (!v || !v->impl || !out) return QASR_ERR_INVALID;
-    if (stream < 0 || stream >= v->impl->max_streams()) return vfail(v, QASR_ERR_INVALID, "silero vad: stream outside [0, max_streams)");
+    if (stream < 0 || stream >= v->impl->max_streams()) return fail(v, QASR_ERR_INVALID, "silero vad: stream outside [0, max_streams)");
     qasr_vad_vt_ctx* c = nullptr;
     for (auto& p : v->vt) if (p->stream == stream) c = p.get();
     if (!c) { v->vt.push_back(std::make_unique<qasr_vad_vt_ctx>(qasr_vad_vt_ctx{v, stream})); c = v->vt.back().get(); }
@@ -159,7 +146,7 @@ int qasr_vad_timing(const qasr_vad* v, float* ms, int* was_graph) {
 
 int qasr_vad_state(qasr_vad* v, int stream, float* h, float* c, float* context) {
     if (!v || !v->impl) return QASR_ERR_INVALID;
-    VAD_GUARD(v, v->impl->state(stream, h, c, context));
+    return guarded(v, [&] { v->impl->state(stream, h, c, context); });
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 #include <algorithm>
+#include <cstdio>
 #include <cstring>
 
 namespace qasr {
@@ -116,6 +117,45 @@ SafeTensorsDir::SafeTensorsDir(const std::string& dir) {
             entries[kv.first] = e;
         }
     }
+}
+
+static std::string shape_str(const std::vector<int64_t>& s) {
+    std::string r = "[";
+    for (size_t i = 0; i < s.size(); ++i) r += (i ? ", " : "") + std::to_string(s[i]);
+    return r + "]";
+}
+
+CheckedWeights load_checked_f32(const std::string& dir, const char* who,
+                                const std::vector<std::pair<std::string, std::vector<int64_t>>>& shapes, bool refuse_unknown_keys) {
+    const std::string pre = std::string(who) + ": ", path = dir + "/model.safetensors";
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) throw WeightLoadError(QASR_ERR_IO, pre + "cannot open " + path);
+    fclose(f);
+    std::unique_ptr<SafeTensorsDir> st;
+    try { st = std::make_unique<SafeTensorsDir>(dir); }
+    catch (const std::exception& ex) { throw WeightLoadError(QASR_ERR_IO, pre + ex.what()); }
+    if (refuse_unknown_keys)                               // update(parameters:verify: .noUnusedKeys)
+        for (const auto& kv : st->entries) {
+            bool known = false;
+            for (const auto& ks : shapes) known = known || ks.first == kv.first;
+            if (!known) throw WeightLoadError(QASR_ERR_INVALID, pre + "unknown tensor " + kv.first);
+        }
+    CheckedWeights w;
+    for (const auto& ks : shapes) {
+        auto it = st->entries.find(ks.first);
+        if (it == st->entries.end()) throw WeightLoadError(QASR_ERR_IO, pre + "missing tensor " + ks.first);
+        const SafeEntry& e = it->second;
+        if (e.shape != ks.second)
+            throw WeightLoadError(QASR_ERR_INVALID, pre + "tensor " + ks.first + " has shape " + shape_str(e.shape) + ", expected " +
+                                                        shape_str(ks.second));
+        if (e.dtype != "F32" && e.dtype != "F16" && e.dtype != "BF16")
+            throw WeightLoadError(QASR_ERR_INVALID, pre + "tensor " + ks.first + " has dtype " + e.dtype + " (F32 / F16 / BF16)");
+        std::vector<float> v(e.numel());
+        for (size_t i = 0; i < v.size(); ++i) v[i] = safe_elem_f32(e, i);     // MLX promotes to f32 (the samples are f32)
+        w.disk_bytes += e.numel() * (e.dtype == "F32" ? 4 : 2);
+        w.t[ks.first] = std::move(v);
+    }
+    return w;
 }
 
 void Engine::load_directory(const std::string& dir) {

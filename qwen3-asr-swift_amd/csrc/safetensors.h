@@ -3,7 +3,9 @@
 #include <cstdint>
 #include <map>
 #include <memory>
+#include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace qasr {
@@ -28,5 +30,19 @@ private:
     struct Mapping;
     std::vector<std::unique_ptr<Mapping>> maps_;
 };
+
+// A small model's whole checkpoint (Silero VAD, WeSpeaker), widened to f32 in the reference's layouts.
+struct CheckedWeights {
+    std::map<std::string, std::vector<float>> t;
+    size_t disk_bytes = 0;                          // parameter bytes as stored (memoryFootprint)
+};
+struct WeightLoadError : std::runtime_error {      // code: QASR_ERR_IO (missing file / key) or QASR_ERR_INVALID (shape / dtype / unknown key)
+    int code;
+    WeightLoadError(int c, const std::string& m) : std::runtime_error(m), code(c) {}
+};
+// reads <dir>/model.safetensors against a key -> shape table: presence, shape and dtype (F32 / F16 / BF16) of every entry, unknown keys
+// refused on request; messages start with "<who>: ".  Host work only: no HIP call.
+CheckedWeights load_checked_f32(const std::string& dir, const char* who,
+                                const std::vector<std::pair<std::string, std::vector<int64_t>>>& shapes, bool refuse_unknown_keys);
 
 }  // namespace qasr

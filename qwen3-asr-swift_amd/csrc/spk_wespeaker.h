@@ -9,6 +9,7 @@
 // | mean ++ std over time (C*F order) | Linear 5120 -> 256 | L2 normalise.
 #pragma once
 #include "engine.h"
+#include "safetensors.h"
 #include <map>
 #include <string>
 #include <vector>
@@ -20,26 +21,15 @@ constexpr int SPK_COL_ALIGN = 8;        // clips sit at multiples of 8 time colu
 
 __host__ __device__ inline int spk_num_frames(size_t n) { return (int)(n / SPK_HOP) + 1; }
 
-struct SpkHostWeights {
-    std::map<std::string, std::vector<float>> t;    // widened to f32, the reference's layouts
-    size_t disk_bytes = 0;                          // parameter bytes as stored (memoryFootprint)
-};
-
-struct SpkLoadError : std::runtime_error {      // code: QASR_ERR_IO (missing file / key) or QASR_ERR_INVALID (shape / dtype / unknown key)
-    int code;
-    SpkLoadError(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
 // key -> shape of every tensor the network reads (WeSpeakerModel.swift)
+// (MLX layouts); load_checked_f32 checks a checkpoint against it, unknown keys refused, with no HIP call
 const std::vector<std::pair<std::string, std::vector<int64_t>>>& spk_tensor_shapes();
-// reads <dir>/model.safetensors; checks every key, shape and dtype and refuses unknown keys; no HIP call
-SpkHostWeights spk_load_weights(const std::string& dir);
 
 class WeSpeaker {
   public:
     // work: the stream the model's work is ordered on (an engine's stream), nullptr = a stream of its own.
     // max_samples: PCM samples one device pass holds (the workspace is sized from it).
-    WeSpeaker(int device, const SpkHostWeights& w, size_t max_samples, hipStream_t work);
+    WeSpeaker(int device, const CheckedWeights& w, size_t max_samples, hipStream_t work);
     ~WeSpeaker();
     // B clips -> out [B][256]; calls larger than the workspace run as several passes; a clip longer than max_samples: std::length_error
     void embed(const float* const* pcm, const size_t* n, size_t B, float* out);

@@ -19,7 +19,6 @@
 #include "spk_wespeaker.h"
 #include "spk_conv.h"
 #include "mel_core.h"
-#include "safetensors.h"
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -215,44 +214,6 @@ const std::vector<std::pair<std::string, std::vector<int64_t>>>& spk_tensor_shap
     return s;
 }
 
-static std::string spk_shape_str(const std::vector<int64_t>& s) {
-    std::string r = "[";
-    for (size_t i = 0; i < s.size(); ++i) r += (i ? ", " : "") + std::to_string(s[i]);
-    return r + "]";
-}
-
-SpkHostWeights spk_load_weights(const std::string& dir) {
-    const std::string path = dir + "/model.safetensors";
-    FILE* f = fopen(path.c_str(), "rb");
-    if (!f) throw SpkLoadError(QASR_ERR_IO, "wespeaker: cannot open " + path);
-    fclose(f);
-    std::unique_ptr<SafeTensorsDir> st;
-    try { st = std::make_unique<SafeTensorsDir>(dir); }
-    catch (const std::exception& ex) { throw SpkLoadError(QASR_ERR_IO, std::string("wespeaker: ") + ex.what()); }
-    const auto& shapes = spk_tensor_shapes();
-    for (const auto& kv : st->entries) {                   // update(parameters:verify: .noUnusedKeys)
-        bool known = false;
-        for (const auto& ks : shapes) known = known || ks.first == kv.first;
-        if (!known) throw SpkLoadError(QASR_ERR_INVALID, "wespeaker: unknown tensor " + kv.first);
-    }
-    SpkHostWeights w;
-    for (const auto& ks : shapes) {
-        auto it = st->entries.find(ks.first);
-        if (it == st->entries.end()) throw SpkLoadError(QASR_ERR_IO, "wespeaker: missing tensor " + ks.first);
-        const SafeEntry& e = it->second;
-        if (e.shape != ks.second)
-            throw SpkLoadError(QASR_ERR_INVALID, "wespeaker: tensor " + ks.first + " has shape " + spk_shape_str(e.shape) + ", expected " +
-                                                     spk_shape_str(ks.second));
-        if (e.dtype != "F32" && e.dtype != "F16" && e.dtype != "BF16")
-            throw SpkLoadError(QASR_ERR_INVALID, "wespeaker: tensor " + ks.first + " has dtype " + e.dtype + " (F32 / F16 / BF16)");
-        std::vector<float> v(e.numel());
-        for (size_t i = 0; i < v.size(); ++i) v[i] = safe_elem_f32(e, i);
-        w.disk_bytes += e.numel() * (e.dtype == "F32" ? 4 : 2);
-        w.t[ks.first] = std::move(v);
-    }
-    return w;
-}
-
 // HTK mel bank of MelFeatureExtractor.setupMelFilterbank (f32, the reference's formulas) in mel_core.h's sparse table slots
 static void spk_fill_tables(std::vector<float>& t) {
     melc_fill_tables(t, 4.0f);                             // twiddles + power scale (|2X|^2); the Whisper bank it writes is replaced below
@@ -290,7 +251,7 @@ static void spk_fill_tables(std::vector<float>& t) {
 }
 
 // ---- host object --------------------------------------------------------------------------------------------------------
-WeSpeaker::WeSpeaker(int device, const SpkHostWeights& w, size_t max_samples, hipStream_t work)
+WeSpeaker::WeSpeaker(int device, const CheckedWeights& w, size_t max_samples, hipStream_t work)
     : device_(device), max_samples_(max_samples) {
     if (max_samples_ < (size_t)SPK_WIN) throw std::invalid_argument("wespeaker: max_batch_samples below 400");
     cap_clips_ = 1024;

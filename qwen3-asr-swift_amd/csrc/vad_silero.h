@@ -6,6 +6,7 @@
 // magnitudes | 4 x (Conv1d k3 + ReLU): 129->128 s1, 128->64 s2, 64->64 s2, 64->128 s1 | LSTM cell H=128 (i, f, g, o) | sigmoid(decoder(relu h)).
 #pragma once
 #include "engine.h"
+#include "safetensors.h"
 #include <map>
 #include <string>
 #include <vector>
@@ -14,20 +15,9 @@ namespace qasr {
 
 constexpr int VAD_CHUNK = 512, VAD_CTX = 64, VAD_H = 128, VAD_G = 512, VAD_RATE = 16000;
 
-// the weights widened to f32, in the reference's layouts (conv weights [out, k, in], lstm.Wx / Wh [512, 128])
-struct SileroHostWeights {
-    std::map<std::string, std::vector<float>> t;
-};
-
-struct VadLoadError : std::runtime_error {      // code: QASR_ERR_IO (missing file / key) or QASR_ERR_INVALID (shape / dtype)
-    int code;
-    VadLoadError(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
 // key -> shape of every tensor the network reads (SileroModel.swift:22-28,44-66)
+// (conv weights [out, k, in], lstm.Wx / Wh [512, 128]); load_checked_f32 checks a checkpoint against it with no HIP call
 const std::vector<std::pair<std::string, std::vector<int64_t>>>& silero_tensor_shapes();
-// reads <dir>/model.safetensors; checks every key and shape; no HIP call
-SileroHostWeights silero_load_weights(const std::string& dir);
 
 struct VadConfig { float onset, offset, min_speech, min_silence; };
 struct VadSegment { float start, end; };
@@ -37,7 +27,7 @@ std::vector<VadSegment> silero_binarize(const float* probs, size_t n, const VadC
 class SileroVad {
   public:
     // work: the stream the VAD's work is ordered on (an engine's stream), nullptr = a stream of its own
-    SileroVad(int device, const SileroHostWeights& w, int max_streams, hipStream_t work);
+    SileroVad(int device, const CheckedWeights& w, int max_streams, hipStream_t work);
     ~SileroVad();
     void reset(int stream);                                                     // stream < 0: every stream
     // processChunk for B distinct streams: chunks [B][512] -> probs [B]

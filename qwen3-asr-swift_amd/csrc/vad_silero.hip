@@ -13,7 +13,6 @@
 // which slot of it, how many chunks it holds, the batch size and the grid size never enter the arithmetic, so a stream fed tick by tick
 // and the same audio fed as one buffer give bit-identical probabilities and state.  No workgroup waits for another.
 #include "vad_silero.h"
-#include "safetensors.h"
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -371,37 +370,6 @@ const std::vector<std::pair<std::string, std::vector<int64_t>>>& silero_tensor_s
     return s;
 }
 
-static std::string shape_str(const std::vector<int64_t>& s) {
-    std::string r = "[";
-    for (size_t i = 0; i < s.size(); ++i) r += (i ? ", " : "") + std::to_string(s[i]);
-    return r + "]";
-}
-
-SileroHostWeights silero_load_weights(const std::string& dir) {
-    const std::string path = dir + "/model.safetensors";
-    FILE* f = fopen(path.c_str(), "rb");
-    if (!f) throw VadLoadError(QASR_ERR_IO, "silero vad: cannot open " + path);
-    fclose(f);
-    std::unique_ptr<SafeTensorsDir> st;
-    try { st = std::make_unique<SafeTensorsDir>(dir); }
-    catch (const std::exception& ex) { throw VadLoadError(QASR_ERR_IO, std::string("silero vad: ") + ex.what()); }
-    SileroHostWeights w;
-    for (const auto& ks : silero_tensor_shapes()) {
-        auto it = st->entries.find(ks.first);
-        if (it == st->entries.end()) throw VadLoadError(QASR_ERR_IO, "silero vad: missing tensor " + ks.first);
-        const SafeEntry& e = it->second;
-        if (e.shape != ks.second)
-            throw VadLoadError(QASR_ERR_INVALID, "silero vad: tensor " + ks.first + " has shape " + shape_str(e.shape) + ", expected " +
-                                                     shape_str(ks.second));
-        if (e.dtype != "F32" && e.dtype != "F16" && e.dtype != "BF16")
-            throw VadLoadError(QASR_ERR_INVALID, "silero vad: tensor " + ks.first + " has dtype " + e.dtype + " (F32 / F16 / BF16)");
-        std::vector<float> v(e.numel());
-        for (size_t i = 0; i < v.size(); ++i) v[i] = safe_elem_f32(e, i);     // MLX promotes to f32 (the samples are f32)
-        w.t[ks.first] = std::move(v);
-    }
-    return w;
-}
-
 // ---- binarize (VADPipeline.swift:117-181 with SileroVAD.swift detectSpeech's frame duration) ---------------------------------------
 std::vector<VadSegment> silero_binarize(const float* probs, size_t n, const VadConfig& cfg) {
     std::vector<VadSegment> segs;
@@ -435,7 +403,7 @@ constexpr int FR_CPW_BIG = 8;
 
 static size_t front_lds(int cpw) { return (size_t)cpw * (X_LEN + ST_LEN + MG_LEN) * sizeof(float); }
 
-SileroVad::SileroVad(int device, const SileroHostWeights& w, int max_streams, hipStream_t work)
+SileroVad::SileroVad(int device, const CheckedWeights& w, int max_streams, hipStream_t work)
     : device_(device), max_streams_(max_streams) {
     if (max_streams <= 0 || max_streams > 4096) throw std::invalid_argument("silero vad: max_streams in 1..4096");
     // device layouts: conv weights [out, k, in] -> [k, in, out], STFT [258, 256, 1] -> [256, 258], Wx [512, 128] -> [128, 512]

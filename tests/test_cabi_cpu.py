@@ -85,6 +85,24 @@ def test_error_paths_without_gpu():
     assert lib.qasr_transcribe(None, None, 0, 16000, None, None) != 0
 
 
+def test_create_error_slots_keep_their_visibility():
+    """What *_last_error(NULL) answers after a failed create: the engine and the Omnilingual handle share one slot (qasr_dp_create builds
+    its message from qasr_last_error(NULL)); the VAD and the speaker model each have their own.  Both creates fail on an argument check,
+    before any HIP call."""
+    lib = _lib.load()
+    want = b"omnilingual: max_audio_seconds must be in 1..40 (the reference's cap), max_batch positive"
+    cfg = _lib.QasrCtcConfig()
+    assert lib.qasr_ctc_default_config(b"tiny", C.byref(cfg)) == 0
+    cfg.max_audio_seconds = 41
+    h = C.c_void_p()
+    assert lib.qasr_ctc_create(None, C.byref(cfg), C.byref(h)) == 1 and not h.value
+    assert lib.qasr_ctc_last_error(None) == want and lib.qasr_last_error(None) == want
+    assert lib.qasr_vad_create(0, None, 4, None, C.byref(h)) == 1 and not h.value
+    assert lib.qasr_vad_last_error(None) == b"silero vad: model_dir is NULL"
+    assert b"silero" not in lib.qasr_spk_last_error(None)
+    assert lib.qasr_ctc_last_error(None) == want                                   # the VAD's failure did not land in the shared slot
+
+
 def test_tuning_knobs_roundtrip():
     """qasr_set_tuning / qasr_get_tuning: the knob table of csrc/tuning.h (pure host state, no GPU)."""
     lib = _lib.load()

@@ -145,22 +145,22 @@ def _create(d):
 
 
 def test_create_errors_name_the_key(tmp_path, sd):
-    """missing file / key -> QASR_ERR_IO, wrong shape, bad dtype or an unknown key -> QASR_ERR_INVALID, the key named; all before any
-    HIP call"""
+    """missing file / key -> QASR_ERR_IO, wrong shape, bad dtype or an unknown key -> QASR_ERR_INVALID, the key named (whole messages, as
+    the loader worded them before it was shared with the VAD); all before any HIP call"""
     rc, msg = _create(tmp_path / "nope")
-    assert rc == 4 and "model.safetensors" in msg
+    assert rc == 4 and msg == f"wespeaker: cannot open {tmp_path / 'nope'}/model.safetensors"
     synth.write_wespeaker_safetensors(sd, str(tmp_path / "a"), drop=("layer3.0.shortcut.bias",))
     rc, msg = _create(tmp_path / "a")
-    assert rc == 4 and "layer3.0.shortcut.bias" in msg
+    assert rc == 4 and msg == "wespeaker: missing tensor layer3.0.shortcut.bias"
     synth.write_wespeaker_safetensors(sd, str(tmp_path / "b"), reshape={"layer2.1.conv1.weight": (64, 64, 3, 3)})
     rc, msg = _create(tmp_path / "b")
-    assert rc == 1 and "layer2.1.conv1.weight" in msg and "[64, 3, 3, 64]" in msg
+    assert rc == 1 and msg == "wespeaker: tensor layer2.1.conv1.weight has shape [64, 64, 3, 3], expected [64, 3, 3, 64]"
     synth.write_wespeaker_safetensors(sd, str(tmp_path / "c"), extra={"layer1.0.shortcut.weight": np.zeros((32, 1, 1, 32))})
     rc, msg = _create(tmp_path / "c")
-    assert rc == 1 and "layer1.0.shortcut.weight" in msg and "unknown" in msg
+    assert rc == 1 and msg == "wespeaker: unknown tensor layer1.0.shortcut.weight"
     synth.write_wespeaker_safetensors(sd, str(tmp_path / "d"), dtype="F64")
     rc, msg = _create(tmp_path / "d")
-    assert rc == 1 and "F64" in msg
+    assert rc == 1 and msg == "wespeaker: tensor conv1.weight has dtype F64 (F32 / F16 / BF16)"
     with pytest.raises(QasrError, match="embedding.weight"):
         synth.write_wespeaker_safetensors(sd, str(tmp_path / "e"), drop=("embedding.weight",))
         WeSpeakerModel.from_pretrained(str(tmp_path / "e"))

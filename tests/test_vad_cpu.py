@@ -159,17 +159,21 @@ def _create(d):
 
 
 def test_create_errors_name_the_key(tmp_path):
-    """Missing directory / file / key -> QASR_ERR_IO, wrong shape or dtype -> QASR_ERR_INVALID, the key named; every check runs before
-    the first HIP call (there is no GPU here: reaching one would answer QASR_ERR_HIP)."""
+    """Missing directory / file / key -> QASR_ERR_IO, wrong shape or dtype -> QASR_ERR_INVALID, the key named (whole messages, as the
+    loader worded them before it was shared with the speaker model); every check runs before the first HIP call (there is no GPU here:
+    reaching one would answer QASR_ERR_HIP)."""
     rc, msg = _create(tmp_path / "nope")
-    assert rc == 4 and "model.safetensors" in msg
+    assert rc == 4 and msg == f"silero vad: cannot open {tmp_path / 'nope'}/model.safetensors"
     sd = synth.synth_silero_state_dict(0)
     synth.write_silero_safetensors(sd, str(tmp_path / "a"), drop=("lstm.Wh",))
     rc, msg = _create(tmp_path / "a")
-    assert rc == 4 and "lstm.Wh" in msg
+    assert rc == 4 and msg == "silero vad: missing tensor lstm.Wh"
     synth.write_silero_safetensors(sd, str(tmp_path / "b"), reshape={"encoder.2.weight": (64, 64, 3)})
     rc, msg = _create(tmp_path / "b")
-    assert rc == 1 and "encoder.2.weight" in msg and "[64, 3, 64]" in msg
+    assert rc == 1 and msg == "silero vad: tensor encoder.2.weight has shape [64, 64, 3], expected [64, 3, 64]"
+    synth.write_silero_safetensors(sd, str(tmp_path / "d"), dtype="F64")
+    rc, msg = _create(tmp_path / "d")
+    assert rc == 1 and msg == "silero vad: tensor stft.weight has dtype F64 (F32 / F16 / BF16)"
     with pytest.raises(QasrError, match="stft.weight"):
         synth.write_silero_safetensors(sd, str(tmp_path / "c"), drop=("stft.weight",))
         SileroVADModel.from_pretrained(str(tmp_path / "c"))
