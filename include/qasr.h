@@ -285,6 +285,14 @@ int qasr_prefill_logits(qasr_engine* e, const float* audio_embeds, int n_audio,
                         const qasr_options* opt, float* logits);
 /* teacher-forced steps on slot 0: feeds tokens[i], returns logits [n, vocab]. */
 int qasr_decode_forced(qasr_engine* e, const int32_t* tokens, int n, float* logits);
+/* The same two stages for a whole batch (no reference counterpart, used by tests).
+ * After qasr_batch_begin (or qasr_batch_begin_staged): mel + encoder + prompt pass of the prepared batch with the logits kept.
+ * logits [B][vocab] f32 = each row's last prompt position.  Leaves every row's KV cache and ctx_len ready for qasr_batch_decode_forced. */
+int qasr_batch_prefill_logits(qasr_engine* e, float* logits);
+/* One teacher-forced decode step for ALL rows of that batch: row b is fed tokens[b]; logits [B][vocab] f32 of the next position.
+ * The step is the one qasr_batch_run captures into its graph, launched eagerly.  QASR_ERR_CAPACITY when a row's cache is full,
+ * QASR_ERR_INVALID for an id outside the vocabulary or without a preceding qasr_batch_prefill_logits of the prepared batch. */
+int qasr_batch_decode_forced(qasr_engine* e, const int32_t* tokens, float* logits);
 
 /* ---- forced aligner ----------------------------------------------------------------------
  * Replaces Qwen3ForcedAligner.align / alignLong (Sources/Qwen3ASR/ForcedAligner.swift:226-331, :97-180):

@@ -426,6 +426,16 @@ int qasr_decode_forced(qasr_engine* e, const int32_t* tokens, int n, float* logi
     return on_device(e, [&] { e->impl->decode_forced_host(tokens, n, logits); });
 }
 
+int qasr_batch_prefill_logits(qasr_engine* e, float* logits) {
+    if (!e || !logits) return QASR_ERR_INVALID;
+    return on_device(e, [&] { e->impl->batch_prefill_logits(logits); });
+}
+
+int qasr_batch_decode_forced(qasr_engine* e, const int32_t* tokens, float* logits) {
+    if (!e || !tokens || !logits) return QASR_ERR_INVALID;
+    return on_device(e, [&] { e->impl->batch_decode_forced(tokens, logits); });
+}
+
 // ---- Omnilingual ASR (wav2vec2 + CTC) -------------------------------------------------------------------
 }  // extern "C"
 

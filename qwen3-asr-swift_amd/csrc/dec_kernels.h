@@ -91,6 +91,9 @@ int decode_gemv_fused_launch(DecEpi epi, const DecGemvArgs& a, const bf16_t* nor
 // GEMV).  lm_head_parts = partials per row the launch will produce (fixed per (N, K)); partial layout
 // [row][parts].  NOTE: the persistent form needs every row group of a step to use the same `parts`.
 int lm_head_parts(int N, int K);
+// batch rows ONE lm_head_launch holds (the persistent kernel keeps them as an LDS image: 4 batch tiles at K = 1024, 2 at K = 2048); more rows
+// take one launch per block of that many (Engine::run_lm_head)
+int lm_head_rows(int N, int K);
 int lm_head_launch(const bf16_t* W, const bf16_t* Wp, const bf16_t* X, const bf16_t* norm_w, float eps, int B, int N, int K,
                    float* logits, float* part_val, int* part_idx, bf16_t* norm_scratch, hipStream_t s);
 // Fragment-major repack of a row-major [N][K] weight (MFMA 16x16x32 A operand, 1 KiB per (row tile, k-step))

@@ -212,6 +212,7 @@ static void lm_head_go(const LmHeadArgs& a, hipStream_t s) {
 
 bool lm_head_supported(int N, int K) { return (K == 1024 || K == 2048) && N % 16 == 0 && N / 16 >= 512 * LMH_WAVES; }
 int lm_head_parts(int N, int K) { return lm_head_supported(N, K) ? lmh_grid() : decode_gemv_blocks(DEC_EPI_LOGITS, N); }
+int lm_head_rows(int N, int K) { return !lm_head_supported(N, K) ? 1 << 30 : K == 1024 ? 64 : 32; }
 
 // final RMSNorm + tied LM head + per-workgroup argmax partials; returns the number of partials per row
 int lm_head_launch(const bf16_t* W, const bf16_t* Wp, const bf16_t* X, const bf16_t* norm_w, float eps, int B, int N, int K,

@@ -70,6 +70,7 @@ void decode_gemv_q_launch(DecEpi epi, const DecGemvArgs& a, const QuantImg& w, c
 
 // Final RMSNorm + tied LM head on the quantised embedding + per-workgroup argmax partials (layout of lm_head_launch).
 int lm_head_q_parts(int N, int K, int bits);
+int lm_head_q_rows(int N, int K, int bits);      // batch rows one lm_head_q_launch holds (see lm_head_rows)
 int lm_head_q_launch(const QuantImg& w, const bf16_t* X, const bf16_t* norm_w, float eps, int B, int N, int K, float* logits,
                      float* part_val, int* part_idx, bf16_t* norm_scratch, hipStream_t s);
 

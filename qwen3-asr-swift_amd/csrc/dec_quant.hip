@@ -815,6 +815,7 @@ static bool lm_head_q_supported(int N, int K, int bits) {
     return (K == 1024 || K == 2048) && (bits == 4 || bits == 8) && N % 16 == 0 && N / 16 >= LMQ_GRID * LMQ_WAVES;
 }
 int lm_head_q_parts(int N, int K, int bits) { return lm_head_q_supported(N, K, bits) ? LMQ_GRID : 1; }
+int lm_head_q_rows(int N, int K, int bits) { return !lm_head_q_supported(N, K, bits) ? 1 << 30 : K == 1024 ? 64 : 32; }
 
 template <int BITS, bool SBF32, int K, int NB, int LR>
 static void lm_head_q_go1(const LmHeadQArgs& a, hipStream_t s) {

@@ -397,11 +397,19 @@ void Engine::reset_greedy_state(int max_tokens, bool ignore_eos) {
     init[cfg_.max_batch + 1] = 0;                                  // err flag
     QASR_HIP(hipMemcpyAsync(gstate_.ctx_len, init, (size_t)(cfg_.max_batch + 2) * sizeof(int), hipMemcpyHostToDevice, stream_));
     steps_done_ = 0;
-    forced_ctx_ = B > 0 ? h_ctx0_[0] : 0;
+    forced_steps_ = 0;
+    forced_ready_ = false;
 }
 
 void Engine::run_lm_head(bool want_logits, int r0, int nr, hipStream_t s) {
     const int H = cfg_.hidden;
+    // one launch holds lm_head_rows batch rows (hidden 2048: 32): a larger row range streams the table once per block of that many rows.  Rows
+    // are independent columns of the head and the logits / partials are indexed by row, so the blocks are the one launch cut in two.
+    const int cap = decw_.quant ? lm_head_q_rows(cfg_.vocab, H, cfg_.bits) : lm_head_rows(cfg_.vocab, H);
+    if (nr > cap) {
+        for (int r = 0; r < nr; r += cap) run_lm_head(want_logits, r0 + r, std::min(cap, nr - r), s);
+        return;
+    }
     if (decw_.quant) {
         // the generic (untuned-shape) quantised head writes every logit and reduces them afterwards: it always needs the buffer
         const bool need = want_logits || n_parts_ == 1;
@@ -828,6 +836,16 @@ __global__ void set_ints_kernel(int* dst, const int* src, int n) {
     if (i < n) dst[i] = src[i];
 }
 
+// Feed the ids at d_ids (device, one per row) to rows [0, B) and run one decode step that keeps the logits of every row: x = embed[id],
+// the RoPE rows of the rows' current positions, the step (eager, outside the graph), ctx_len + 1.  The host sampler's loop below,
+// qasr_decode_forced (B = 1) and qasr_batch_decode_forced all step through here.
+void Engine::forced_step(const int* d_ids, int B) {
+    embed_rows(d_ids, d_dx_.as<bf16_t>(), B, stream_);
+    hipLaunchKernelGGL(refresh_rope_rows_kernel, dim3(B), dim3(64), 0, stream_, gstate_.ctx_len, rope_rows(0));
+    run_decode_step(true, false, 0, B, stream_, true);
+    hipLaunchKernelGGL(add_scalar_kernel, dim3(cdiv(B, 64)), dim3(64), 0, stream_, gstate_.ctx_len, B, 1);
+}
+
 // Slow path (generateSlow, Qwen3ASR.swift:396-433): the logits of every row come back to the host each step and
 // pickNextToken runs on the CPU, exactly like the reference; the step itself is the same HIP decode step.
 void Engine::decode_loop_slow() {
@@ -855,13 +873,9 @@ void Engine::decode_loop_slow() {
             all_done = all_done && done[b];
         }
         if (all_done || step + 1 >= cur_max_tokens_) break;
-        // feed the picked ids: x = embed[token], rope rows for the current positions, one decode step with logits
         std::memcpy(h_tok.p, next.data(), (size_t)B * sizeof(int));
         QASR_HIP(hipMemcpyAsync(d_tok.p, h_tok.p, (size_t)B * sizeof(int), hipMemcpyHostToDevice, stream_));
-        embed_rows(d_tok.as<int>(), d_dx_.as<bf16_t>(), B, stream_);
-        hipLaunchKernelGGL(refresh_rope_rows_kernel, dim3(B), dim3(64), 0, stream_, gstate_.ctx_len, rope_rows(0));
-        run_decode_step(true, false, 0, B, stream_, true);
-        hipLaunchKernelGGL(add_scalar_kernel, dim3(cdiv(B, 64)), dim3(64), 0, stream_, gstate_.ctx_len, B, 1);
+        forced_step(d_tok.as<int>(), B);
         ++steps_done_;
     }
     // publish through the same device-side result block the fast path uses
@@ -934,6 +948,7 @@ void Engine::batch_run() {
     if (pcm_staged_over_)
         throw std::invalid_argument("batch_run: qasr_batch_stage has replaced this batch's samples in the device PCM buffer; a batch cannot be run "
                                     "again (qasr_batch_rewind) once its successor is staged");
+    forced_ready_ = false;                         // the greedy loop moves ctx_len on the device
     hipStream_t s = stream_;
     QASR_HIP(hipEventRecord(ev_[0], s));
     run_mel();
@@ -1296,8 +1311,9 @@ void Engine::decode_forced_host(const int32_t* tokens, int n, float* logits) {
     require_asr("decode_forced");
     // every forced token appends one K/V row at ctx_len and reads the RoPE row of that position: stay inside the
     // cache (max_ctx_ rows; the last row is never a query position of the greedy path either)
-    if (n < 0 || forced_ctx_ + n > max_ctx_ - 1)
-        throw std::length_error("decode_forced: " + std::to_string(forced_ctx_) + " cached positions + " + std::to_string(n) +
+    const int ctx = h_ctx0_[0] + forced_steps_;
+    if (n < 0 || ctx + n > max_ctx_ - 1)
+        throw std::length_error("decode_forced: " + std::to_string(ctx) + " cached positions + " + std::to_string(n) +
                                 " forced tokens exceed the cache capacity of " + std::to_string(max_ctx_ - 1));
     HostBuf idx;
     idx.alloc(sizeof(int));
@@ -1307,15 +1323,60 @@ void Engine::decode_forced_host(const int32_t* tokens, int n, float* logits) {
         if (tokens[i] < 0 || tokens[i] >= cfg_.vocab) throw std::invalid_argument("token id out of range");
         *idx.as<int>() = tokens[i];
         QASR_HIP(hipMemcpyAsync(didx.p, idx.p, sizeof(int), hipMemcpyHostToDevice, stream_));
-        embed_rows(didx.as<int>(), d_dx_.as<bf16_t>(), 1, stream_);
-        hipLaunchKernelGGL(refresh_rope_rows_kernel, dim3(1), dim3(64), 0, stream_, gstate_.ctx_len, rope_rows(0));
-        run_decode_step(true, false, 0, 1, stream_, true);
-        hipLaunchKernelGGL(add_scalar_kernel, dim3(1), dim3(64), 0, stream_, gstate_.ctx_len, 1, 1);
+        forced_step(didx.as<int>(), 1);
         QASR_HIP(hipMemcpyAsync(logits + (size_t)i * cfg_.vocab, d_logits_.p, (size_t)cfg_.vocab * sizeof(float),
                                 hipMemcpyDeviceToHost, stream_));
         QASR_HIP(hipStreamSynchronize(stream_));
-        ++forced_ctx_;
+        ++forced_steps_;
     }
+}
+
+// qasr_batch_prefill_logits: the first half of batch_run (log-mel, encoder, prompt pass) on the prepared batch, with the LM head writing the
+// logits of every row.  No token is picked and no decode step follows: the rows' caches and ctx_len are what batch_decode_forced continues from.
+void Engine::batch_prefill_logits(float* logits) {
+    require_batch("batch_prefill_logits");
+    require_asr("batch_prefill_logits");
+    if (pcm_staged_over_)
+        throw std::invalid_argument("batch_prefill_logits: qasr_batch_stage has replaced this batch's samples in the device PCM buffer");
+    QASR_HIP(hipStreamSynchronize(stream_));       // h_ginit_ is reused
+    reset_greedy_state(cur_max_tokens_, cur_ignore_eos_);
+    run_mel();
+    if (ev_mel_done_) QASR_HIP(hipEventRecord(ev_mel_done_, stream_));
+    run_issued_ = true;
+    run_encoder();
+    run_prefill(true);
+    QASR_HIP(hipMemcpyAsync(logits, d_logits_.p, (size_t)batch_ * cfg_.vocab * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    QASR_HIP(hipStreamSynchronize(stream_));
+    forced_ready_ = true;
+}
+
+// qasr_batch_decode_forced: one teacher-forced step of every row of that batch.
+void Engine::batch_decode_forced(const int32_t* tokens, float* logits) {
+    require_batch("batch_decode_forced");
+    require_asr("batch_decode_forced");
+    if (!forced_ready_) throw std::runtime_error("batch_decode_forced needs a preceding batch_prefill_logits of this batch");
+    const int B = batch_;
+    // one K/V row per batch row at its ctx_len, and the RoPE row of that position: every row stays inside its cache (see decode_forced_host)
+    for (int b = 0; b < B; ++b)
+        if (h_ctx0_[b] + forced_steps_ + 1 > max_ctx_ - 1)
+            throw std::length_error("batch_decode_forced: row " + std::to_string(b) + " holds " + std::to_string(h_ctx0_[b] + forced_steps_) +
+                                    " cached positions, one more exceeds the cache capacity of " + std::to_string(max_ctx_ - 1));
+    for (int b = 0; b < B; ++b)
+        if (tokens[b] < 0 || tokens[b] >= cfg_.vocab) throw std::invalid_argument("token id out of range");
+    HostBuf h_tok;
+    h_tok.alloc((size_t)B * sizeof(int));
+    DevBuf d_tok;
+    d_tok.alloc((size_t)B * sizeof(int));
+    std::memcpy(h_tok.p, tokens, (size_t)B * sizeof(int));
+    QASR_HIP(hipMemcpyAsync(d_tok.p, h_tok.p, (size_t)B * sizeof(int), hipMemcpyHostToDevice, stream_));
+    forced_step(d_tok.as<int>(), B);
+    QASR_HIP(hipMemcpyAsync(logits, d_logits_.p, (size_t)B * cfg_.vocab * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    int err = 0;
+    QASR_HIP(hipMemcpyAsync(&err, d_err_flag_, sizeof(int), hipMemcpyDeviceToHost, stream_));
+    QASR_HIP(hipStreamSynchronize(stream_));
+    ++forced_steps_;
+    if (err & CHAIN_ERR_TIMEOUT)
+        throw HipError("decode chain: an in-launch hand-off wait gave up (a workgroup of the persistent grid was not resident within the budget); logits are not valid");
 }
 
 }  // namespace qasr

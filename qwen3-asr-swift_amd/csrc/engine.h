@@ -94,6 +94,8 @@ public:
     int num_audio_tokens(int n_frames) const;
     void prefill_logits_host(const float* audio_embeds, int n_audio, const qasr_options* opt, float* logits);
     void decode_forced_host(const int32_t* tokens, int n, float* logits);
+    void batch_prefill_logits(float* logits);
+    void batch_decode_forced(const int32_t* tokens, float* logits);
 
     // batch pipeline (qasr_batch_*): H2D + plan | mel + encoder + prefill + greedy decode | D2H
     void batch_begin(const float* const* pcm, const size_t* n, size_t B, const qasr_options* opt);
@@ -285,7 +287,9 @@ private:
     long graph_key_ = -1;
     unsigned graph_epoch_ = 0;                                 // tuning().epoch the graph was captured under
     int* d_err_flag_ = nullptr;                                // device word: set when a greedy step sees a non-finite best logit
-    int forced_ctx_ = 0;                                       // host copy of slot 0's context length (decode_forced capacity)
+    int forced_steps_ = 0;                                     // forced steps since the prompt pass: row b holds h_ctx0_[b] + forced_steps_ positions
+    bool forced_ready_ = false;                                // batch_prefill_logits ran and no greedy loop has moved ctx_len since
+    void forced_step(const int* d_ids, int B);
     void drop_graph();
     void require_batch(const char* what) const;
     hipEvent_t ev_[6] = {};

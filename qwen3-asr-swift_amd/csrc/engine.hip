@@ -110,7 +110,8 @@ void Engine::finalize() {
     staged_valid_ = false;
     run_issued_ = false;
     h_ctx0_.clear();
-    forced_ctx_ = 0;
+    forced_steps_ = 0;
+    forced_ready_ = false;
     finalized_ = false;
     finalize_encoder();
     finalize_decoder();
@@ -129,7 +130,8 @@ void Engine::unload() {
     run_issued_ = false;
     batch_ = 0;
     h_ctx0_.clear();
-    forced_ctx_ = 0;
+    forced_steps_ = 0;
+    forced_ready_ = false;
     finalized_ = false;
 }
 void Engine::require_batch(const char* what) const {

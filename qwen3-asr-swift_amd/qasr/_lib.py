@@ -138,6 +138,8 @@ SIGNATURES = {
     "qasr_encode": (C.c_int, [_E, _F, C.c_int, _F]),
     "qasr_prefill_logits": (C.c_int, [_E, _F, C.c_int, _P(QasrOptions), _F]),
     "qasr_decode_forced": (C.c_int, [_E, _I, C.c_int, _F]),
+    "qasr_batch_prefill_logits": (C.c_int, [_E, _F]),
+    "qasr_batch_decode_forced": (C.c_int, [_E, _I, _F]),
     "qasr_split_words": (C.c_int, [C.c_char_p, C.c_char_p, _P(C.c_void_p), _P(C.c_void_p)]),
     "qasr_lis_positions": (C.c_int, [_I, C.c_size_t, _I]),
     "qasr_enforce_monotonicity": (C.c_int, [_I, C.c_size_t, _I]),

@@ -43,6 +43,10 @@ class Engine:
     def load_state_dict(self, sd):
         """Upload a reference-named torch state dict tensor by tensor, then finalize: bf16 / f32 float tensors, int32
         tensors = the uint32 words of MLX-quantised weights."""
+        self.set_tensors(sd)
+
+    def set_tensors(self, sd):
+        """Upload (or replace) the tensors of `sd` and finalize again: the other tensors of the engine stay."""
         import torch
         codes = {torch.bfloat16: "bf16", torch.float32: "f32", torch.int32: "u32"}
         for name, t in sd.items():
@@ -87,6 +91,33 @@ class Engine:
         logits = np.empty((t.shape[0], self.cfg.vocab), dtype=np.float32)
         self.check(self.lib.qasr_decode_forced(self.h, iptr(t), t.shape[0], fptr(logits)))
         return logits
+
+    def batch_prefill_logits(self, clips, **opt):
+        """qasr_batch_begin + qasr_batch_prefill_logits: [B, vocab] logits of every row's last prompt position; the batch stays prepared for
+        batch_decode_forced."""
+        clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
+        B = len(clips)
+        ptrs = (C.POINTER(C.c_float) * B)(*[fptr(c) for c in clips])
+        ns = (C.c_size_t * B)(*[c.shape[0] for c in clips])
+        o = self.options(**opt)
+        self.check(self.lib.qasr_batch_begin(self.h, ptrs, ns, B, C.byref(o)))
+        self._batch = B
+        logits = np.empty((B, self.cfg.vocab), dtype=np.float32)
+        self.check(self.lib.qasr_batch_prefill_logits(self.h, fptr(logits)))
+        return logits
+
+    def batch_decode_forced(self, tokens):
+        """One teacher-forced step of every row of the batch of batch_prefill_logits: row b is fed tokens[b] -> [B, vocab] logits."""
+        t = np.ascontiguousarray(tokens, dtype=np.int32)
+        assert t.shape == (self._batch,), (t.shape, self._batch)
+        logits = np.empty((self._batch, self.cfg.vocab), dtype=np.float32)
+        self.check(self.lib.qasr_batch_decode_forced(self.h, iptr(t), fptr(logits)))
+        return logits
+
+    def get_tuning(self, key):
+        v = C.c_int()
+        assert self.lib.qasr_get_tuning(key.encode(), C.byref(v)) == 0, key
+        return v.value
 
     def transcribe_batch(self, clips, **opt):
         clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]

@@ -85,6 +85,16 @@ def test_error_paths_without_gpu():
     assert lib.qasr_transcribe(None, None, 0, 16000, None, None) != 0
 
 
+def test_batch_logit_entry_points_check_their_arguments():
+    """qasr_batch_prefill_logits / qasr_batch_decode_forced: a null handle or a null buffer is QASR_ERR_INVALID before anything is touched (the
+    refusal without a prepared batch needs an engine, so it is in tests/test_gpu_batch_logits.py)."""
+    lib = _lib.load()
+    buf = (C.c_float * 4)()
+    tok = (C.c_int32 * 4)()
+    assert lib.qasr_batch_prefill_logits(None, buf) == 1 and lib.qasr_batch_prefill_logits(None, None) == 1
+    assert lib.qasr_batch_decode_forced(None, tok, buf) == 1 and lib.qasr_batch_decode_forced(None, None, None) == 1
+
+
 def test_create_error_slots_keep_their_visibility():
     """What *_last_error(NULL) answers after a failed create: the engine and the Omnilingual handle share one slot (qasr_dp_create builds
     its message from qasr_last_error(NULL)); the VAD and the speaker model each have their own.  Both creates fail on an argument check,
