@@ -530,6 +530,97 @@ float qasr_spk_cosine_similarity(const float* a, const float* b, size_t n);
 /* device time of the last embed / fbank call in ms (HIP events on the work stream: H2D + kernels + D2H of every pass) */
 int qasr_spk_timing(const qasr_spk* s, float* ms);
 
+/* ---- pyannote segmentation and diarization (csrc/seg_pyannote.hip, csrc/api_seg.cpp, csrc/diarize.cpp) ------------------------
+ * The PyanNet segmentation network (Sources/SpeechVAD/Segmentation.swift:17-97, SincNet.swift:15-129, BiLSTM.swift:9-100,
+ * PowersetDecoder.swift:23-72) and the two public things built on it, rebuilt as HIP launches over all windows of a file at once:
+ *   SegmentationModel.callAsFunction (Segmentation.swift:63-84) + speakerProbabilities (PowersetDecoder.swift:23-31)
+ *        + speechProbability (Segmentation.swift:93-96)                                -> qasr_seg_forward, qasr_seg_windows
+ *   SegmentationWeightLoader / fromPretrained (SpeechVAD.swift:51-81)                   -> qasr_seg_create (model_dir/model.safetensors)
+ *   isLoaded / unload / memoryFootprint (PyannoteVAD+Memory.swift)                      -> qasr_seg_is_loaded / _unload / _memory_footprint
+ *   PyannoteVADModel.detectSpeech (SpeechVAD.swift:89-140)                              -> qasr_seg_detect_speech
+ *   VADPipeline.windowPositions / aggregateFrames / binarize (VADPipeline.swift:37-181) -> qasr_seg_window_positions / _aggregate_frames / _binarize
+ *   PyannoteDiarizationPipeline.diarize / extractSpeaker (DiarizationPipeline.swift:187-537) -> qasr_diarize, qasr_diar_extract_speaker
+ *   DiarizationHelpers (DiarizationHelpers.swift:11-182)                                -> qasr_diar_merge_segments / _compact_speaker_ids / _cluster / _cosine_distance
+ * The reference's progress / cancel callback is not carried over.  Sharing a GPU with an engine: as for the VAD and
+ * WeSpeaker, pass it as order_with.  One object, one thread at a time.
+ * Precision: f32 throughout.  A window's outputs are bit-identical alone, in any batch, under any max_windows, and run to run
+ * (DESIGN.md section 13). */
+typedef struct qasr_seg qasr_seg;
+typedef struct qasr_seg_vad_config {   /* VADConfig (Configuration.swift:52-82) */
+    float onset, offset, min_speech_duration, min_silence_duration, window_duration, step_ratio;
+} qasr_seg_vad_config;
+int qasr_seg_vad_default_config(qasr_seg_vad_config* out);         /* VADConfig.default: 0.767, 0.377, 0.136, 0.067, 10 s, 0.1 */
+/* fromPretrained from a local directory.  Every key, shape and dtype (F32 / F16 / BF16, widened to f32) is checked before any HIP call:
+ * missing file or required key -> QASR_ERR_IO, wrong shape or dtype or an unknown key (verify: .noUnusedKeys) -> QASR_ERR_INVALID, the
+ * key named in qasr_seg_last_error(NULL).  A missing sincnet conv bias (0), norm weight (1) or norm bias (0) keeps the module's initial
+ * value, as in the reference.  max_windows: windows one device pass holds (0 = 64); larger calls run as several passes with identical
+ * results.  order_with: an engine on `device` whose stream orders the model's work, or NULL. */
+int qasr_seg_create(int device, const char* model_dir, int max_windows, qasr_engine* order_with, qasr_seg** out);
+void qasr_seg_destroy(qasr_seg* s);
+const char* qasr_seg_last_error(const qasr_seg* s);                 /* s may be NULL: last create() failure */
+int qasr_seg_is_loaded(const qasr_seg* s);
+int qasr_seg_unload(qasr_seg* s);                                   /* later device calls return QASR_ERR_NOT_LOADED */
+size_t qasr_seg_memory_footprint(const qasr_seg* s);                /* parameter bytes as stored, 0 unloaded */
+/* frames for n samples: L0 = (n - 251) / 10 + 1, then /3, -4, /3, -4, /3 (all floored); 589 for 160 000; -1 below 991.  Pure CPU. */
+int qasr_seg_num_frames(size_t n);
+int qasr_seg_timing(const qasr_seg* s, float* ms);                  /* device time of the last call in ms (H2D + kernels + D2H) */
+/* SegmentationModel.callAsFunction on pcm [B][n] (any n >= 991, else QASR_ERR_INVALID) with both decoders; F = qasr_seg_num_frames(n):
+ * posteriors [B][F][7] (softmax), speaker_probs [B][F][3], speech_probs [B][F]; any of them may be NULL. */
+int qasr_seg_forward(qasr_seg* s, const float* pcm, size_t B, size_t n, float* posteriors, float* speaker_probs, float* speech_probs);
+/* windowPositions (VADPipeline.swift:37-60 = DiarizationPipeline.swift:319-332), pure CPU: the window count; the first min(count, cap)
+ * (start, end) sample pairs are written (starts / ends may be NULL). */
+int qasr_seg_window_positions(size_t n_samples, size_t window_samples, size_t step_samples, int64_t* starts, int64_t* ends, size_t cap);
+/* every window of a buffer in one call: the buffer is uploaded once, each window reads it at its start (its tail past the buffer reads
+ * as zero) and is bit-identical to qasr_seg_forward of the sliced, zero-padded copy.  Outputs as qasr_seg_forward with B = the count
+ * and n = window_samples.  Returns the window count or -status (-QASR_ERR_CAPACITY when count > cap; nothing is run then). */
+int qasr_seg_windows(qasr_seg* s, const float* pcm, size_t n_samples, size_t window_samples, size_t step_samples, float* posteriors,
+                     float* speaker_probs, float* speech_probs, int64_t* starts, int64_t* ends, size_t cap);
+/* VADPipeline.aggregateFrames (VADPipeline.swift:74-106) with frameDuration = window_duration / frames_per_window and its f32
+ * Int(frameTime / frameDuration) indexing, pure CPU: window_probs [n_windows][frames_per_window]; the frame count (first cap written). */
+int qasr_seg_aggregate_frames(const float* window_probs, size_t n_windows, size_t frames_per_window, const int64_t* starts, size_t n_samples,
+                              int sample_rate, float window_duration, float* out, size_t cap);
+/* hysteresis binarisation, pure CPU: filter_durations = 0 is PowersetDecoder.binarize (PowersetDecoder.swift:44-72, no duration filter),
+ * 1 is VADPipeline.binarize (VADPipeline.swift:117-181, with filterDurations).  (start, end) pairs; the count or -status. */
+int qasr_seg_binarize(const float* probs, size_t n, float frame_duration, const qasr_vad_config* cfg, int filter_durations, float* segments,
+                      size_t cap);
+/* PyannoteVADModel.detectSpeech (SpeechVAD.swift:89-140): windows of cfg->window_duration at cfg->step_ratio, aggregated and binarised
+ * with the 589-frame duration.  cfg NULL = VADConfig.default.  The segment count or -status; sample_rate != 16000 -> -QASR_ERR_UNSUPPORTED. */
+int qasr_seg_detect_speech(qasr_seg* s, const float* pcm, size_t n, int sample_rate, const qasr_seg_vad_config* cfg, float* segments,
+                           size_t cap);
+
+typedef struct qasr_diar_config {      /* DiarizationConfig (DiarizationPipeline.swift:11-39) */
+    float onset, offset, min_speech_duration, min_silence_duration, clustering_threshold;
+} qasr_diar_config;
+typedef struct qasr_diar_segment {     /* DiarizedSegment */
+    float start_time, end_time;
+    int32_t speaker_id;
+} qasr_diar_segment;
+typedef struct qasr_diar_result qasr_diar_result;
+int qasr_diar_default_config(qasr_diar_config* out);                /* 0.5, 0.3, 0.3, 0.15, 0.715 */
+/* cosineDistance (DiarizationHelpers.swift:168-182), pure CPU: 2 for empty input or a denominator <= 1e-10 */
+float qasr_diar_cosine_distance(const float* a, const float* b, size_t n);
+/* constrainedAgglomerativeClustering (DiarizationHelpers.swift:83-164), pure CPU: centroid linkage, items of one window never merge,
+ * first-found minimum over the sorted active list, size-weighted centroids, compact ids.  embeddings [n][dim]; assignment [n];
+ * centroids [n][dim] capacity (may be NULL).  The cluster count or -status. */
+int qasr_diar_cluster(const float* embeddings, const int32_t* window_index, size_t n, size_t dim, float threshold, int32_t* assignment,
+                      float* centroids);
+/* mergeSegments (DiarizationHelpers.swift:11-45), pure CPU: out has room for n; the count.  Speakers in ascending id, stable sorts. */
+int qasr_diar_merge_segments(const qasr_diar_segment* in, size_t n, float min_silence, qasr_diar_segment* out);
+int qasr_diar_compact_speaker_ids(qasr_diar_segment* segments, size_t n);    /* compactSpeakerIds (:48-58), in place */
+/* PyannoteDiarizationPipeline.diarize (DiarizationPipeline.swift:209-537) behind one call: optional Silero pre-filter on vad's stream 0
+ * (vad NULL = none; an empty mask gives an empty result), 10 s windows at a 5 s step, the solo-speaker clip of every (window, local
+ * speaker) with at least 0.5 s, ALL clips in one qasr_spk_embed_batch, clustering, centre-zone ownership, trimToSpeechMask, sort,
+ * compact, merge.  cfg NULL = the default.  *out is released with qasr_diar_result_free.  Errors are reported on seg. */
+int qasr_diarize(qasr_seg* seg, qasr_spk* spk, qasr_vad* vad, const float* pcm, size_t n, int sample_rate, const qasr_diar_config* cfg,
+                 qasr_diar_result** out);
+const qasr_diar_segment* qasr_diar_result_segments(const qasr_diar_result* r, size_t* count);
+int qasr_diar_result_num_speakers(const qasr_diar_result* r);
+const float* qasr_diar_result_embeddings(const qasr_diar_result* r);         /* [num_speakers][256]; truncated / zero-padded as :519-530 */
+void qasr_diar_result_free(qasr_diar_result* r);
+/* the cosine argmax half of extractSpeaker (DiarizationPipeline.swift:259-275): (start, end) pairs of the speaker whose centroid is
+ * most similar to target[256]; the count (first cap written) or -status */
+int qasr_diar_extract_speaker(const qasr_diar_result* r, const float* target, float* segments, size_t cap);
+
 /* transducer greedy loops (pure CPU).  The caller owns the networks and their state:
  *   decoder_step(ctx, token)  advance the prediction network with `token` (the loops prime it with the blank id where the reference does)
  *   joint(ctx, frame, token_logits[vocab_size + 1], duration_logits[n_durations] or NULL)  logits for encoder frame `frame` and the

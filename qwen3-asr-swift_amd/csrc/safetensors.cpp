@@ -126,7 +126,8 @@ static std::string shape_str(const std::vector<int64_t>& s) {
 }
 
 CheckedWeights load_checked_f32(const std::string& dir, const char* who,
-                                const std::vector<std::pair<std::string, std::vector<int64_t>>>& shapes, bool refuse_unknown_keys) {
+                                const std::vector<std::pair<std::string, std::vector<int64_t>>>& shapes, bool refuse_unknown_keys,
+                                float (*optional_default)(const std::string&)) {
     const std::string pre = std::string(who) + ": ", path = dir + "/model.safetensors";
     FILE* f = fopen(path.c_str(), "rb");
     if (!f) throw WeightLoadError(QASR_ERR_IO, pre + "cannot open " + path);
@@ -143,7 +144,14 @@ CheckedWeights load_checked_f32(const std::string& dir, const char* who,
     CheckedWeights w;
     for (const auto& ks : shapes) {
         auto it = st->entries.find(ks.first);
-        if (it == st->entries.end()) throw WeightLoadError(QASR_ERR_IO, pre + "missing tensor " + ks.first);
+        if (it == st->entries.end()) {
+            const float dflt = optional_default ? optional_default(ks.first) : -1.0f;
+            if (dflt < 0.0f) throw WeightLoadError(QASR_ERR_IO, pre + "missing tensor " + ks.first);
+            size_t numel = 1;                              // the module's deterministic initial value stays in place
+            for (auto d : ks.second) numel *= (size_t)d;
+            w.t[ks.first] = std::vector<float>(numel, dflt);
+            continue;
+        }
         const SafeEntry& e = it->second;
         if (e.shape != ks.second)
             throw WeightLoadError(QASR_ERR_INVALID, pre + "tensor " + ks.first + " has shape " + shape_str(e.shape) + ", expected " +

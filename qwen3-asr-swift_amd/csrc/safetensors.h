@@ -41,8 +41,11 @@ struct WeightLoadError : std::runtime_error {      // code: QASR_ERR_IO (missing
     WeightLoadError(int c, const std::string& m) : std::runtime_error(m), code(c) {}
 };
 // reads <dir>/model.safetensors against a key -> shape table: presence, shape and dtype (F32 / F16 / BF16) of every entry, unknown keys
-// refused on request; messages start with "<who>: ".  Host work only: no HIP call.
+// refused on request; messages start with "<who>: ".  Host work only: no HIP call.  optional_default: for a key the file lacks, the
+// value (>= 0) the reference's module holds before loading, which then fills the tensor; a negative answer (or no function) makes the
+// key required.
 CheckedWeights load_checked_f32(const std::string& dir, const char* who,
-                                const std::vector<std::pair<std::string, std::vector<int64_t>>>& shapes, bool refuse_unknown_keys);
+                                const std::vector<std::pair<std::string, std::vector<int64_t>>>& shapes, bool refuse_unknown_keys,
+                                float (*optional_default)(const std::string&) = nullptr);
 
 }  // namespace qasr

@@ -81,6 +81,18 @@ class QasrVadConfig(C.Structure):
     _fields_ = [("onset", C.c_float), ("offset", C.c_float), ("min_speech_duration", C.c_float), ("min_silence_duration", C.c_float)]
 
 
+class QasrSegVadConfig(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("onset", "offset", "min_speech_duration", "min_silence_duration", "window_duration", "step_ratio")]
+
+
+class QasrDiarConfig(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("onset", "offset", "min_speech_duration", "min_silence_duration", "clustering_threshold")]
+
+
+class QasrDiarSegment(C.Structure):
+    _fields_ = [("start_time", C.c_float), ("end_time", C.c_float), ("speaker_id", C.c_int32)]
+
+
 VAD_PROCESS_FN = C.CFUNCTYPE(C.c_float, C.c_void_p, C.POINTER(C.c_float), C.c_size_t)
 VAD_RESET_FN = C.CFUNCTYPE(None, C.c_void_p)
 VAD_CHUNK_FN = C.CFUNCTYPE(C.c_size_t, C.c_void_p)
@@ -213,6 +225,32 @@ SIGNATURES = {
     "qasr_spk_num_frames": (C.c_int, [C.c_size_t]),
     "qasr_spk_cosine_similarity": (C.c_float, [_F, _F, C.c_size_t]),
     "qasr_spk_timing": (C.c_int, [_E, _F]),
+    "qasr_seg_vad_default_config": (C.c_int, [_P(QasrSegVadConfig)]),
+    "qasr_seg_create": (C.c_int, [C.c_int, C.c_char_p, C.c_int, _E, _P(_E)]),
+    "qasr_seg_destroy": (None, [_E]),
+    "qasr_seg_last_error": (C.c_char_p, [_E]),
+    "qasr_seg_is_loaded": (C.c_int, [_E]),
+    "qasr_seg_unload": (C.c_int, [_E]),
+    "qasr_seg_memory_footprint": (C.c_size_t, [_E]),
+    "qasr_seg_num_frames": (C.c_int, [C.c_size_t]),
+    "qasr_seg_timing": (C.c_int, [_E, _F]),
+    "qasr_seg_forward": (C.c_int, [_E, _F, C.c_size_t, C.c_size_t, _F, _F, _F]),
+    "qasr_seg_window_positions": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, _P(C.c_int64), _P(C.c_int64), C.c_size_t]),
+    "qasr_seg_windows": (C.c_int, [_E, _F, C.c_size_t, C.c_size_t, C.c_size_t, _F, _F, _F, _P(C.c_int64), _P(C.c_int64), C.c_size_t]),
+    "qasr_seg_aggregate_frames": (C.c_int, [_F, C.c_size_t, C.c_size_t, _P(C.c_int64), C.c_size_t, C.c_int, C.c_float, _F, C.c_size_t]),
+    "qasr_seg_binarize": (C.c_int, [_F, C.c_size_t, C.c_float, _P(QasrVadConfig), C.c_int, _F, C.c_size_t]),
+    "qasr_seg_detect_speech": (C.c_int, [_E, _F, C.c_size_t, C.c_int, _P(QasrSegVadConfig), _F, C.c_size_t]),
+    "qasr_diar_default_config": (C.c_int, [_P(QasrDiarConfig)]),
+    "qasr_diar_cosine_distance": (C.c_float, [_F, _F, C.c_size_t]),
+    "qasr_diar_cluster": (C.c_int, [_F, _I, C.c_size_t, C.c_size_t, C.c_float, _I, _F]),
+    "qasr_diar_merge_segments": (C.c_int, [_P(QasrDiarSegment), C.c_size_t, C.c_float, _P(QasrDiarSegment)]),
+    "qasr_diar_compact_speaker_ids": (C.c_int, [_P(QasrDiarSegment), C.c_size_t]),
+    "qasr_diarize": (C.c_int, [_E, _E, _E, _F, C.c_size_t, C.c_int, _P(QasrDiarConfig), _P(_E)]),
+    "qasr_diar_result_segments": (_P(QasrDiarSegment), [_E, _P(C.c_size_t)]),
+    "qasr_diar_result_num_speakers": (C.c_int, [_E]),
+    "qasr_diar_result_embeddings": (_F, [_E]),
+    "qasr_diar_result_free": (None, [_E]),
+    "qasr_diar_extract_speaker": (C.c_int, [_E, _F, _F, C.c_size_t]),
     "qasr_transducer_default_config": (C.c_int, [C.c_char_p, _P(QasrTransducerConfig)]),
     "qasr_tdt_greedy_decode": (C.c_int, [_P(QasrTransducerConfig), _P(QasrTransducerCallbacks), C.c_int32, _I, _F, C.c_int32, _F]),
     "qasr_rnnt_greedy_decode": (C.c_int, [_P(QasrTransducerConfig), _P(QasrTransducerCallbacks), C.c_int32, C.c_int32, _I, _F, C.c_int32, _I]),

@@ -346,3 +346,72 @@ def write_wespeaker_safetensors(sd: dict, model_dir: str, dtype: str = "F32", dr
     for k, v in (extra.items() if isinstance(extra, dict) else extra):
         d[k] = np.asarray(v, dtype=np.float32)
     return _write_safetensors(d, model_dir, dtype, drop, reshape)
+
+
+def pyannote_tensor_shapes() -> dict:
+    """key -> shape of every PyanNet segmentation tensor (Segmentation.swift, SincNet.swift, BiLSTM.swift; MLX conv layout [out, k, in])."""
+    s = {"sincnet.wav_norm.weight": (1,), "sincnet.wav_norm.bias": (1,)}
+    for i, (co, k, ci) in enumerate([(80, 251, 1), (60, 5, 80), (60, 5, 60)]):
+        s[f"sincnet.conv.{i}.weight"], s[f"sincnet.conv.{i}.bias"] = (co, k, ci), (co,)
+        s[f"sincnet.norm.{i}.weight"], s[f"sincnet.norm.{i}.bias"] = (co,), (co,)
+    for d in ("lstm_fwd", "lstm_bwd"):
+        for l in range(4):
+            p = f"{d}.layers.{l}."
+            s[p + "Wx"], s[p + "Wh"], s[p + "bias"] = (512, 60 if l == 0 else 256), (512, 128), (512,)
+    s["linear.0.weight"], s["linear.0.bias"] = (128, 256), (128,)
+    s["linear.1.weight"], s["linear.1.bias"] = (128, 128), (128,)
+    s["classifier.weight"], s["classifier.bias"] = (7, 128), (7,)
+    return s
+
+
+def synth_pyannote_state_dict(seed: int = 0) -> dict:
+    """Seeded PyanNet-shaped weights (float32 numpy, reference keys and layouts).
+
+    sincnet.conv.0 holds real band-passes, as the converted checkpoint does: 80 Hamming-windowed differences of two sincs with mel-spaced
+    edges from 40 Hz to 7.6 kHz, unit energy.  The rest is fan-in scaled; the LSTMs carry a forget-gate bias so their state follows the
+    0.25 s level pattern of the test clips instead of single frames, and the classifier has a gain of several units so that the
+    posteriors move across the thresholds with the input (tests/test_pyannote_cpu.py asserts what the tests need of them)."""
+    rng = np.random.default_rng(9111 + seed)
+    sd = {"sincnet.wav_norm.weight": np.array([0.9]), "sincnet.wav_norm.bias": np.array([0.02])}
+    mel = lambda f: 2595.0 * np.log10(1.0 + f / 700.0)
+    hz = lambda m: 700.0 * (10.0 ** (m / 2595.0) - 1.0)
+    edges = hz(np.linspace(mel(40.0), mel(7600.0), 82))
+    t = (np.arange(251) - 125) / 16000.0
+    ham = 0.54 - 0.46 * np.cos(2 * np.pi * np.arange(251) / 250)
+    bank = np.zeros((80, 251))
+    for c in range(80):
+        lo, hi = edges[c], edges[c + 2]
+        f = (2 * hi * np.sinc(2 * hi * t) - 2 * lo * np.sinc(2 * lo * t)) * ham
+        bank[c] = f / np.sqrt((f * f).sum())
+    sd["sincnet.conv.0.weight"] = bank[:, :, None]
+    sd["sincnet.conv.0.bias"] = 0.01 * rng.standard_normal(80)
+    for i, (co, k, ci) in enumerate([(80, 251, 1), (60, 5, 80), (60, 5, 60)]):
+        if i > 0:
+            sd[f"sincnet.conv.{i}.weight"] = 1.5 * rng.standard_normal((co, k, ci)) / np.sqrt(k * ci)
+            sd[f"sincnet.conv.{i}.bias"] = 0.05 * rng.standard_normal(co)
+        sd[f"sincnet.norm.{i}.weight"] = 1.0 + 0.1 * rng.standard_normal(co)
+        sd[f"sincnet.norm.{i}.bias"] = 0.1 * rng.standard_normal(co)
+    for d in ("lstm_fwd", "lstm_bwd"):
+        for l in range(4):
+            p, cin = f"{d}.layers.{l}.", (60 if l == 0 else 256)
+            sd[p + "Wx"] = 1.2 * rng.standard_normal((512, cin)) / np.sqrt(cin)
+            sd[p + "Wh"] = 0.6 * rng.standard_normal((512, 128)) / np.sqrt(128)
+            b = 0.1 * rng.standard_normal(512)
+            b[128:256] += 1.5                                          # forget gate: the state outlives a frame
+            sd[p + "bias"] = b
+    sd["linear.0.weight"] = 1.4 * rng.standard_normal((128, 256)) / np.sqrt(256)
+    sd["linear.0.bias"] = 0.05 * rng.standard_normal(128)
+    sd["linear.1.weight"] = 1.4 * rng.standard_normal((128, 128)) / np.sqrt(128)
+    sd["linear.1.bias"] = 0.05 * rng.standard_normal(128)
+    sd["classifier.weight"] = PYANNOTE_CLASSIFIER_GAIN * rng.standard_normal((7, 128)) / np.sqrt(128)
+    sd["classifier.bias"] = np.zeros(7)
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in sd.items()}
+
+
+PYANNOTE_CLASSIFIER_GAIN = 8.0
+
+
+def write_pyannote_safetensors(sd: dict, model_dir: str, dtype: str = "F32", drop=(), extra=(), reshape=None) -> str:
+    """Writes `sd` as model_dir/model.safetensors (dtype F32 | F16 | BF16; F64 for the dtype error).  `drop`: keys left out, `extra`:
+    (key, array) pairs added (unknown keys), `reshape`: {key: shape} written with a wrong shape.  Returns the file path."""
+    return write_wespeaker_safetensors(sd, model_dir, dtype, drop, extra, reshape)
