@@ -621,6 +621,60 @@ void qasr_diar_result_free(qasr_diar_result* r);
  * most similar to target[256]; the count (first cap written) or -status */
 int qasr_diar_extract_speaker(const qasr_diar_result* r, const float* target, float* segments, size_t cap);
 
+/* ---- Open-Unmix music source separation (csrc/sep_openunmix.hip, csrc/api_sep.cpp) ----------------------------------------------------
+ * Reference: Sources/SourceSeparation.  What each entry replaces:
+ *   SourceSeparator.fromPretrained (SourceSeparation.swift:178-240), from a local directory        -> qasr_sep_create
+ *   SourceSeparator.separate(audio:sampleRate:targets:wiener:) (:45-175), one file or many         -> qasr_sep_separate / _separate_batch
+ *   STFTProcessor.forward + magnitude (STFT.swift:40-102)                                           -> qasr_sep_stft
+ *   OpenUnmixStemModel.callAsFunction of the four stems (OpenUnmixModel.swift:91-127, 175-301)      -> qasr_sep_masks
+ *   WienerFilterMLX.applyMLX (WienerFilterMLX.swift:26-84, 139-261)                                 -> qasr_sep_wiener
+ *   STFTProcessor.inverseMLX (STFT.swift:183-231)                                                   -> qasr_sep_istft
+ * Stems are numbered vocals 0, drums 1, bass 2, other 3; a target mask has bit s set for stem s; outputs keep that order.
+ * Precision: f32 throughout, as the reference.  A file's stems are bit-identical alone, in any batch and position, under any
+ * max_batch_samples, and run to run.  One object, one thread at a time. */
+typedef struct qasr_sep qasr_sep;
+typedef struct qasr_sep_config {
+    int32_t wiener;                    /* 1: Wiener EM when more than one target is asked (SourceSeparation.swift:127) */
+    int32_t wiener_iterations;         /* EM rounds, 1 as separate passes (1..16) */
+    int32_t wiener_window;             /* frames per EM window, 300 (WienerFilterMLX.swift:34) */
+} qasr_sep_config;
+int qasr_sep_default_config(qasr_sep_config* out);                  /* 1, 1, 300 */
+/* model_dir holds {vocals,drums,bass,other}.safetensors in the reference's keys.  The preset (hidden 512 umxhq | 1024 umxl,
+ * OpenUnmixConfig.swift:24-46) is read from the shape of fc1.weight.  Every file, key, shape and dtype (F32 / F16 / BF16, widened to
+ * f32) is checked before any HIP call: missing file or key -> QASR_ERR_IO, wrong shape or dtype or an unknown key -> QASR_ERR_INVALID,
+ * file and key named in qasr_sep_last_error(NULL).  max_batch_samples: samples per channel one device pass holds (0 = 64 x 10 s);
+ * larger calls run as several passes, split between files, with identical results.  order_with: as for qasr_seg_create. */
+int qasr_sep_create(int device, const char* model_dir, size_t max_batch_samples, qasr_engine* order_with, qasr_sep** out);
+void qasr_sep_destroy(qasr_sep* s);
+const char* qasr_sep_last_error(const qasr_sep* s);                 /* s may be NULL: last create() failure */
+int qasr_sep_is_loaded(const qasr_sep* s);
+int qasr_sep_unload(qasr_sep* s);                                   /* later device calls return QASR_ERR_NOT_LOADED */
+size_t qasr_sep_memory_footprint(const qasr_sep* s);                /* parameter bytes of the four stems as stored, 0 unloaded */
+int qasr_sep_hidden_size(const qasr_sep* s);                        /* 512 | 1024 */
+int qasr_sep_sample_rate(void);                                     /* 44100 */
+int64_t qasr_sep_num_frames(size_t n);                              /* T = n / 1024 + 1 (STFT.swift:60).  Pure CPU. */
+int qasr_sep_timing(const qasr_sep* s, float* ms);                  /* ms[4]: device time of the last call's stft, network, wiener, istft */
+/* the recurrence kernel's form: 0 (default) W_hh streamed from L2 every step | 1 its first columns resident in registers.  Both
+ * sum in the same order and give the same bits. */
+int qasr_sep_set_recurrence_form(qasr_sep* s, int form);
+/* separate: left[b] / right[b] hold n[b] samples at 44.1 kHz (any other rate: QASR_ERR_UNSUPPORTED; separate() does not resample either,
+ * whatever its comment says); right[b] == NULL duplicates the mono channel (:52-58).  out[b] receives [targets asked, in stem order][2][n[b]].
+ * cfg NULL = the default.  An empty file: QASR_ERR_EMPTY_AUDIO; a file over max_batch_samples: QASR_ERR_CAPACITY. */
+int qasr_sep_separate_batch(qasr_sep* s, const float* const* left, const float* const* right, const size_t* n, size_t B, int sample_rate,
+                            unsigned target_mask, const qasr_sep_config* cfg, float* const* out);
+int qasr_sep_separate(qasr_sep* s, const float* left, const float* right, size_t n, int sample_rate, unsigned target_mask,
+                      const qasr_sep_config* cfg, float* out);
+/* stage entry points.  stft: re, im, magnitude [T][2][2049] each (any may be NULL), T = qasr_sep_num_frames(n). */
+int qasr_sep_stft(qasr_sep* s, const float* left, const float* right, size_t n, float* re, float* im, float* magnitude);
+/* the four stem networks on B files' magnitudes [sum T][2][2049] (file b has T[b] frames): masked magnitudes [4][sum T][2][2049] */
+int qasr_sep_masks(qasr_sep* s, const float* magnitude, const size_t* T, size_t B, float* out);
+/* Wiener EM of one file: masked [n_sources][T][2][2049], mixture STFT re / im [T][2][2049] -> out_re / out_im [n_sources][T][2][2049];
+ * cfg gives the rounds and the window (cfg->wiener is not read) */
+int qasr_sep_wiener(qasr_sep* s, const float* masked, int n_sources, const float* re, const float* im, size_t T, const qasr_sep_config* cfg,
+                    float* out_re, float* out_im);
+/* inverse STFT of n_spectra (1..4) spectra [n_spectra][T][2][2049] with T = length / 1024 + 1 -> out [n_spectra][2][length] */
+int qasr_sep_istft(qasr_sep* s, const float* re, const float* im, int n_spectra, size_t T, size_t length, float* out);
+
 /* transducer greedy loops (pure CPU).  The caller owns the networks and their state:
  *   decoder_step(ctx, token)  advance the prediction network with `token` (the loops prime it with the blank id where the reference does)
  *   joint(ctx, frame, token_logits[vocab_size + 1], duration_logits[n_durations] or NULL)  logits for encoder frame `frame` and the

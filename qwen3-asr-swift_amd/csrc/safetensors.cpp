@@ -70,9 +70,10 @@ float safe_elem_f32(const SafeEntry& e, size_t i) {
 
 SafeTensorsDir::~SafeTensorsDir() = default;
 
-SafeTensorsDir::SafeTensorsDir(const std::string& dir) {
+SafeTensorsDir::SafeTensorsDir(const std::string& dir, const std::string& only_file) {
     std::vector<std::string> files;
-    if (DIR* d = opendir(dir.c_str())) {
+    if (!only_file.empty()) files.push_back(dir + "/" + only_file);
+    else if (DIR* d = opendir(dir.c_str())) {
         while (dirent* de = readdir(d)) {
             std::string f = de->d_name;
             if (f.size() > 12 && f.compare(f.size() - 12, 12, ".safetensors") == 0) files.push_back(dir + "/" + f);
@@ -127,13 +128,13 @@ static std::string shape_str(const std::vector<int64_t>& s) {
 
 CheckedWeights load_checked_f32(const std::string& dir, const char* who,
                                 const std::vector<std::pair<std::string, std::vector<int64_t>>>& shapes, bool refuse_unknown_keys,
-                                float (*optional_default)(const std::string&)) {
-    const std::string pre = std::string(who) + ": ", path = dir + "/model.safetensors";
+                                float (*optional_default)(const std::string&), const char* file) {
+    const std::string pre = std::string(who) + ": ", path = dir + "/" + (file ? file : "model.safetensors");
     FILE* f = fopen(path.c_str(), "rb");
     if (!f) throw WeightLoadError(QASR_ERR_IO, pre + "cannot open " + path);
     fclose(f);
     std::unique_ptr<SafeTensorsDir> st;
-    try { st = std::make_unique<SafeTensorsDir>(dir); }
+    try { st = std::make_unique<SafeTensorsDir>(dir, file ? file : ""); }
     catch (const std::exception& ex) { throw WeightLoadError(QASR_ERR_IO, pre + ex.what()); }
     if (refuse_unknown_keys)                               // update(parameters:verify: .noUnusedKeys)
         for (const auto& kv : st->entries) {

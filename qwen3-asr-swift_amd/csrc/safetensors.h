@@ -23,7 +23,8 @@ float safe_elem_f32(const SafeEntry& e, size_t i);
 
 class SafeTensorsDir {
 public:
-    explicit SafeTensorsDir(const std::string& dir);     // maps every *.safetensors of the directory, validates the headers
+    // maps every *.safetensors of the directory (only_file given: that one file of it), validates the headers
+    explicit SafeTensorsDir(const std::string& dir, const std::string& only_file = "");
     ~SafeTensorsDir();
     std::map<std::string, SafeEntry> entries;
 private:
@@ -40,12 +41,12 @@ struct WeightLoadError : std::runtime_error {      // code: QASR_ERR_IO (missing
     int code;
     WeightLoadError(int c, const std::string& m) : std::runtime_error(m), code(c) {}
 };
-// reads <dir>/model.safetensors against a key -> shape table: presence, shape and dtype (F32 / F16 / BF16) of every entry, unknown keys
+// reads <dir>/<file> (model.safetensors unless named; a named file is read alone, the directory's other files are left out) against a key -> shape table: presence, shape and dtype (F32 / F16 / BF16) of every entry, unknown keys
 // refused on request; messages start with "<who>: ".  Host work only: no HIP call.  optional_default: for a key the file lacks, the
 // value (>= 0) the reference's module holds before loading, which then fills the tensor; a negative answer (or no function) makes the
 // key required.
 CheckedWeights load_checked_f32(const std::string& dir, const char* who,
                                 const std::vector<std::pair<std::string, std::vector<int64_t>>>& shapes, bool refuse_unknown_keys,
-                                float (*optional_default)(const std::string&) = nullptr);
+                                float (*optional_default)(const std::string&) = nullptr, const char* file = nullptr);
 
 }  // namespace qasr

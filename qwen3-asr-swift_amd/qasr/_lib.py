@@ -85,6 +85,10 @@ class QasrSegVadConfig(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("onset", "offset", "min_speech_duration", "min_silence_duration", "window_duration", "step_ratio")]
 
 
+class QasrSepConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("wiener", "wiener_iterations", "wiener_window")]
+
+
 class QasrDiarConfig(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("onset", "offset", "min_speech_duration", "min_silence_duration", "clustering_threshold")]
 
@@ -251,6 +255,24 @@ SIGNATURES = {
     "qasr_diar_result_embeddings": (_F, [_E]),
     "qasr_diar_result_free": (None, [_E]),
     "qasr_diar_extract_speaker": (C.c_int, [_E, _F, _F, C.c_size_t]),
+    "qasr_sep_default_config": (C.c_int, [_P(QasrSepConfig)]),
+    "qasr_sep_create": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t, _E, _P(_E)]),
+    "qasr_sep_destroy": (None, [_E]),
+    "qasr_sep_last_error": (C.c_char_p, [_E]),
+    "qasr_sep_is_loaded": (C.c_int, [_E]),
+    "qasr_sep_unload": (C.c_int, [_E]),
+    "qasr_sep_memory_footprint": (C.c_size_t, [_E]),
+    "qasr_sep_hidden_size": (C.c_int, [_E]),
+    "qasr_sep_sample_rate": (C.c_int, []),
+    "qasr_sep_num_frames": (C.c_int64, [C.c_size_t]),
+    "qasr_sep_timing": (C.c_int, [_E, _F]),
+    "qasr_sep_set_recurrence_form": (C.c_int, [_E, C.c_int]),
+    "qasr_sep_separate_batch": (C.c_int, [_E, _P(_F), _P(_F), _P(C.c_size_t), C.c_size_t, C.c_int, C.c_uint, _P(QasrSepConfig), _P(_F)]),
+    "qasr_sep_separate": (C.c_int, [_E, _F, _F, C.c_size_t, C.c_int, C.c_uint, _P(QasrSepConfig), _F]),
+    "qasr_sep_stft": (C.c_int, [_E, _F, _F, C.c_size_t, _F, _F, _F]),
+    "qasr_sep_masks": (C.c_int, [_E, _F, _P(C.c_size_t), C.c_size_t, _F]),
+    "qasr_sep_wiener": (C.c_int, [_E, _F, C.c_int, _F, _F, C.c_size_t, _P(QasrSepConfig), _F, _F]),
+    "qasr_sep_istft": (C.c_int, [_E, _F, _F, C.c_int, C.c_size_t, C.c_size_t, _F]),
     "qasr_transducer_default_config": (C.c_int, [C.c_char_p, _P(QasrTransducerConfig)]),
     "qasr_tdt_greedy_decode": (C.c_int, [_P(QasrTransducerConfig), _P(QasrTransducerCallbacks), C.c_int32, _I, _F, C.c_int32, _F]),
     "qasr_rnnt_greedy_decode": (C.c_int, [_P(QasrTransducerConfig), _P(QasrTransducerCallbacks), C.c_int32, C.c_int32, _I, _F, C.c_int32, _I]),

@@ -415,3 +415,71 @@ def write_pyannote_safetensors(sd: dict, model_dir: str, dtype: str = "F32", dro
     """Writes `sd` as model_dir/model.safetensors (dtype F32 | F16 | BF16; F64 for the dtype error).  `drop`: keys left out, `extra`:
     (key, array) pairs added (unknown keys), `reshape`: {key: shape} written with a wrong shape.  Returns the file path."""
     return write_wespeaker_safetensors(sd, model_dir, dtype, drop, extra, reshape)
+
+
+OPENUNMIX_STEMS = ("vocals", "drums", "bass", "other")
+
+
+def openunmix_tensor_shapes(hidden: int = 512) -> dict:
+    """key -> shape of every tensor of one Open-Unmix stem file (OpenUnmixModel.swift:59-85, 229-236)."""
+    H = hidden
+    s = {"input_mean": (1487,), "input_scale": (1487,), "output_mean": (2049,), "output_scale": (2049,),
+         "fc1.weight": (H, 2974), "fc2.weight": (H, 2 * H), "fc3.weight": (4098, H)}
+    for i, f in enumerate((H, H, 4098)):
+        for k in ("weight", "bias", "running_mean", "running_var"):
+            s[f"bn{i + 1}.{k}"] = (f,)
+    for l in range(3):
+        for d in ("forward", "backward"):
+            p = f"lstm.layers.{l}.{d}."
+            s[p + "weight_ih"], s[p + "weight_hh"] = (2 * H, H), (2 * H, H // 2)
+            s[p + "bias_ih"], s[p + "bias_hh"] = (2 * H,), (2 * H,)
+    return s
+
+
+def synth_openunmix_state_dict(seed: int = 0, hidden: int = 512) -> dict:
+    """Seeded Open-Unmix-shaped weights: {stem: {key: float32 array}} in the reference's keys and layouts.
+
+    Fan-in scaled matrices; BatchNorm running statistics away from (0, 1) and affine weights away from (1, 0); input_mean negative and
+    input_scale positive of the order of the real checkpoint's (magnitudes of a few units map to O(1) inputs); output_scale positive and
+    output_mean about 0.6 so the ReLU mask is neither zero everywhere nor saturated (tests/test_openunmix_cpu.py asserts that)."""
+    H = hidden
+    out = {}
+    for si, stem in enumerate(OPENUNMIX_STEMS):
+        rng = np.random.default_rng(77001 + 10 * seed + si)
+        sd = {}
+        sd["input_mean"] = -1.5 + 0.3 * rng.standard_normal(1487)
+        sd["input_scale"] = 0.25 + 0.1 * rng.random(1487)
+        sd["output_mean"] = 0.6 + 0.1 * rng.standard_normal(2049)
+        sd["output_scale"] = 0.5 + 0.2 * rng.random(2049)
+        sd["fc1.weight"] = 1.5 * rng.standard_normal((H, 2974)) / np.sqrt(2974)
+        sd["fc2.weight"] = 1.5 * rng.standard_normal((H, 2 * H)) / np.sqrt(2 * H)
+        sd["fc3.weight"] = 1.5 * rng.standard_normal((4098, H)) / np.sqrt(H)
+        for i, f in enumerate((H, H, 4098)):
+            sd[f"bn{i + 1}.weight"] = 1.0 + 0.2 * rng.standard_normal(f)
+            sd[f"bn{i + 1}.bias"] = 0.1 * rng.standard_normal(f)
+            sd[f"bn{i + 1}.running_mean"] = 0.2 * rng.standard_normal(f)
+            sd[f"bn{i + 1}.running_var"] = 0.5 + rng.random(f)
+        for l in range(3):
+            for d in ("forward", "backward"):
+                p = f"lstm.layers.{l}.{d}."
+                sd[p + "weight_ih"] = 1.2 * rng.standard_normal((2 * H, H)) / np.sqrt(H)
+                sd[p + "weight_hh"] = 0.8 * rng.standard_normal((2 * H, H // 2)) / np.sqrt(H // 2)
+                sd[p + "bias_ih"] = 0.1 * rng.standard_normal(2 * H)
+                b = 0.1 * rng.standard_normal(2 * H)
+                b[H // 2:H] += 1.0                                       # forget gate: the state outlives a frame
+                sd[p + "bias_hh"] = b
+        out[stem] = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in sd.items()}
+    return out
+
+
+def write_openunmix_safetensors(sd: dict, model_dir: str, dtype: str = "F32", drop=(), reshape=None, skip_stems=()) -> str:
+    """Writes {stem: state dict} as model_dir/{vocals,drums,bass,other}.safetensors.  For the loader's error tests: `drop` keys are left
+    out and `reshape` {key: shape} written with a wrong shape, both in the "drums" file only; `skip_stems` files are not written."""
+    import os
+    for stem in OPENUNMIX_STEMS:
+        if stem in skip_stems or stem not in sd:
+            continue
+        tweak = stem == "drums"
+        path = _write_safetensors(sd[stem], model_dir, dtype, drop if tweak else (), reshape if tweak else None)
+        os.replace(path, os.path.join(model_dir, stem + ".safetensors"))
+    return model_dir
