@@ -675,6 +675,58 @@ int qasr_sep_wiener(qasr_sep* s, const float* masked, int n_sources, const float
 /* inverse STFT of n_spectra (1..4) spectra [n_spectra][T][2][2049] with T = length / 1024 + 1 -> out [n_spectra][2][length] */
 int qasr_sep_istft(qasr_sep* s, const float* re, const float* im, int n_spectra, size_t T, size_t length, float* out);
 
+/* ---- Qwen3-TTS 12.5 Hz speech tokenizer decoder (csrc/codec_qwen3tts.hip, csrc/api_codec.cpp) -----------------------------------------
+ * Reference: Sources/Qwen3TTS/SpeechTokenizerDecoder.swift.  16 code streams at 12.5 Hz -> a 24 kHz waveform.  What each entry replaces:
+ *   TTSWeightLoader.loadSpeechTokenizerDecoderWeights (TTSWeightLoading.swift:190-247), local directory -> qasr_codec_create
+ *   SpeechTokenizerDecoder.callAsFunction (:658-688)                                                      -> qasr_codec_forward
+ *   chunkedDecode's window loop (:696-733)                                                                -> qasr_codec_window_positions
+ *   decode(codes:) (:739-744) and decodeBatch (:750-752)                                                  -> qasr_codec_decode / _decode_batch
+ *   SplitResidualVectorQuantizer.decode (:513-521)                                                        -> qasr_codec_quantizer_decode
+ *   DecoderTransformer.callAsFunction (:368-391)                                                          -> qasr_codec_pre_transformer
+ * Codes are int32, one utterance [num_quantizers][T] with quantizer 0 the semantic stream.  Precision: f32 throughout, as the reference.
+ * The chunking is part of the result (windows of 25 frames after 10 frames of context, one pass up to 35 frames).  A window's samples are
+ * bit-identical alone, in any batch and place, under any max_windows, and run to run.  One object, one thread
+ * at a time.  Not covered: the tokenizer's encoder, the Talker, the code predictor, bf16 or quantised forms, streaming decode. */
+typedef struct qasr_codec qasr_codec;
+/* model_dir holds model.safetensors with the decoder.* keys in the PyTorch layouts (conv [out][in][k], transposed conv [in][out][k]); a
+ * codebook is read from `..._codebook.embed`, else from embedding_sum / max(cluster_usage, 1e-7) (TTSWeightLoading.swift:280-301).  The
+ * geometry is SpeechTokenizerDecoderConfig's defaults (Configuration.swift:128-148) unless model_dir/config.json carries a "decoder_config"
+ * object (latent_dim, decoder_dim, hidden_size, num_heads | num_attention_heads, head_dim, num_layers | num_hidden_layers, upsample_rates,
+ * upsampling_ratios, num_quantizers, codebook_size | semantic_codebook_size + acoustic_codebook_size, codebook_dim, rms_norm_eps);
+ * head_dim must be 64, with four upsample rates and two upsampling ratios whose product is 1920, the samples per frame every output
+ * buffer here is sized by (any other geometry: QASR_ERR_INVALID at create).  Every key, shape and dtype (F32 / F16 / BF16, widened to f32)
+ * is checked before any HIP call: missing file or key -> QASR_ERR_IO, wrong shape, dtype or geometry -> QASR_ERR_INVALID, the tensor named
+ * in qasr_codec_last_error(NULL).  max_windows: windows one device pass holds (0 = 16, at most 512); longer inputs run in several
+ * passes with identical results.  order_with: as for qasr_seg_create. */
+int qasr_codec_create(int device, const char* model_dir, int max_windows, qasr_engine* order_with, qasr_codec** out);
+void qasr_codec_destroy(qasr_codec* c);
+const char* qasr_codec_last_error(const qasr_codec* c);             /* c may be NULL: last create() failure */
+int qasr_codec_is_loaded(const qasr_codec* c);
+int qasr_codec_unload(qasr_codec* c);                               /* later device calls return QASR_ERR_NOT_LOADED */
+size_t qasr_codec_memory_footprint(const qasr_codec* c);            /* parameter bytes as stored, 0 unloaded */
+int qasr_codec_sample_rate(void);                                   /* 24000 (Configuration.swift:143) */
+int qasr_codec_samples_per_frame(void);                             /* 1920 (SpeechTokenizerDecoder.swift:698) */
+int qasr_codec_num_quantizers(const qasr_codec* c);                 /* 16 (Configuration.swift:138) */
+int qasr_codec_hidden_size(const qasr_codec* c);                    /* 512: row width of qasr_codec_quantizer_decode */
+int qasr_codec_latent_dim(const qasr_codec* c);                     /* 1024: row width of qasr_codec_pre_transformer */
+/* callAsFunction (:658-688) on B windows of T <= 35 frames each: codes [B][Q][T] -> out [B][samples_per_frame T].  clip = 0 returns the
+ * signal before the clip to [-1, 1] (:685).  A code outside its codebook is QASR_ERR_INVALID, found on the host before anything is
+ * uploaded; T = 0, T > 35 and a NULL buffer are QASR_ERR_INVALID too. */
+int qasr_codec_forward(qasr_codec* c, const int32_t* codes, size_t B, size_t T, int clip, float* out);
+/* chunkedDecode's windows for T frames (:696-733): window i decodes frames starts[i] .. ends[i] and drops its first context[i] frames.
+ * Returns the window count or -status (-QASR_ERR_CAPACITY when it exceeds cap; nothing is written then).  Pure CPU. */
+int64_t qasr_codec_window_positions(size_t T, int32_t* starts, int32_t* context, int32_t* ends, size_t cap);
+/* decode(codes:) (:739-744): codes [Q][T], any T >= 1 -> out [samples_per_frame T], chunked as above */
+int qasr_codec_decode(qasr_codec* c, const int32_t* codes, size_t T, float* out);
+/* decodeBatch (:750-752) with every window of every item in one batch, max_windows per pass: codes[b] [Q][T[b]] -> out[b] */
+int qasr_codec_decode_batch(qasr_codec* c, const int32_t* const* codes, const size_t* T, size_t B, float* const* out);
+/* stage entry points on B windows of T <= 35 frames: codes [B][Q][T] -> out [B][T][hidden_size]; x [B][T][latent_dim] -> out the same */
+int qasr_codec_quantizer_decode(qasr_codec* c, const int32_t* codes, size_t B, size_t T, float* out);
+int qasr_codec_pre_transformer(qasr_codec* c, const float* x, size_t B, size_t T, float* out);
+/* ms[8]: device time of the last call: quantizer + pre_conv, pre-transformer, the two upsampling stages, decoder blocks 1..4
+ * (decoder.decoder.0 counted with block 1), output conv */
+int qasr_codec_timing(const qasr_codec* c, float* ms);
+
 /* transducer greedy loops (pure CPU).  The caller owns the networks and their state:
  *   decoder_step(ctx, token)  advance the prediction network with `token` (the loops prime it with the blank id where the reference does)
  *   joint(ctx, frame, token_logits[vocab_size + 1], duration_logits[n_durations] or NULL)  logits for encoder frame `frame` and the

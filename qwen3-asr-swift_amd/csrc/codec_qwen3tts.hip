@@ -1,0 +1,746 @@
+// codec_qwen3tts.hip -- the Qwen3-TTS speech tokenizer decoder for gfx950 (codec_qwen3tts.h).  f32 throughout, accurate sinf / expf /
+// erff / sqrtf, no atomics, no vendor BLAS.
+//
+// A pass runs W windows (of any utterances, 1..35 frames each).  Activations are [window rows back to back][C]; a window of F frames
+// whose first frame is row `off` of the 1x tensors owns rows off * r .. (off + F) * r of the tensors at rate r (2, 4, 32, 160, 640,
+// 1920), so one table fstart[frame row] = off serves every rate; row indices are 64-bit.
+// Launches of a pass:
+//   codec_gather_kernel    per frame: codebook 0's vector | the 15 acoustic vectors summed in codebook order -> [M][2 D]
+//   codec_gemm_kernel      the 64 x 64 tiled f32 GEMM of sep_gemm_kernel as an implicit-GEMM causal conv: K = taps x C_in, the A element of
+//                          (row t, tap j, channel c) is x[t - (taps - 1 - j) dilation][c], zero before the window's first row, SnakeBeta
+//                          optionally applied as it is loaded; the epilogue is bias | bias + GELU | bias + residual | layer scale +
+//                          residual | SiLU(gate) x up over interleaved columns.  It runs the two RVQ projections (one GEMM, K = 2 D),
+//                          pre_conv, every Linear, decoder.decoder.0, the k = 7 and k = 1 convs of the residual units, and every
+//                          transposed conv: with k = 2 s, output row t s + j is x[t] W[:, :, j] + x[t - 1] W[:, :, j + s], a two-tap GEMM
+//                          with N = s C_out whose output row [s][C_out] IS rows t s .. t s + s - 1 of the upsampled tensor; the trim
+//                          falls out.  Edge tiles are guarded, not padded.
+//   codec_rms_kernel       RMSNorm, one workgroup per row
+//   codec_attn_kernel      one workgroup per (window, head): q, k (RoPE on the way in, rotate-halves, positions from 0) and v in LDS,
+//                          causal scores, softmax, P V
+//   codec_dwln_kernel      depthwise k = 7 causal conv + LayerNorm, one workgroup per row
+//   codec_out_kernel       final SnakeBeta, the C -> 1 k = 7 conv as one dot of 7 C terms per sample, clip
+// Summation order: every GEMM output is one thread's fmaf chain over k = 0..K-1 (taps outer, channels inner;
+// rows before the window add exact zeros); the row reductions of the norms are a thread's sequential partial over c = tid, tid + 256, ..
+// then a fixed tree; attention sums over d, then over j, in order.  No reduction crosses a window and nothing depends on a window's
+// place, so a window's samples are the same bits alone, in any batch, at any place in it and under any split into passes.
+#include "codec_qwen3tts.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+namespace qasr {
+
+// ---- geometry, keys, windows (host) -------------------------------------------------------------------------------------------------
+void codec_check_geometry(const CodecGeom& g) {
+    auto bad = [](const std::string& m) { throw std::invalid_argument("speech tokenizer decoder: " + m); };
+    if (g.head_dim != 64) bad("head_dim must be 64");
+    if (g.heads < 1 || g.heads > 64) bad("num_heads in 1..64");
+    if (g.layers < 1 || g.layers > 64) bad("num_layers in 1..64");
+    if (g.hidden < 1 || g.hidden > 4096 || g.latent < 1 || g.latent > 4096) bad("hidden_size and latent_dim in 1..4096");
+    if (g.decoder_dim < 16 || g.decoder_dim > 8192 || g.decoder_dim % 16) bad("decoder_dim a multiple of 16 in 16..8192");
+    for (int r : g.rates) if (r < 1 || r > 16) bad("four upsample_rates in 1..16");
+    for (int r : g.ratios) if (r < 1 || r > 16) bad("two upsampling_ratios in 1..16");
+    if (g.quantizers < 2 || g.quantizers > 64) bad("num_quantizers in 2..64");
+    if (g.semantic_size < 1 || g.acoustic_size < 1 || g.semantic_size > (1 << 20) || g.acoustic_size > (1 << 20)) bad("codebook sizes in 1..2^20");
+    if (g.codebook_dim < 1 || g.codebook_dim > 4096) bad("codebook_dim in 1..4096");
+    if (((long)g.semantic_size * g.codebook_dim) % 4 || ((long)g.acoustic_size * g.codebook_dim) % 4) bad("codebook size x codebook_dim a multiple of 4");
+    if (!(g.eps > 0.0f)) bad("rms_norm_eps > 0");
+    // every output buffer of the C ABI is [1920 T] (qasr_codec_samples_per_frame, SpeechTokenizerDecoder.swift:698 fixes it too)
+    if (g.samples_per_frame() != CODEC_SAMPLES_PER_FRAME)
+        bad("upsampling_ratios x upsample_rates multiply to " + std::to_string(g.samples_per_frame()) + " samples per frame, must be 1920");
+}
+
+std::string codec_codebook_prefix(int q) {
+    return q == 0 ? std::string("decoder.quantizer.rvq_first.vq.layers.0._codebook")
+                  : "decoder.quantizer.rvq_rest.vq.layers." + std::to_string(q - 1) + "._codebook";
+}
+
+std::vector<std::pair<std::string, std::vector<int64_t>>> codec_tensor_shapes(const CodecGeom& g, const std::vector<bool>& embed_stored) {
+    std::vector<std::pair<std::string, std::vector<int64_t>>> s;
+    auto add = [&](const std::string& k, std::vector<int64_t> sh) { s.emplace_back(k, std::move(sh)); };
+    const int64_t L = g.latent, H = g.hidden, Dd = g.decoder_dim, D = g.codebook_dim, A = (int64_t)g.heads * g.head_dim;
+    for (int q = 0; q < g.quantizers; ++q) {
+        const int64_t n = q == 0 ? g.semantic_size : g.acoustic_size;
+        const std::string p = codec_codebook_prefix(q);
+        if (embed_stored[q]) add(p + ".embed", {n, D});
+        else { add(p + ".embedding_sum", {n, D}); add(p + ".cluster_usage", {n}); }
+    }
+    add("decoder.quantizer.rvq_first.output_proj.weight", {H, D, 1});
+    add("decoder.quantizer.rvq_rest.output_proj.weight", {H, D, 1});
+    add("decoder.pre_conv.conv.weight", {L, H, 3}); add("decoder.pre_conv.conv.bias", {L});
+    const std::string P = "decoder.pre_transformer.";
+    add(P + "input_proj.weight", {H, L}); add(P + "input_proj.bias", {H});
+    add(P + "output_proj.weight", {L, H}); add(P + "output_proj.bias", {L});
+    add(P + "norm.weight", {H});
+    for (int l = 0; l < g.layers; ++l) {
+        const std::string p = P + "layers." + std::to_string(l) + ".";
+        for (const char* k : {"q_proj", "k_proj", "v_proj"}) add(p + "self_attn." + k + ".weight", {A, H});
+        add(p + "self_attn.o_proj.weight", {H, A});
+        add(p + "input_layernorm.weight", {H}); add(p + "post_attention_layernorm.weight", {H});
+        add(p + "mlp.gate_proj.weight", {2 * H, H}); add(p + "mlp.up_proj.weight", {2 * H, H}); add(p + "mlp.down_proj.weight", {H, 2 * H});
+        add(p + "self_attn_layer_scale.scale", {H}); add(p + "mlp_layer_scale.scale", {H});
+    }
+    for (int i = 0; i < 2; ++i) {
+        const std::string p = "decoder.upsample." + std::to_string(i) + ".";
+        add(p + "0.conv.weight", {L, L, 2 * g.ratios[i]}); add(p + "0.conv.bias", {L});
+        add(p + "1.dwconv.conv.weight", {L, 1, 7}); add(p + "1.dwconv.conv.bias", {L});
+        add(p + "1.norm.weight", {L}); add(p + "1.norm.bias", {L});
+        add(p + "1.pwconv1.weight", {4 * L, L}); add(p + "1.pwconv1.bias", {4 * L});
+        add(p + "1.pwconv2.weight", {L, 4 * L}); add(p + "1.pwconv2.bias", {L});
+        add(p + "1.gamma", {L});
+    }
+    add("decoder.decoder.0.conv.weight", {Dd, L, 7}); add("decoder.decoder.0.conv.bias", {Dd});
+    int64_t c = Dd;
+    for (int b = 0; b < 4; ++b) {
+        const std::string p = "decoder.decoder." + std::to_string(b + 1) + ".block.";
+        const int64_t co = c / 2;
+        add(p + "0.alpha", {c}); add(p + "0.beta", {c});
+        add(p + "1.conv.weight", {c, co, 2 * g.rates[b]}); add(p + "1.conv.bias", {co});
+        for (int j = 2; j <= 4; ++j) {
+            const std::string u = p + std::to_string(j) + ".";
+            for (const char* a : {"act1", "act2"}) { add(u + a + ".alpha", {co}); add(u + a + ".beta", {co}); }
+            add(u + "conv1.conv.weight", {co, co, 7}); add(u + "conv1.conv.bias", {co});
+            add(u + "conv2.conv.weight", {co, co, 1}); add(u + "conv2.conv.bias", {co});
+        }
+        c = co;
+    }
+    add("decoder.decoder.5.alpha", {c}); add("decoder.decoder.5.beta", {c});
+    add("decoder.decoder.6.conv.weight", {1, c, 7}); add("decoder.decoder.6.conv.bias", {1});
+    return s;
+}
+
+std::vector<CodecSpan> codec_window_positions(long T) {
+    std::vector<CodecSpan> out;
+    if (T <= CODEC_CHUNK + CODEC_CONTEXT) { out.push_back({0, 0, (int)T}); return out; }
+    for (long offset = 0; offset < T;) {
+        const long end = std::min(offset + CODEC_CHUNK, T), start = std::max(offset - CODEC_CONTEXT, 0L);
+        out.push_back({(int)start, (int)(offset - start), (int)end});
+        offset = end;
+    }
+    return out;
+}
+
+// ---- kernels ------------------------------------------------------------------------------------------------------------------------
+constexpr int CG_THREADS = 256, CG_T = 64, CG_K = 16, ROW_THREADS = 256;
+enum { E_LIN = 0, E_GELU = 1, E_RES = 2, E_LSRES = 3, E_SWIGLU = 4 };
+
+// x + (1 / exp(beta)) sin^2(exp(alpha) x) with a = exp(alpha), b = 1 / exp(beta) formed at load (SpeechTokenizerDecoder.swift:105-110)
+__device__ __forceinline__ float codec_snake(float x, float a, float b) {
+    const float s = sinf(a * x);
+    return x + b * (s * s);
+}
+
+// sum over the workgroup's 256 values in a fixed tree; every thread gets it.  Ends with a barrier that also frees `red`.
+__device__ __forceinline__ float codec_block_sum(float v, float* red, int tid) {
+    red[tid] = v;
+    __syncthreads();
+    for (int s = ROW_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) red[tid] = red[tid] + red[tid + s];
+        __syncthreads();
+    }
+    const float r = red[0];
+    __syncthreads();
+    return r;
+}
+
+// codes [M][Q]; cb: codebook 0 [S0][D], then Q - 1 codebooks [S1][D]; out [M][2 D] = first | rest summed in codebook order (:449-462)
+__global__ __launch_bounds__(ROW_THREADS) void codec_gather_kernel(const int* __restrict__ codes, int Q, int D, long S0, long S1,
+                                                                   const float* __restrict__ cb, float* __restrict__ out) {
+    const long m = blockIdx.x;
+    const int* c = codes + m * Q;
+    for (int d = threadIdx.x; d < D; d += ROW_THREADS) {
+        out[m * 2 * D + d] = cb[(long)c[0] * D + d];
+        float acc = 0.0f;
+        for (int q = 1; q < Q; ++q) {
+            const float e = cb[(S0 + (long)(q - 1) * S1 + c[q]) * D + d];
+            acc = q == 1 ? e : acc + e;
+        }
+        out[m * 2 * D + D + d] = acc;
+    }
+}
+
+// C = epilogue(sum_k A(m, k) Wt[k][n]), k = j C_in + c <-> x[m - (taps - 1 - j) dil][c].  A [M][C_in], Wt [K][N], fstart[m / rate] * rate is
+// the first row of m's window.  bias[n % bmod] (nullptr: none).  E_SWIGLU: columns 2 i, 2 i + 1 are gate i, up i; C [M][N / 2].
+template <bool SNAKE, int EPI>
+__global__ __launch_bounds__(CG_THREADS) void codec_gemm_kernel(const float* __restrict__ A, long M, int Cin, int taps, int dil, int rate,
+                                                                const int* __restrict__ fstart, const float* __restrict__ Wt, int K, int N,
+                                                                const float* __restrict__ bias, int bmod, const float* __restrict__ sa,
+                                                                const float* __restrict__ sb, const float* __restrict__ ls,
+                                                                const float* R, float* C, int ldc) {
+    __shared__ __attribute__((aligned(16))) float As[CG_K][CG_T + 4];
+    __shared__ __attribute__((aligned(16))) float Bs[CG_K][CG_T];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const long m0 = (long)blockIdx.x * CG_T;
+    const int n0 = blockIdx.y * CG_T;
+    long wstart[4];                                    // first row of the window of each A row this thread loads
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const long m = m0 + ((tid + r * CG_THREADS) >> 4);
+        wstart[r] = m < M ? (long)fstart[m / rate] * rate : 0;
+    }
+    float acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[i][q] = 0.0f;
+    for (int k0 = 0; k0 < K; k0 += CG_K) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int idx = tid + r * CG_THREADS, row = idx >> 4, kk = idx & 15, k = k0 + kk;
+            const long m = m0 + row;
+            float v = 0.0f;                            // rows past M, inputs past K and rows before the window add exact zeros
+            if (m < M && k < K) {
+                const int j = k / Cin, c = k - j * Cin;
+                const long src = m - (long)(taps - 1 - j) * dil;
+                if (src >= wstart[r]) {
+                    v = A[src * Cin + c];
+                    if (SNAKE) v = codec_snake(v, sa[c], sb[c]);
+                }
+            }
+            As[kk][row] = v;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int idx = tid + r * CG_THREADS, kk = idx >> 6, col = idx & 63, k = k0 + kk, n = n0 + col;
+            Bs[kk][col] = (k < K && n < N) ? Wt[(size_t)k * N + n] : 0.0f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < CG_K; ++kk) {
+            const float4 a = lds_read_f4(&As[kk][ty * 4]);
+            const float4 bq = lds_read_f4(&Bs[kk][tx * 4]);
+            const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {bq.x, bq.y, bq.z, bq.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc[i][q] = fmaf(av[i], bv[q], acc[i][q]);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const long m = m0 + ty * 4 + i;
+        if (m >= M) continue;
+        if (EPI == E_SWIGLU) {                         // silu(gate) * up (:340)
+#pragma unroll
+            for (int q = 0; q < 4; q += 2) {
+                const int n = n0 + tx * 4 + q;
+                if (n + 1 >= N) continue;
+                const float g = acc[i][q];
+                C[m * ldc + (n >> 1)] = (g / (1.0f + expf(-g))) * acc[i][q + 1];
+            }
+            continue;
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int n = n0 + tx * 4 + q;
+            if (n >= N) continue;
+            float v = acc[i][q];
+            if (bias) v = v + bias[n % bmod];
+            if (EPI == E_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+            if (EPI == E_RES) v = v + R[m * ldc + n];
+            if (EPI == E_LSRES) v = v * ls[n] + R[m * ldc + n];
+            C[m * ldc + n] = v;
+        }
+    }
+}
+
+// y = x / sqrt(mean(x^2) + eps) * w, one workgroup per row
+__global__ __launch_bounds__(ROW_THREADS) void codec_rms_kernel(const float* __restrict__ x, int C, const float* __restrict__ w, float eps,
+                                                                float* __restrict__ y) {
+    __shared__ float red[ROW_THREADS];
+    const long m = blockIdx.x;
+    const int tid = threadIdx.x;
+    float p = 0.0f;
+    for (int c = tid; c < C; c += ROW_THREADS) { const float v = x[m * C + c]; p = p + v * v; }
+    const float inv = 1.0f / sqrtf(codec_block_sum(p, red, tid) / (float)C + eps);
+    for (int c = tid; c < C; c += ROW_THREADS) y[m * C + c] = (x[m * C + c] * inv) * w[c];
+}
+
+// depthwise causal conv k = 7 (w [7][C], + bias) then LayerNorm eps 1e-5, one workgroup per row; C <= 4096 (:156-160)
+__global__ __launch_bounds__(ROW_THREADS) void codec_dwln_kernel(const float* __restrict__ x, int C, int rate, const int* __restrict__ fstart,
+                                                                 const float* __restrict__ w, const float* __restrict__ b,
+                                                                 const float* __restrict__ lnw, const float* __restrict__ lnb,
+                                                                 float* __restrict__ y) {
+    __shared__ float red[ROW_THREADS];
+    __shared__ float val[4096];
+    const long m = blockIdx.x, start = (long)fstart[m / rate] * rate;
+    const int tid = threadIdx.x;
+    float p = 0.0f;
+    for (int c = tid; c < C; c += ROW_THREADS) {
+        float acc = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+            const long src = m - (6 - j);
+            if (src >= start) acc = acc + x[src * C + c] * w[j * C + c];
+        }
+        acc = acc + b[c];
+        val[c] = acc;
+        p = p + acc;
+    }
+    const float mu = codec_block_sum(p, red, tid) / (float)C;
+    float q = 0.0f;
+    for (int c = tid; c < C; c += ROW_THREADS) { const float d = val[c] - mu; q = q + d * d; }
+    const float inv = 1.0f / sqrtf(codec_block_sum(q, red, tid) / (float)C + 1e-5f);
+    for (int c = tid; c < C; c += ROW_THREADS) y[m * C + c] = ((val[c] - mu) * inv) * lnw[c] + lnb[c];
+}
+
+// qkv [M][3 A] (A = heads x 64), win[w] = (frames, first row), rope [35][32] (cos, sin); out [M][A].  grid (windows, heads).
+__global__ __launch_bounds__(ROW_THREADS) void codec_attn_kernel(const float* __restrict__ qkv, const int2* __restrict__ win,
+                                                                 const float2* __restrict__ rope, int heads, float* __restrict__ out) {
+    __shared__ float sq[CODEC_MAX_T][64], sk[CODEC_MAX_T][65], sv[CODEC_MAX_T][64], sp[CODEC_MAX_T][CODEC_MAX_T + 1];
+    const int tid = threadIdx.x, h = blockIdx.y, A = heads * 64;
+    const int T = min(win[blockIdx.x].x, CODEC_MAX_T);
+    const long off = win[blockIdx.x].y;
+    for (int i = tid; i < T * 32; i += ROW_THREADS) {                  // MLXNN.RoPE traditional: false: element d pairs with d + 32
+        const int t = i >> 5, d = i & 31;
+        const float* base = qkv + (off + t) * 3 * A + h * 64;
+        const float2 cs = rope[t * 32 + d];
+        const float q1 = base[d], q2 = base[d + 32], k1 = base[A + d], k2 = base[A + d + 32];
+        sq[t][d] = q1 * cs.x - q2 * cs.y; sq[t][d + 32] = q1 * cs.y + q2 * cs.x;
+        sk[t][d] = k1 * cs.x - k2 * cs.y; sk[t][d + 32] = k1 * cs.y + k2 * cs.x;
+    }
+    for (int i = tid; i < T * 64; i += ROW_THREADS) sv[i >> 6][i & 63] = qkv[(off + (i >> 6)) * 3 * A + 2 * A + h * 64 + (i & 63)];
+    __syncthreads();
+    for (int p = tid; p < T * T; p += ROW_THREADS) {                   // the additive -1e9 mask leaves exact zeros after the softmax
+        const int i = p / T, j = p - i * T;
+        if (j > i) continue;
+        float acc = 0.0f;
+#pragma unroll 8
+        for (int d = 0; d < 64; ++d) acc = fmaf(sq[i][d], sk[j][d], acc);
+        sp[i][j] = acc * 0.125f;
+    }
+    __syncthreads();
+    if (tid < T) {
+        const int i = tid;
+        float mx = sp[i][0];
+        for (int j = 1; j <= i; ++j) mx = fmaxf(mx, sp[i][j]);
+        float sum = 0.0f;
+        for (int j = 0; j <= i; ++j) { const float e = expf(sp[i][j] - mx); sp[i][j] = e; sum = sum + e; }
+        for (int j = 0; j <= i; ++j) sp[i][j] = sp[i][j] / sum;
+    }
+    __syncthreads();
+    for (int p = tid; p < T * 64; p += ROW_THREADS) {
+        const int i = p >> 6, d = p & 63;
+        float acc = 0.0f;
+        for (int j = 0; j <= i; ++j) acc = fmaf(sp[i][j], sv[j][d], acc);
+        out[(off + i) * A + h * 64 + d] = acc;
+    }
+}
+
+// wave[m] = clip(bias + sum_j sum_c snake(x[m - (6 - j)][c]) w[j][c]) (:683-685); x [M][C], one thread per sample
+__global__ __launch_bounds__(ROW_THREADS) void codec_out_kernel(const float* __restrict__ x, long M, int C, int rate, const int* __restrict__ fstart,
+                                                                const float* __restrict__ sa, const float* __restrict__ sb,
+                                                                const float* __restrict__ w, const float* __restrict__ b, int clip,
+                                                                float* __restrict__ wave) {
+    const long m = (long)blockIdx.x * ROW_THREADS + threadIdx.x;
+    if (m >= M) return;
+    const long start = (long)fstart[m / rate] * rate;
+    float acc = 0.0f;
+    for (int j = 0; j < 7; ++j) {
+        const long src = m - (6 - j);
+        if (src < start) continue;
+        for (int c = 0; c < C; ++c) acc = fmaf(codec_snake(x[src * C + c], sa[c], sb[c]), w[j * C + c], acc);
+    }
+    acc = acc + b[0];
+    if (clip) acc = fminf(fmaxf(acc, -1.0f), 1.0f);
+    wave[m] = acc;
+}
+
+// ---- weights ------------------------------------------------------------------------------------------------------------------------
+namespace {
+struct Builder {
+    std::vector<float> h;
+    const CheckedWeights& w;
+    explicit Builder(const CheckedWeights& cw) : w(cw) {}
+    const std::vector<float>& t(const std::string& k) const { return w.t.at(k); }
+    size_t take(size_t n) { const size_t at = h.size(); h.resize(at + ((n + 3) & ~(size_t)3), 0.0f); return at; }
+    size_t vec(const std::string& k) { const auto& v = t(k); const size_t at = take(v.size()); std::copy(v.begin(), v.end(), h.begin() + at); return at; }
+};
+}  // namespace
+
+CodecQwen3TTS::CodecQwen3TTS(int device, const CheckedWeights& cw, const CodecGeom& g, const std::vector<bool>& embed_stored,
+                             int max_windows, hipStream_t work)
+    : device_(device), g_(g), max_windows_(max_windows), spf_(g.samples_per_frame()) {
+    codec_check_geometry(g);
+    if (max_windows < 1 || max_windows > 512) throw std::invalid_argument("speech tokenizer decoder: max_windows in 1..512");
+    param_bytes_ = cw.disk_bytes;
+    Builder b(cw);
+    const int L = g.latent, H = g.hidden, Dd = g.decoder_dim, D = g.codebook_dim, A = g.heads * g.head_dim, I = 2 * H;
+    // Wt[j C_in + c][n] = W[n][c][j] of a conv [out][in][k] (k = 1: a Linear [out][in])
+    auto conv = [&](const std::string& key, int Cout, int Cin, int k, bool bias) {
+        Gemm gm; gm.K = k * Cin; gm.N = Cout; gm.Cin = Cin; gm.taps = k;
+        const auto& W = b.t(key + ".weight");
+        gm.wt = b.take((size_t)gm.K * gm.N);
+        for (int n = 0; n < Cout; ++n)
+            for (int c = 0; c < Cin; ++c)
+                for (int j = 0; j < k; ++j) b.h[gm.wt + ((size_t)j * Cin + c) * Cout + n] = W[((size_t)n * Cin + c) * k + j];
+        gm.has_bias = bias;
+        if (bias) gm.bias = b.vec(key + ".bias");
+        return gm;
+    };
+    // transposed conv [in][out][2 s] as two taps: tap 0 (x[t - 1]) holds W[:, :, ph + s], tap 1 (x[t]) holds W[:, :, ph]; n = ph C_out + co
+    auto tconv = [&](const std::string& key, int Cin, int Cout, int s) {
+        Gemm gm; gm.K = 2 * Cin; gm.N = s * Cout; gm.Cin = Cin; gm.taps = 2;
+        const auto& W = b.t(key + ".weight");
+        gm.wt = b.take((size_t)gm.K * gm.N);
+        for (int c = 0; c < Cin; ++c)
+            for (int co = 0; co < Cout; ++co)
+                for (int ph = 0; ph < s; ++ph) {
+                    const size_t src = ((size_t)c * Cout + co) * 2 * s;
+                    b.h[gm.wt + (size_t)c * gm.N + ph * Cout + co] = W[src + ph + s];
+                    b.h[gm.wt + ((size_t)Cin + c) * gm.N + ph * Cout + co] = W[src + ph];
+                }
+        gm.has_bias = true;
+        gm.bias = b.vec(key + ".bias");
+        return gm;
+    };
+    auto snake = [&](const std::string& key) {          // exp(alpha) | 1 / exp(beta), in f32 as the reference forms them
+        Snake s;
+        const auto &al = b.t(key + ".alpha"), &be = b.t(key + ".beta");
+        s.a = b.take(al.size()); s.b = b.take(be.size());
+        for (size_t i = 0; i < al.size(); ++i) { b.h[s.a + i] = expf(al[i]); b.h[s.b + i] = 1.0f / expf(be[i]); }
+        return s;
+    };
+    // codebooks (TTSWeightLoading.swift:280-301)
+    for (int q = 0; q < g.quantizers; ++q) {
+        const int n = q == 0 ? g.semantic_size : g.acoustic_size;
+        const std::string p = codec_codebook_prefix(q);
+        // codec_gather_kernel indexes all codebooks from cb_first_ as one array: take() pads to 4 floats, and codec_check_geometry
+        // requires size x dim to be a multiple of 4, so consecutive takes are contiguous
+        const size_t at = b.take((size_t)n * D);
+        if (q == 0) cb_first_ = at;
+        if (embed_stored[q]) std::copy(b.t(p + ".embed").begin(), b.t(p + ".embed").end(), b.h.begin() + at);
+        else {
+            const auto &sum = b.t(p + ".embedding_sum"), &use = b.t(p + ".cluster_usage");
+            for (int i = 0; i < n; ++i)
+                for (int d = 0; d < D; ++d) b.h[at + (size_t)i * D + d] = sum[(size_t)i * D + d] / std::max(use[i], 1e-7f);
+        }
+    }
+    {   // both output projections as one GEMM over [first | rest]
+        rvq_.K = 2 * D; rvq_.N = H; rvq_.Cin = 2 * D; rvq_.taps = 1;
+        rvq_.wt = b.take((size_t)2 * D * H);
+        const auto &w1 = b.t("decoder.quantizer.rvq_first.output_proj.weight"), &w2 = b.t("decoder.quantizer.rvq_rest.output_proj.weight");
+        for (int n = 0; n < H; ++n)
+            for (int c = 0; c < D; ++c) {
+                b.h[rvq_.wt + (size_t)c * H + n] = w1[(size_t)n * D + c];
+                b.h[rvq_.wt + ((size_t)D + c) * H + n] = w2[(size_t)n * D + c];
+            }
+    }
+    pre_conv_ = conv("decoder.pre_conv.conv", L, H, 3, true);
+    const std::string P = "decoder.pre_transformer.";
+    in_proj_ = conv(P + "input_proj", H, L, 1, true);
+    out_proj_ = conv(P + "output_proj", L, H, 1, true);
+    norm_ = b.vec(P + "norm.weight");
+    for (int l = 0; l < g.layers; ++l) {
+        const std::string p = P + "layers." + std::to_string(l) + ".";
+        Layer ly;
+        ly.n1 = b.vec(p + "input_layernorm.weight"); ly.n2 = b.vec(p + "post_attention_layernorm.weight");
+        ly.ls1 = b.vec(p + "self_attn_layer_scale.scale"); ly.ls2 = b.vec(p + "mlp_layer_scale.scale");
+        ly.qkv.K = H; ly.qkv.N = 3 * A; ly.qkv.Cin = H;
+        ly.qkv.wt = b.take((size_t)H * 3 * A);
+        int part = 0;
+        for (const char* k : {"q_proj", "k_proj", "v_proj"}) {
+            const auto& W = b.t(p + "self_attn." + k + ".weight");
+            for (int n = 0; n < A; ++n)
+                for (int c = 0; c < H; ++c) b.h[ly.qkv.wt + (size_t)c * 3 * A + part * A + n] = W[(size_t)n * H + c];
+            ++part;
+        }
+        ly.o = conv(p + "self_attn.o_proj", H, A, 1, false);
+        ly.gu.K = H; ly.gu.N = 2 * I; ly.gu.Cin = H;
+        ly.gu.wt = b.take((size_t)H * 2 * I);
+        const auto &Wg = b.t(p + "mlp.gate_proj.weight"), &Wu = b.t(p + "mlp.up_proj.weight");
+        for (int n = 0; n < I; ++n)
+            for (int c = 0; c < H; ++c) {
+                b.h[ly.gu.wt + (size_t)c * 2 * I + 2 * n] = Wg[(size_t)n * H + c];
+                b.h[ly.gu.wt + (size_t)c * 2 * I + 2 * n + 1] = Wu[(size_t)n * H + c];
+            }
+        ly.down = conv(p + "mlp.down_proj", H, I, 1, false);
+        layers_.push_back(ly);
+    }
+    for (int i = 0; i < 2; ++i) {
+        const std::string p = "decoder.upsample." + std::to_string(i) + ".";
+        Up& u = up_[i];
+        u.tconv = tconv(p + "0.conv", L, L, g.ratios[i]);
+        const auto& dw = b.t(p + "1.dwconv.conv.weight");                // [L][1][7] -> [7][L]
+        u.dw = b.take((size_t)7 * L);
+        for (int c = 0; c < L; ++c)
+            for (int j = 0; j < 7; ++j) b.h[u.dw + (size_t)j * L + c] = dw[(size_t)c * 7 + j];
+        u.dwb = b.vec(p + "1.dwconv.conv.bias");
+        u.lnw = b.vec(p + "1.norm.weight"); u.lnb = b.vec(p + "1.norm.bias");
+        u.pw1 = conv(p + "1.pwconv1", 4 * L, L, 1, true);
+        u.pw2 = conv(p + "1.pwconv2", L, 4 * L, 1, true);
+        u.gamma = b.vec(p + "1.gamma");
+    }
+    dec0_ = conv("decoder.decoder.0.conv", Dd, L, 7, true);
+    size_t big = std::max((size_t)g.ratios[0] * g.ratios[1] * 4 * L, (size_t)g.ratios[0] * g.ratios[1] * Dd);
+    int c = Dd, rate = g.ratios[0] * g.ratios[1];
+    for (int k = 0; k < 4; ++k) {
+        const std::string p = "decoder.decoder." + std::to_string(k + 1) + ".block.";
+        const int co = c / 2;
+        Block& bl = blocks_[k];
+        bl.s = snake(p + "0");
+        bl.tconv = tconv(p + "1.conv", c, co, g.rates[k]);
+        for (int j = 0; j < 3; ++j) {
+            const std::string u = p + std::to_string(j + 2) + ".";
+            bl.u[j].s1 = snake(u + "act1"); bl.u[j].s2 = snake(u + "act2");
+            bl.u[j].c1 = conv(u + "conv1.conv", co, co, 7, true);
+            bl.u[j].c2 = conv(u + "conv2.conv", co, co, 1, true);
+        }
+        c = co; rate *= g.rates[k];
+        big = std::max(big, (size_t)rate * c);
+    }
+    big_per_frame_ = big;
+    final_snake_ = snake("decoder.decoder.5");
+    {   // [1][C][7] -> [7][C]
+        const auto& W = b.t("decoder.decoder.6.conv.weight");
+        final_w_ = b.take((size_t)7 * c);
+        for (int ch = 0; ch < c; ++ch)
+            for (int j = 0; j < 7; ++j) b.h[final_w_ + (size_t)j * c + ch] = W[(size_t)ch * 7 + j];
+        final_b_ = b.vec("decoder.decoder.6.conv.bias");
+    }
+    rope_ = b.take((size_t)CODEC_MAX_T * 32 * 2);      // MLXNN.RoPE base 10000 over all 64 dimensions, positions 0..34
+    for (int t = 0; t < CODEC_MAX_T; ++t)
+        for (int d = 0; d < 32; ++d) {
+            const float inv = (float)pow(10000.0, -(double)d / 32.0), ang = (float)t * inv;
+            b.h[rope_ + ((size_t)t * 32 + d) * 2] = (float)cos((double)ang);
+            b.h[rope_ + ((size_t)t * 32 + d) * 2 + 1] = (float)sin((double)ang);
+        }
+    QASR_HIP(hipSetDevice(device_));
+    QASR_HIP(hipStreamCreateWithFlags(&own_, hipStreamNonBlocking));
+    work_ = work ? work : own_;
+    for (auto& e : ev_) QASR_HIP(hipEventCreate(&e));
+    d_w_.alloc(b.h.size() * sizeof(float));
+    QASR_HIP(hipMemcpy(d_w_.p, b.h.data(), b.h.size() * sizeof(float), hipMemcpyHostToDevice));
+}
+
+CodecQwen3TTS::~CodecQwen3TTS() {
+    if (work_) (void)hipStreamSynchronize(work_);
+    for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
+    if (own_) (void)hipStreamDestroy(own_);
+}
+
+void CodecQwen3TTS::unload() {
+    if (!loaded_) return;
+    QASR_HIP(hipSetDevice(device_));
+    QASR_HIP(hipStreamSynchronize(work_));
+    for (DevBuf* b : {&d_w_, &d_codes_, &d_fstart_, &d_win_, &d_emb_, &d_q_, &d_lat_[0], &d_lat_[1], &d_x_, &d_h_, &d_qkv_, &d_att_, &d_g_,
+                      &d_big_[0], &d_big_[1], &d_big_[2], &d_wave_})
+        b->release();
+    cap_small_ = cap_big_ = cap_win_ = 0;
+    loaded_ = false;
+}
+
+void CodecQwen3TTS::check_loaded() const {
+    if (!loaded_) throw NotLoaded("speech tokenizer decoder: model unloaded");
+}
+
+// ---- a pass -------------------------------------------------------------------------------------------------------------------------
+void CodecQwen3TTS::ensure(long M1, Mode mode) {
+    const size_t F = sizeof(float), A = (size_t)g_.heads * g_.head_dim;
+    // a capacity is recorded only once every buffer behind it exists: a failed allocation leaves it 0, so the next call allocates again
+    if (M1 > cap_small_) {
+        QASR_HIP(hipStreamSynchronize(work_));
+        cap_small_ = 0;
+        d_codes_.alloc(M1 * g_.quantizers * sizeof(int));
+        d_fstart_.alloc(M1 * sizeof(int));
+        d_emb_.alloc(M1 * 2 * g_.codebook_dim * F);
+        d_q_.alloc(M1 * g_.hidden * F);
+        d_lat_[0].alloc(M1 * g_.latent * F); d_lat_[1].alloc(M1 * g_.latent * F);
+        d_x_.alloc(M1 * g_.hidden * F); d_h_.alloc(M1 * g_.hidden * F);
+        d_qkv_.alloc(M1 * 3 * A * F); d_att_.alloc(M1 * A * F); d_g_.alloc(M1 * 2 * g_.hidden * F);
+        cap_small_ = M1;
+    }
+    if (mode == FULL && M1 > cap_big_) {
+        QASR_HIP(hipStreamSynchronize(work_));
+        cap_big_ = 0;
+        for (auto& b : d_big_) b.alloc((size_t)M1 * big_per_frame_ * F);
+        d_wave_.alloc((size_t)M1 * spf_ * F);
+        cap_big_ = M1;
+    }
+}
+
+// uploads the pass's tables: fstart[frame row] = its window's first row, win[w] = (frames, first row), codes [M1][Q]
+void CodecQwen3TTS::plan(const CodecWin* w, int n, bool with_codes) {
+    QASR_HIP(hipStreamSynchronize(work_));             // the tables are rewritten
+    long M1 = 0;
+    for (int i = 0; i < n; ++i) M1 += w[i].frames;
+    M1_ = M1; n_win_ = n;
+    std::vector<int> fstart((size_t)M1), win((size_t)2 * n);
+    const int Q = g_.quantizers;
+    if (with_codes) h_codes_.resize((size_t)M1 * Q);
+    long off = 0;
+    for (int i = 0; i < n; ++i) {
+        win[2 * i] = w[i].frames; win[2 * i + 1] = (int)off;
+        for (int t = 0; t < w[i].frames; ++t) {
+            fstart[off + t] = (int)off;
+            if (with_codes)
+                for (int q = 0; q < Q; ++q) h_codes_[(size_t)(off + t) * Q + q] = w[i].codes[(size_t)q * w[i].ld + w[i].start + t];
+        }
+        off += w[i].frames;
+    }
+    if (n > cap_win_) { cap_win_ = 0; d_win_.alloc((size_t)2 * n * sizeof(int)); cap_win_ = n; }
+    QASR_HIP(hipMemcpy(d_win_.p, win.data(), win.size() * sizeof(int), hipMemcpyHostToDevice));
+    QASR_HIP(hipMemcpy(d_fstart_.p, fstart.data(), fstart.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (with_codes) QASR_HIP(hipMemcpy(d_codes_.p, h_codes_.data(), h_codes_.size() * sizeof(int), hipMemcpyHostToDevice));
+}
+
+template <bool SNAKE, int EPI>
+void CodecQwen3TTS::gemm(const Gemm& gm, const float* A, long M, int dil, int rate, const Snake* sn, const float* ls, const float* R, float* C,
+                         int ldc, int bmod) {
+    const dim3 grid((unsigned)cdiv(M, CG_T), (unsigned)cdiv(gm.N, CG_T));
+    hipLaunchKernelGGL((codec_gemm_kernel<SNAKE, EPI>), grid, dim3(CG_THREADS), 0, work_, A, M, gm.Cin, gm.taps, dil, rate,
+                       d_fstart_.as<int>(), W(gm.wt), gm.K, gm.N, gm.has_bias ? W(gm.bias) : (const float*)nullptr, bmod,
+                       sn ? W(sn->a) : (const float*)nullptr, sn ? W(sn->b) : (const float*)nullptr, ls, R, C, ldc);
+}
+
+void CodecQwen3TTS::dev_rvq() {
+    hipLaunchKernelGGL(codec_gather_kernel, dim3((unsigned)M1_), dim3(ROW_THREADS), 0, work_, d_codes_.as<int>(), g_.quantizers,
+                       g_.codebook_dim, (long)g_.semantic_size, (long)g_.acoustic_size, W(cb_first_), d_emb_.as<float>());
+    gemm<false, E_LIN>(rvq_, d_emb_.as<float>(), M1_, 1, 1, nullptr, nullptr, nullptr, d_q_.as<float>(), g_.hidden, g_.hidden);
+    QASR_HIP(hipGetLastError());
+}
+
+// d_lat_[0] -> d_lat_[1]
+void CodecQwen3TTS::dev_pre_transformer() {
+    const int H = g_.hidden, L = g_.latent, A = g_.heads * g_.head_dim;
+    const long M = M1_;
+    float *x = d_x_.as<float>(), *h = d_h_.as<float>(), *qkv = d_qkv_.as<float>(), *att = d_att_.as<float>(), *gg = d_g_.as<float>();
+    gemm<false, E_LIN>(in_proj_, d_lat_[0].as<float>(), M, 1, 1, nullptr, nullptr, nullptr, x, H, H);
+    for (const Layer& ly : layers_) {
+        hipLaunchKernelGGL(codec_rms_kernel, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(ly.n1), g_.eps, h);
+        gemm<false, E_LIN>(ly.qkv, h, M, 1, 1, nullptr, nullptr, nullptr, qkv, 3 * A, 3 * A);
+        hipLaunchKernelGGL(codec_attn_kernel, dim3((unsigned)n_win_, (unsigned)g_.heads), dim3(ROW_THREADS), 0, work_, qkv,
+                           d_win_.as<int2>(), reinterpret_cast<const float2*>(W(rope_)), g_.heads, att);
+        gemm<false, E_LSRES>(ly.o, att, M, 1, 1, nullptr, W(ly.ls1), x, x, H, H);
+        hipLaunchKernelGGL(codec_rms_kernel, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(ly.n2), g_.eps, h);
+        gemm<false, E_SWIGLU>(ly.gu, h, M, 1, 1, nullptr, nullptr, nullptr, gg, 2 * H, 2 * H);
+        gemm<false, E_LSRES>(ly.down, gg, M, 1, 1, nullptr, W(ly.ls2), x, x, H, H);
+    }
+    hipLaunchKernelGGL(codec_rms_kernel, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(norm_), g_.eps, h);
+    gemm<false, E_LIN>(out_proj_, h, M, 1, 1, nullptr, nullptr, nullptr, d_lat_[1].as<float>(), L, L);
+    QASR_HIP(hipGetLastError());
+}
+
+// d_lat_[1] -> d_wave_; records ev_[2] .. ev_[8]
+void CodecQwen3TTS::dev_vocoder(bool clip) {
+    const int L = g_.latent;
+    float* buf[3] = {d_big_[0].as<float>(), d_big_[1].as<float>(), d_big_[2].as<float>()};
+    const float* x = d_lat_[1].as<float>();
+    int rate = 1;
+    for (int i = 0; i < 2; ++i) {                      // transposed conv, ConvNeXt (:669-672)
+        const Up& u = up_[i];
+        float *y = buf[i == 0 ? 0 : 1], *h = buf[i == 0 ? 1 : 0], *mid = buf[2];
+        gemm<false, E_LIN>(u.tconv, x, M1_ * rate, 1, rate, nullptr, nullptr, nullptr, y, u.tconv.N, L);
+        rate *= g_.ratios[i];
+        const long M = M1_ * rate;
+        hipLaunchKernelGGL(codec_dwln_kernel, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, y, L, rate, d_fstart_.as<int>(), W(u.dw),
+                           W(u.dwb), W(u.lnw), W(u.lnb), h);
+        gemm<false, E_GELU>(u.pw1, h, M, 1, rate, nullptr, nullptr, nullptr, mid, 4 * L, 4 * L);
+        gemm<false, E_LSRES>(u.pw2, mid, M, 1, rate, nullptr, W(u.gamma), y, y, L, L);
+        x = y;
+    }
+    QASR_HIP(hipEventRecord(ev_[3], work_));
+    // x is buf[1]
+    int cur = 1;
+    {
+        const int nxt = 0;
+        gemm<false, E_LIN>(dec0_, buf[cur], M1_ * rate, 1, rate, nullptr, nullptr, nullptr, buf[nxt], g_.decoder_dim, g_.decoder_dim);
+        cur = nxt;
+    }
+    int C = g_.decoder_dim;
+    for (int k = 0; k < 4; ++k) {                      // SnakeBeta, transposed conv, three residual units (:221-228)
+        const Block& bl = blocks_[k];
+        const int nxt = (cur + 1) % 3, tmp = (cur + 2) % 3, co = C / 2;
+        gemm<true, E_LIN>(bl.tconv, buf[cur], M1_ * rate, 1, rate, &bl.s, nullptr, nullptr, buf[nxt], bl.tconv.N, co);
+        rate *= g_.rates[k];
+        const long M = M1_ * rate;
+        const int dil[3] = {1, 3, 9};
+        for (int j = 0; j < 3; ++j) {
+            gemm<true, E_LIN>(bl.u[j].c1, buf[nxt], M, dil[j], rate, &bl.u[j].s1, nullptr, nullptr, buf[tmp], co, co);
+            gemm<true, E_RES>(bl.u[j].c2, buf[tmp], M, 1, rate, &bl.u[j].s2, nullptr, buf[nxt], buf[nxt], co, co);
+        }
+        cur = nxt; C = co;
+        QASR_HIP(hipEventRecord(ev_[4 + k], work_));
+    }
+    const long M = M1_ * rate;
+    hipLaunchKernelGGL(codec_out_kernel, dim3((unsigned)cdiv(M, ROW_THREADS)), dim3(ROW_THREADS), 0, work_, buf[cur], M, C, rate,
+                       d_fstart_.as<int>(), W(final_snake_.a), W(final_snake_.b), W(final_w_), W(final_b_), clip ? 1 : 0, d_wave_.as<float>());
+    QASR_HIP(hipEventRecord(ev_[8], work_));
+    QASR_HIP(hipGetLastError());
+}
+
+void CodecQwen3TTS::pass(const CodecWin* w, int n, Mode mode, bool clip, const float* xin, float* xout) {
+    QASR_HIP(hipSetDevice(device_));
+    long M1 = 0;
+    for (int i = 0; i < n; ++i) {
+        if (w[i].frames < 1 || w[i].frames > CODEC_MAX_T || w[i].context < 0 || w[i].context >= w[i].frames)
+            throw std::invalid_argument("speech tokenizer decoder: a window holds 1..35 frames");
+        M1 += w[i].frames;
+    }
+    ensure(M1, mode);
+    plan(w, n, mode != PT);
+    const size_t F = sizeof(float);
+    QASR_HIP(hipEventRecord(ev_[0], work_));
+    if (mode != PT) dev_rvq();
+    if (mode == RVQ) {
+        QASR_HIP(hipEventRecord(ev_[1], work_));
+        QASR_HIP(hipMemcpyAsync(xout, d_q_.p, (size_t)M1_ * g_.hidden * F, hipMemcpyDeviceToHost, work_));
+        QASR_HIP(hipStreamSynchronize(work_));
+        float ms = 0; QASR_HIP(hipEventElapsedTime(&ms, ev_[0], ev_[1])); timing_[0] += ms;
+        return;
+    }
+    if (mode == PT) QASR_HIP(hipMemcpyAsync(d_lat_[0].p, xin, (size_t)M1_ * g_.latent * F, hipMemcpyHostToDevice, work_));
+    else gemm<false, E_LIN>(pre_conv_, d_q_.as<float>(), M1_, 1, 1, nullptr, nullptr, nullptr, d_lat_[0].as<float>(), g_.latent, g_.latent);
+    QASR_HIP(hipEventRecord(ev_[1], work_));
+    dev_pre_transformer();
+    QASR_HIP(hipEventRecord(ev_[2], work_));
+    if (mode == PT) {
+        QASR_HIP(hipMemcpyAsync(xout, d_lat_[1].p, (size_t)M1_ * g_.latent * F, hipMemcpyDeviceToHost, work_));
+        QASR_HIP(hipStreamSynchronize(work_));
+        float ms = 0; QASR_HIP(hipEventElapsedTime(&ms, ev_[1], ev_[2])); timing_[1] += ms;
+        return;
+    }
+    dev_vocoder(clip);
+    for (int i = 0, off = 0; i < n; off += w[i].frames, ++i)
+        QASR_HIP(hipMemcpyAsync(w[i].out, d_wave_.as<float>() + (size_t)(off + w[i].context) * spf_,
+                                (size_t)(w[i].frames - w[i].context) * spf_ * F, hipMemcpyDeviceToHost, work_));
+    QASR_HIP(hipStreamSynchronize(work_));
+    QASR_HIP(hipGetLastError());
+    for (int s = 0; s < CODEC_STAGES; ++s) {
+        float ms = 0;
+        QASR_HIP(hipEventElapsedTime(&ms, ev_[s], ev_[s + 1]));
+        timing_[s] += ms;
+    }
+}
+
+// ---- entry points -------------------------------------------------------------------------------------------------------------------
+void CodecQwen3TTS::run(const std::vector<CodecWin>& wins, bool clip) {
+    check_loaded();
+    for (float& t : timing_) t = 0.0f;
+    for (size_t i = 0; i < wins.size(); i += (size_t)max_windows_)
+        pass(wins.data() + i, (int)std::min(wins.size() - i, (size_t)max_windows_), FULL, clip, nullptr, nullptr);
+}
+
+void CodecQwen3TTS::quantizer_decode(const int32_t* codes, int B, int T, float* out) {
+    check_loaded();
+    for (float& t : timing_) t = 0.0f;
+    for (int b0 = 0; b0 < B; b0 += max_windows_) {
+        const int n = std::min(B - b0, max_windows_);
+        std::vector<CodecWin> w;
+        for (int b = b0; b < b0 + n; ++b) w.push_back({codes + (size_t)b * g_.quantizers * T, T, 0, T, 0, nullptr});
+        pass(w.data(), n, RVQ, false, nullptr, out + (size_t)b0 * T * g_.hidden);
+    }
+}
+
+void CodecQwen3TTS::pre_transformer(const float* x, int B, int T, float* out) {
+    check_loaded();
+    for (float& t : timing_) t = 0.0f;
+    for (int b0 = 0; b0 < B; b0 += max_windows_) {
+        const int n = std::min(B - b0, max_windows_);
+        std::vector<CodecWin> w((size_t)n, CodecWin{nullptr, T, 0, T, 0, nullptr});
+        pass(w.data(), n, PT, false, x + (size_t)b0 * T * g_.latent, out + (size_t)b0 * T * g_.latent);
+    }
+}
+
+}  // namespace qasr

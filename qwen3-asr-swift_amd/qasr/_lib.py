@@ -273,6 +273,24 @@ SIGNATURES = {
     "qasr_sep_masks": (C.c_int, [_E, _F, _P(C.c_size_t), C.c_size_t, _F]),
     "qasr_sep_wiener": (C.c_int, [_E, _F, C.c_int, _F, _F, C.c_size_t, _P(QasrSepConfig), _F, _F]),
     "qasr_sep_istft": (C.c_int, [_E, _F, _F, C.c_int, C.c_size_t, C.c_size_t, _F]),
+    "qasr_codec_create": (C.c_int, [C.c_int, C.c_char_p, C.c_int, _E, _P(_E)]),
+    "qasr_codec_destroy": (None, [_E]),
+    "qasr_codec_last_error": (C.c_char_p, [_E]),
+    "qasr_codec_is_loaded": (C.c_int, [_E]),
+    "qasr_codec_unload": (C.c_int, [_E]),
+    "qasr_codec_memory_footprint": (C.c_size_t, [_E]),
+    "qasr_codec_sample_rate": (C.c_int, []),
+    "qasr_codec_samples_per_frame": (C.c_int, []),
+    "qasr_codec_num_quantizers": (C.c_int, [_E]),
+    "qasr_codec_hidden_size": (C.c_int, [_E]),
+    "qasr_codec_latent_dim": (C.c_int, [_E]),
+    "qasr_codec_forward": (C.c_int, [_E, _I, C.c_size_t, C.c_size_t, C.c_int, _F]),
+    "qasr_codec_window_positions": (C.c_int64, [C.c_size_t, _I, _I, _I, C.c_size_t]),
+    "qasr_codec_decode": (C.c_int, [_E, _I, C.c_size_t, _F]),
+    "qasr_codec_decode_batch": (C.c_int, [_E, _P(_I), _P(C.c_size_t), C.c_size_t, _P(_F)]),
+    "qasr_codec_quantizer_decode": (C.c_int, [_E, _I, C.c_size_t, C.c_size_t, _F]),
+    "qasr_codec_pre_transformer": (C.c_int, [_E, _F, C.c_size_t, C.c_size_t, _F]),
+    "qasr_codec_timing": (C.c_int, [_E, _F]),
     "qasr_transducer_default_config": (C.c_int, [C.c_char_p, _P(QasrTransducerConfig)]),
     "qasr_tdt_greedy_decode": (C.c_int, [_P(QasrTransducerConfig), _P(QasrTransducerCallbacks), C.c_int32, _I, _F, C.c_int32, _F]),
     "qasr_rnnt_greedy_decode": (C.c_int, [_P(QasrTransducerConfig), _P(QasrTransducerCallbacks), C.c_int32, C.c_int32, _I, _F, C.c_int32, _I]),

@@ -483,3 +483,115 @@ def write_openunmix_safetensors(sd: dict, model_dir: str, dtype: str = "F32", dr
         path = _write_safetensors(sd[stem], model_dir, dtype, drop if tweak else (), reshape if tweak else None)
         os.replace(path, os.path.join(model_dir, stem + ".safetensors"))
     return model_dir
+
+
+# ---- Qwen3-TTS speech tokenizer decoder (SpeechTokenizerDecoder.swift, Configuration.swift:128-148) -------------------------------
+CODEC_REAL = dict(latent_dim=1024, decoder_dim=1536, hidden_size=512, num_heads=16, head_dim=64, num_layers=8,
+                  upsample_rates=(8, 5, 4, 3), upsampling_ratios=(2, 2), num_quantizers=16, semantic_codebook_size=2048,
+                  acoustic_codebook_size=2048, codebook_dim=256, rms_norm_eps=1e-8)
+CODEC_REDUCED = dict(CODEC_REAL, latent_dim=96, decoder_dim=48, hidden_size=64, num_heads=2, num_layers=2, semantic_codebook_size=64,
+                     acoustic_codebook_size=64, codebook_dim=24)
+
+
+def speech_tokenizer_tensor_shapes(geometry=None) -> dict:
+    """key -> shape of every decoder tensor in the checkpoint's names and PyTorch layouts (TTSWeightLoading.swift:190-301, :347-381,
+    :458-480).  A codebook appears under its `embed` key; the loader also takes embedding_sum + cluster_usage in its place."""
+    g = geometry or CODEC_REAL
+    L, H, Dd, D, A = g["latent_dim"], g["hidden_size"], g["decoder_dim"], g["codebook_dim"], g["num_heads"] * g["head_dim"]
+    s = {}
+    for name, n, size in (("rvq_first", 1, g["semantic_codebook_size"]), ("rvq_rest", g["num_quantizers"] - 1, g["acoustic_codebook_size"])):
+        for i in range(n):
+            s[f"decoder.quantizer.{name}.vq.layers.{i}._codebook.embed"] = (size, D)
+        s[f"decoder.quantizer.{name}.output_proj.weight"] = (H, D, 1)
+    s["decoder.pre_conv.conv.weight"], s["decoder.pre_conv.conv.bias"] = (L, H, 3), (L,)
+    P = "decoder.pre_transformer."
+    s[P + "input_proj.weight"], s[P + "input_proj.bias"] = (H, L), (H,)
+    s[P + "output_proj.weight"], s[P + "output_proj.bias"] = (L, H), (L,)
+    s[P + "norm.weight"] = (H,)
+    for l in range(g["num_layers"]):
+        p = P + f"layers.{l}."
+        for k in ("q_proj", "k_proj", "v_proj"):
+            s[p + f"self_attn.{k}.weight"] = (A, H)
+        s[p + "self_attn.o_proj.weight"] = (H, A)
+        s[p + "input_layernorm.weight"] = s[p + "post_attention_layernorm.weight"] = (H,)
+        s[p + "mlp.gate_proj.weight"] = s[p + "mlp.up_proj.weight"] = (2 * H, H)
+        s[p + "mlp.down_proj.weight"] = (H, 2 * H)
+        s[p + "self_attn_layer_scale.scale"] = s[p + "mlp_layer_scale.scale"] = (H,)
+    for i, r in enumerate(g["upsampling_ratios"]):
+        p = f"decoder.upsample.{i}."
+        s[p + "0.conv.weight"], s[p + "0.conv.bias"] = (L, L, 2 * r), (L,)
+        s[p + "1.dwconv.conv.weight"], s[p + "1.dwconv.conv.bias"] = (L, 1, 7), (L,)
+        s[p + "1.norm.weight"] = s[p + "1.norm.bias"] = s[p + "1.gamma"] = s[p + "1.pwconv2.bias"] = (L,)
+        s[p + "1.pwconv1.weight"], s[p + "1.pwconv1.bias"] = (4 * L, L), (4 * L,)
+        s[p + "1.pwconv2.weight"] = (L, 4 * L)
+    s["decoder.decoder.0.conv.weight"], s["decoder.decoder.0.conv.bias"] = (Dd, L, 7), (Dd,)
+    c = Dd
+    for b, r in enumerate(g["upsample_rates"]):
+        p, co = f"decoder.decoder.{b + 1}.block.", c // 2
+        s[p + "0.alpha"] = s[p + "0.beta"] = (c,)
+        s[p + "1.conv.weight"], s[p + "1.conv.bias"] = (c, co, 2 * r), (co,)
+        for j in (2, 3, 4):
+            for a in ("act1", "act2"):
+                s[p + f"{j}.{a}.alpha"] = s[p + f"{j}.{a}.beta"] = (co,)
+            s[p + f"{j}.conv1.conv.weight"], s[p + f"{j}.conv2.conv.weight"] = (co, co, 7), (co, co, 1)
+            s[p + f"{j}.conv1.conv.bias"] = s[p + f"{j}.conv2.conv.bias"] = (co,)
+        c = co
+    s["decoder.decoder.5.alpha"] = s["decoder.decoder.5.beta"] = (c,)
+    s["decoder.decoder.6.conv.weight"], s["decoder.decoder.6.conv.bias"] = (1, c, 7), (1,)
+    return s
+
+
+def synth_speech_tokenizer_state_dict(seed: int = 0, geometry=None) -> dict:
+    """Seeded decoder weights {key: float32 array}, drawn so that a test can see every layer: layer scales around 0.5 (at the reference's
+    initial 0.01 a wrong attention hides under the tolerance), alpha and beta in [-0.5, 0.5], norm weights away from 1, fan-in scaled
+    matrices whose gains keep the signal O(1) through the residual chain and the pre-clip output inside (-1, 1)
+    (tests/test_codec_cpu.py asserts that).  Even codebooks are stored as `embed`, odd ones as embedding_sum + cluster_usage with
+    a few usages below the loader's 1e-7 clamp."""
+    g = geometry or CODEC_REAL
+    rng = np.random.default_rng(91001 + seed)
+    sd = {}
+    for key, shape in speech_tokenizer_tensor_shapes(g).items():
+        leaf = key.rsplit(".", 1)[-1]
+        if leaf == "embed":
+            e = rng.standard_normal(shape) * 0.5
+            q = int(key.split(".layers.")[1].split(".")[0]) + (0 if "rvq_first" in key else 1)
+            if q % 2 == 0:
+                sd[key] = e
+            else:
+                usage = 0.5 + 4.0 * rng.random(shape[0])
+                usage[rng.integers(0, shape[0], size=max(2, shape[0] // 16))] = 1e-9
+                usage[:2] = 0.0
+                sd[key[:-5] + "cluster_usage"] = usage
+                sd[key[:-5] + "embedding_sum"] = e * np.maximum(usage, 1e-7)[:, None]
+        elif leaf in ("alpha", "beta"):
+            sd[key] = rng.uniform(-0.5, 0.5, shape)
+        elif leaf in ("scale", "gamma"):
+            sd[key] = 0.5 + 0.1 * rng.standard_normal(shape)
+        elif leaf == "bias":
+            sd[key] = 0.05 * rng.standard_normal(shape)
+        elif len(shape) == 1:                                          # norm weights
+            sd[key] = 1.0 + 0.2 * rng.standard_normal(shape)
+        else:
+            if "dwconv" in key:
+                fan, gain = shape[2], 1.0
+            elif ".block.1.conv" in key or ".0.conv.weight" in key and "upsample" in key:
+                fan, gain = 2 * shape[0], 1.0                         # transposed conv: two taps of C_in reach an output
+            elif len(shape) == 3:
+                fan, gain = shape[1] * shape[2], (0.1 if "decoder.6" in key else 0.6 if ".conv1." in key or ".conv2." in key else 1.0)
+            else:
+                fan, gain = shape[1], 1.0
+            sd[key] = gain * rng.standard_normal(shape) / np.sqrt(fan)
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in sd.items()}
+
+
+def write_speech_tokenizer_safetensors(sd: dict, model_dir: str, geometry=None, dtype: str = "F32", drop=(), reshape=None) -> str:
+    """Writes `sd` as model_dir/model.safetensors and, for a geometry given, model_dir/config.json with it under "decoder_config".
+    `drop` / `reshape`: as write_silero_safetensors (the loader's error tests).  Returns model_dir."""
+    import json
+    import os
+    _write_safetensors(sd, model_dir, dtype, drop, reshape)
+    if geometry is not None:
+        cfg = {k: (list(v) if isinstance(v, tuple) else v) for k, v in geometry.items()}
+        with open(os.path.join(model_dir, "config.json"), "w") as f:
+            json.dump({"decoder_config": cfg}, f)
+    return model_dir
