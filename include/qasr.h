@@ -727,6 +727,51 @@ int qasr_codec_pre_transformer(qasr_codec* c, const float* x, size_t B, size_t T
  * (decoder.decoder.0 counted with block 1), output conv */
 int qasr_codec_timing(const qasr_codec* c, float* ms);
 
+/* ---- Qwen3-TTS 12.5 Hz speech tokenizer encoder (csrc/codec_enc_qwen3tts.hip, csrc/api_codec_enc.cpp) -------------------------------
+ * Reference: Sources/Qwen3TTS/SpeechTokenizerEncoder.swift.  24 kHz mono PCM -> 16 code streams at 12.5 Hz, the other direction of
+ * qasr_codec_*.  What each entry replaces:
+ *   TTSWeightLoader.loadSpeechTokenizerEncoderWeights (TTSWeightLoading+Encoder.swift:14-86), local directory -> qasr_codec_enc_create
+ *   SpeechTokenizerEncoder.callAsFunction (:223-241) and encode(samples:) (:246-249)                          -> qasr_codec_enc_encode / _encode_batch
+ *   callAsFunction up to postConv (:224-237)                                                                  -> qasr_codec_enc_conv
+ *   ... and EncoderTransformer.callAsFunction (:94-102)                                                       -> qasr_codec_enc_latent
+ *   EncoderRVQ.encode (:130-134) over ResidualVectorQuantizer.encode (SpeechTokenizerDecoder.swift:467-485)   -> qasr_codec_enc_quantize
+ * A clip of n >= 1 samples gives ceil(n / 1920) frames (every CausalConv1d pads on the left only; a stride-s conv gives ceil(T / s)
+ * rows).  Attention has no mask: every frame of a clip attends to every frame of that clip, so a clip is never chunked and one longer
+ * than max_samples is refused.  Both quantizers encode the same latent (:131-132).  Precision: f32 throughout.  A clip's rows and codes
+ * are bit-identical alone, in any batch and place, under any max_samples that holds it, and run to run.  One
+ * object, one thread at a time.  Not covered: the Talker, the code predictor, bf16 or quantised forms, streaming encode. */
+typedef struct qasr_codec_enc qasr_codec_enc;
+/* model_dir holds model.safetensors with the encoder.* keys in the PyTorch layouts (conv [out][in][k]); it may hold the decoder.* keys
+ * too, as the real checkpoint does.  encoder.quantizer.rvq_{first,rest}.input_proj.weight is [hidden_size][codebook_dim][1], the matrix
+ * ResidualVectorQuantizer.encode multiplies by; encoder.pre_transformer.output_proj must be present and is not applied (:100).
+ * Codebooks, geometry (config.json's "decoder_config"; the channel schedule is decoder_dim / 16, / 8, .. , decoder_dim), checks and
+ * statuses: as qasr_codec_create, the tensor named in qasr_codec_enc_last_error(NULL).  max_samples: samples one device pass holds
+ * (0 = 720000, 30 s; at most 2^24); every buffer is sized from it at create.  order_with: as for qasr_seg_create. */
+int qasr_codec_enc_create(int device, const char* model_dir, size_t max_samples, qasr_engine* order_with, qasr_codec_enc** out);
+void qasr_codec_enc_destroy(qasr_codec_enc* c);
+const char* qasr_codec_enc_last_error(const qasr_codec_enc* c);     /* c may be NULL: last create() failure */
+int qasr_codec_enc_is_loaded(const qasr_codec_enc* c);
+int qasr_codec_enc_unload(qasr_codec_enc* c);                       /* later device calls return QASR_ERR_NOT_LOADED */
+size_t qasr_codec_enc_memory_footprint(const qasr_codec_enc* c);    /* parameter bytes as stored, 0 unloaded */
+int qasr_codec_enc_num_quantizers(const qasr_codec_enc* c);         /* 16 (Configuration.swift:138) */
+int qasr_codec_enc_hidden_size(const qasr_codec_enc* c);            /* 512: row width of qasr_codec_enc_latent and _quantize */
+int qasr_codec_enc_latent_dim(const qasr_codec_enc* c);             /* 1024: row width of qasr_codec_enc_conv */
+size_t qasr_codec_enc_num_frames(size_t n);                         /* ceil(n / 1920), 0 for 0.  Pure CPU. */
+/* encode(samples:) (:246-249): pcm [n] -> codes [Q][frames].  n = 0, n > max_samples and a NULL buffer are QASR_ERR_INVALID. */
+int qasr_codec_enc_encode(qasr_codec_enc* c, const float* pcm, size_t n, int32_t* codes);
+/* B clips of any lengths, cut into passes of at most max_samples samples at clip boundaries: pcm[b] [n[b]] -> codes[b] [Q][frames] */
+int qasr_codec_enc_encode_batch(qasr_codec_enc* c, const float* const* pcm, const size_t* n, size_t B, int32_t* const* codes);
+/* stage entry points: out [frames][latent_dim] after post_conv (:237); out [frames][hidden_size] after the transformer's norm (:99) */
+int qasr_codec_enc_conv(qasr_codec_enc* c, const float* pcm, size_t n, float* out);
+int qasr_codec_enc_conv_batch(qasr_codec_enc* c, const float* const* pcm, const size_t* n, size_t B, float* const* out);
+int qasr_codec_enc_latent(qasr_codec_enc* c, const float* pcm, size_t n, float* out);
+int qasr_codec_enc_latent_batch(qasr_codec_enc* c, const float* const* pcm, const size_t* n, size_t B, float* const* out);
+/* EncoderRVQ.encode (:130-134) of caller-supplied rows: h [F][hidden_size] -> codes [Q][F]; frames are independent */
+int qasr_codec_enc_quantize(qasr_codec_enc* c, const float* h, size_t F, int32_t* codes);
+/* ms[8]: device time of the last call: input conv, encoder blocks 1..4, encoder.5 + the two downsampling stages + post_conv,
+ * pre-transformer, quantizer */
+int qasr_codec_enc_timing(const qasr_codec_enc* c, float* ms);
+
 /* transducer greedy loops (pure CPU).  The caller owns the networks and their state:
  *   decoder_step(ctx, token)  advance the prediction network with `token` (the loops prime it with the blank id where the reference does)
  *   joint(ctx, frame, token_logits[vocab_size + 1], duration_logits[n_durations] or NULL)  logits for encoder frame `frame` and the

@@ -17,7 +17,7 @@ using namespace qasr;
 static const char* const WHO = "speech tokenizer decoder";
 
 // model_dir/config.json's "decoder_config" (or the object itself when it carries the decoder's fields) over the reference's defaults
-static CodecGeom read_geometry(const std::string& dir) {
+CodecGeom qasr::codec_read_geometry(const std::string& dir, const char* WHO) {
     CodecGeom g;
     std::ifstream f(dir + "/config.json", std::ios::binary);
     if (!f) return g;
@@ -31,7 +31,7 @@ static CodecGeom read_geometry(const std::string& dir) {
     if (!d && root.get("upsample_rates") && root.get("latent_dim")) d = &root;
     if (!d) return g;
     if (d->type != Json::Obj) throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": config.json: decoder_config is not an object");
-    auto bad = [](const std::string& k) { throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": config.json: " + k); };
+    auto bad = [WHO](const std::string& k) { throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": config.json: " + k); };
     auto num = [&](const char* k, int* out) {
         const Json* v = d->get(k);
         if (!v) return;
@@ -98,7 +98,7 @@ int qasr_codec_create(int device, const char* model_dir, int max_windows, qasr_e
     CodecGeom g;
     std::vector<bool> embed_stored;
     try {                                              // geometry, every key, shape and dtype before any HIP call
-        g = read_geometry(model_dir);
+        g = codec_read_geometry(model_dir, WHO);
         try { codec_check_geometry(g); }
         catch (const std::exception& ex) { throw WeightLoadError(QASR_ERR_INVALID, ex.what()); }
         {   // which form each codebook is stored in (TTSWeightLoading.swift:286-300)

@@ -1,0 +1,847 @@
+// codec_enc_qwen3tts.hip -- the Qwen3-TTS speech tokenizer encoder for gfx950 (codec_enc_qwen3tts.h).  f32 throughout, accurate sinf /
+// expf / erff / sqrtf, no atomics, no vendor BLAS.
+//
+// A pass holds clips back to back.  A clip of n samples owns len[l] = ceil(n / rate[l]) rows of the tensors at level l (rates 1, 3, 12,
+// 60, 480, 960, 1920): the lengths are ceilings, not multiples of one another, so every level has its own table start[l][clip] of first
+// rows (start[l][clips] = the level's row count) and a kernel finds a row's clip by bisection.  Row and element indices are 64-bit.
+// Launches of a pass:
+//   cenc_in_kernel      the 1 -> C k = 7 conv as a 7-term dot, one thread per output element, 96-wide rows stored coalesced
+//   cenc_gemm_kernel    codec_gemm_kernel's 64 x 64 f32 tile and k order (taps outer, channels inner, one fmaf chain per output) with a
+//                       stride: the A element of (output row t of a clip, tap j, channel c) is x[t s - (taps - 1 - j) dilation][c] of
+//                       the same clip one level up, exact zero before the clip's first row, SnakeBeta optionally applied as it is
+//                       loaded; the same epilogues.  Runs every conv but the first, every Linear and the RVQ projections.
+//   cenc_rms_kernel, cenc_dwln_kernel   RMSNorm; depthwise k = 7 causal conv + LayerNorm; one workgroup per row
+//   cenc_attn_kernel    unmasked attention over a whole clip, flash-style: a workgroup owns 32 queries of one clip and one head, streams
+//                       the clip's K / V in tiles of 32 through LDS (RoPE on the way in, rotate-halves, positions from 0) with a running
+//                       max and sum
+//   cenc_vq_kernel      ResidualVectorQuantizer.encode: a workgroup owns 64 frames of one quantizer and walks its codebooks in order;
+//                       per codebook the [64][size] score GEMM in the same tile, the distance in the reference's expanded form, a
+//                       (value, index) argmin, then the residual update in place
+// Summation order: every GEMM output is one thread's fmaf chain over k = 0..K-1; the norms as in the decoder; an
+// attention output row is accumulated over the clip's keys in order, tile after tile from the clip's first frame.  No reduction crosses a
+// clip and nothing depends on a clip's place, so a clip's latent and codes are the same bits alone, in any batch and under any split
+// into passes.
+#include "codec_enc_qwen3tts.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+namespace qasr {
+
+// ---- geometry, keys, lengths (host) -------------------------------------------------------------------------------------------------
+void codec_enc_check_geometry(const CodecGeom& g) {
+    try { codec_check_geometry(g); }
+    catch (const std::invalid_argument& ex) {
+        std::string m = ex.what();
+        const std::string from = "speech tokenizer decoder";
+        if (m.compare(0, from.size(), from) == 0) m = "speech tokenizer encoder" + m.substr(from.size());
+        throw std::invalid_argument(m);
+    }
+}
+
+std::string codec_enc_codebook_prefix(int q) {
+    return q == 0 ? std::string("encoder.quantizer.rvq_first.vq.layers.0._codebook")
+                  : "encoder.quantizer.rvq_rest.vq.layers." + std::to_string(q - 1) + "._codebook";
+}
+
+void codec_enc_strides(const CodecGeom& g, int s[6]) {
+    for (int i = 0; i < 4; ++i) s[i] = g.rates[3 - i];
+    s[4] = g.ratios[1]; s[5] = g.ratios[0];
+}
+
+void codec_enc_lengths(const CodecGeom& g, long n, long len[CENC_LEVELS]) {
+    int s[6];
+    codec_enc_strides(g, s);
+    len[0] = n;
+    for (int l = 0; l < 6; ++l) len[l + 1] = (len[l] + s[l] - 1) / s[l];
+}
+
+std::vector<std::pair<std::string, std::vector<int64_t>>> codec_enc_tensor_shapes(const CodecGeom& g, const std::vector<bool>& embed_stored) {
+    std::vector<std::pair<std::string, std::vector<int64_t>>> s;
+    auto add = [&](const std::string& k, std::vector<int64_t> sh) { s.emplace_back(k, std::move(sh)); };
+    const int64_t L = g.latent, H = g.hidden, Dd = g.decoder_dim, D = g.codebook_dim, A = (int64_t)g.heads * g.head_dim;
+    int st[6];
+    codec_enc_strides(g, st);
+    for (int q = 0; q < g.quantizers; ++q) {
+        const int64_t n = q == 0 ? g.semantic_size : g.acoustic_size;
+        const std::string p = codec_enc_codebook_prefix(q);
+        if (embed_stored[q]) add(p + ".embed", {n, D});
+        else { add(p + ".embedding_sum", {n, D}); add(p + ".cluster_usage", {n}); }
+    }
+    // the [hidden][codebook_dim] matrix ResidualVectorQuantizer.encode multiplies by (:472-475), stored as the module holds it
+    add("encoder.quantizer.rvq_first.input_proj.weight", {H, D, 1});
+    add("encoder.quantizer.rvq_rest.input_proj.weight", {H, D, 1});
+    int64_t c = Dd / 16;
+    add("encoder.encoder.0.conv.weight", {c, 1, 7}); add("encoder.encoder.0.conv.bias", {c});
+    for (int b = 0; b < 4; ++b) {
+        const std::string p = "encoder.encoder." + std::to_string(b + 1) + ".block.";
+        for (int j = 0; j < 3; ++j) {
+            const std::string u = p + std::to_string(j) + ".";
+            for (const char* a : {"act1", "act2"}) { add(u + a + ".alpha", {c}); add(u + a + ".beta", {c}); }
+            add(u + "conv1.conv.weight", {c, c, 7}); add(u + "conv1.conv.bias", {c});
+            add(u + "conv2.conv.weight", {c, c, 1}); add(u + "conv2.conv.bias", {c});
+        }
+        add(p + "3.alpha", {c}); add(p + "3.beta", {c});
+        add(p + "4.conv.weight", {2 * c, c, 2 * st[b]}); add(p + "4.conv.bias", {2 * c});
+        c *= 2;
+    }
+    add("encoder.encoder.5.conv.weight", {L, Dd, 7}); add("encoder.encoder.5.conv.bias", {L});
+    for (int i = 0; i < 2; ++i) {
+        const std::string p = "encoder.downsample." + std::to_string(i) + ".";
+        add(p + "0.dwconv.conv.weight", {L, 1, 7}); add(p + "0.dwconv.conv.bias", {L});
+        add(p + "0.norm.weight", {L}); add(p + "0.norm.bias", {L});
+        add(p + "0.pwconv1.weight", {4 * L, L}); add(p + "0.pwconv1.bias", {4 * L});
+        add(p + "0.pwconv2.weight", {L, 4 * L}); add(p + "0.pwconv2.bias", {L});
+        add(p + "0.gamma", {L});
+        add(p + "1.conv.weight", {L, L, 2 * st[4 + i]}); add(p + "1.conv.bias", {L});
+    }
+    add("encoder.post_conv.conv.weight", {L, L, 3}); add("encoder.post_conv.conv.bias", {L});
+    const std::string P = "encoder.pre_transformer.";
+    add(P + "input_proj.weight", {H, L}); add(P + "input_proj.bias", {H});
+    add(P + "output_proj.weight", {L, H}); add(P + "output_proj.bias", {L});      // read by the reference's loader, never applied (:100)
+    add(P + "norm.weight", {H});
+    for (int l = 0; l < g.layers; ++l) {
+        const std::string p = P + "layers." + std::to_string(l) + ".";
+        for (const char* k : {"q_proj", "k_proj", "v_proj"}) add(p + "self_attn." + k + ".weight", {A, H});
+        add(p + "self_attn.o_proj.weight", {H, A});
+        add(p + "input_layernorm.weight", {H}); add(p + "post_attention_layernorm.weight", {H});
+        add(p + "mlp.gate_proj.weight", {2 * H, H}); add(p + "mlp.up_proj.weight", {2 * H, H}); add(p + "mlp.down_proj.weight", {H, 2 * H});
+        add(p + "self_attn_layer_scale.scale", {H}); add(p + "mlp_layer_scale.scale", {H});
+    }
+    return s;
+}
+
+// ---- kernels ------------------------------------------------------------------------------------------------------------------------
+constexpr int CG_THREADS = 256, CG_T = 64, CG_K = 16, ROW_THREADS = 256, AT_Q = 32, AT_K = 32;
+enum { E_LIN = 0, E_GELU = 1, E_RES = 2, E_LSRES = 3, E_SWIGLU = 4 };
+
+// x + (1 / exp(beta)) sin^2(exp(alpha) x) with a = exp(alpha), b = 1 / exp(beta) formed at load (SpeechTokenizerDecoder.swift:105-110)
+__device__ __forceinline__ float cenc_snake(float x, float a, float b) {
+    const float s = sinf(a * x);
+    return x + b * (s * s);
+}
+
+// the clip that owns row m: start[0] = 0 < start[1] < .. < start[n] = rows, every clip holds at least one row
+__device__ __forceinline__ int cenc_clip_of(const int* __restrict__ start, int n, long m) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((long)start[mid] <= m) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// sum over the workgroup's 256 values in a fixed tree; every thread gets it.  Ends with a barrier that also frees `red`.
+__device__ __forceinline__ float cenc_block_sum(float v, float* red, int tid) {
+    red[tid] = v;
+    __syncthreads();
+    for (int s = ROW_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) red[tid] = red[tid] + red[tid + s];
+        __syncthreads();
+    }
+    const float r = red[0];
+    __syncthreads();
+    return r;
+}
+
+// y[m][c] = b[c] + sum_j w[j][c] x[m - (6 - j)] inside the clip (:224); x [M], w [7][C], y [M][C]; one thread per (m, c)
+__global__ __launch_bounds__(ROW_THREADS) void cenc_in_kernel(const float* __restrict__ x, long M, int C, const int* __restrict__ start,
+                                                              int nclips, const float* __restrict__ w, const float* __restrict__ b,
+                                                              float* __restrict__ y) {
+    const long e = (long)blockIdx.x * ROW_THREADS + threadIdx.x;
+    if (e >= M * C) return;
+    const long m = e / C;
+    const int c = (int)(e - m * C);
+    const long first = start[cenc_clip_of(start, nclips, m)];
+    float acc = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+        const long src = m - (6 - j);
+        acc = fmaf(src >= first ? x[src] : 0.0f, w[j * C + c], acc);
+    }
+    y[e] = acc + b[c];
+}
+
+// C = epilogue(sum_k A(m, k) Wt[k][n]), k = j C_in + c <-> x[first_in + (m - first_out) stride - (taps - 1 - j) dil][c], zero before
+// first_in.  A [rows of the input level][C_in], Wt [K][N]; ostart / istart: the first rows of the clips at the output / input level
+// (nullptr: rows are independent, taps = 1).  E_SWIGLU: columns 2 i, 2 i + 1 are gate i, up i; C [M][N / 2].
+template <bool SNAKE, int EPI>
+__global__ __launch_bounds__(CG_THREADS) void cenc_gemm_kernel(const float* __restrict__ A, long M, int Cin, int taps, int dil, int stride,
+                                                               const int* __restrict__ ostart, const int* __restrict__ istart, int nclips,
+                                                               const float* __restrict__ Wt, int K, int N, const float* __restrict__ bias,
+                                                               const float* __restrict__ sa, const float* __restrict__ sb,
+                                                               const float* __restrict__ ls, const float* R, float* C, int ldc) {
+    __shared__ __attribute__((aligned(16))) float As[CG_K][CG_T + 4];
+    __shared__ __attribute__((aligned(16))) float Bs[CG_K][CG_T];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const long m0 = (long)blockIdx.x * CG_T;
+    const int n0 = blockIdx.y * CG_T;
+    long base[4], first[4];                            // input row of the last tap, and the clip's first input row, per A row loaded
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const long m = m0 + ((tid + r * CG_THREADS) >> 4);
+        base[r] = m; first[r] = 0;
+        if (ostart && m < M) {
+            const int clip = cenc_clip_of(ostart, nclips, m);
+            first[r] = istart[clip];
+            base[r] = first[r] + (m - ostart[clip]) * stride;
+        }
+    }
+    float acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[i][q] = 0.0f;
+    for (int k0 = 0; k0 < K; k0 += CG_K) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int idx = tid + r * CG_THREADS, row = idx >> 4, kk = idx & 15, k = k0 + kk;
+            float v = 0.0f;                            // rows past M, inputs past K and rows before the clip add exact zeros
+            if (m0 + row < M && k < K) {
+                const int j = k / Cin, c = k - j * Cin;
+                const long src = base[r] - (long)(taps - 1 - j) * dil;
+                if (src >= first[r]) {
+                    v = A[src * Cin + c];
+                    if (SNAKE) v = cenc_snake(v, sa[c], sb[c]);
+                }
+            }
+            As[kk][row] = v;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int idx = tid + r * CG_THREADS, kk = idx >> 6, col = idx & 63, k = k0 + kk, n = n0 + col;
+            Bs[kk][col] = (k < K && n < N) ? Wt[(size_t)k * N + n] : 0.0f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < CG_K; ++kk) {
+            const float4 a = lds_read_f4(&As[kk][ty * 4]);
+            const float4 bq = lds_read_f4(&Bs[kk][tx * 4]);
+            const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {bq.x, bq.y, bq.z, bq.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc[i][q] = fmaf(av[i], bv[q], acc[i][q]);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const long m = m0 + ty * 4 + i;
+        if (m >= M) continue;
+        if (EPI == E_SWIGLU) {                         // silu(gate) * up (SpeechTokenizerDecoder.swift:340)
+#pragma unroll
+            for (int q = 0; q < 4; q += 2) {
+                const int n = n0 + tx * 4 + q;
+                if (n + 1 >= N) continue;
+                const float g = acc[i][q];
+                C[m * ldc + (n >> 1)] = (g / (1.0f + expf(-g))) * acc[i][q + 1];
+            }
+            continue;
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int n = n0 + tx * 4 + q;
+            if (n >= N) continue;
+            float v = acc[i][q];
+            if (bias) v = v + bias[n];
+            if (EPI == E_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+            if (EPI == E_RES) v = v + R[m * ldc + n];
+            if (EPI == E_LSRES) v = v * ls[n] + R[m * ldc + n];
+            C[m * ldc + n] = v;
+        }
+    }
+}
+
+// y = x / sqrt(mean(x^2) + eps) * w, one workgroup per row
+__global__ __launch_bounds__(ROW_THREADS) void cenc_rms_kernel(const float* __restrict__ x, int C, const float* __restrict__ w, float eps,
+                                                               float* __restrict__ y) {
+    __shared__ float red[ROW_THREADS];
+    const long m = blockIdx.x;
+    const int tid = threadIdx.x;
+    float p = 0.0f;
+    for (int c = tid; c < C; c += ROW_THREADS) { const float v = x[m * C + c]; p = p + v * v; }
+    const float inv = 1.0f / sqrtf(cenc_block_sum(p, red, tid) / (float)C + eps);
+    for (int c = tid; c < C; c += ROW_THREADS) y[m * C + c] = (x[m * C + c] * inv) * w[c];
+}
+
+// depthwise causal conv k = 7 (w [7][C], + bias) then LayerNorm eps 1e-5, one workgroup per row; C <= 4096 (:156-160 of the decoder)
+__global__ __launch_bounds__(ROW_THREADS) void cenc_dwln_kernel(const float* __restrict__ x, int C, const int* __restrict__ start, int nclips,
+                                                                const float* __restrict__ w, const float* __restrict__ b,
+                                                                const float* __restrict__ lnw, const float* __restrict__ lnb,
+                                                                float* __restrict__ y) {
+    __shared__ float red[ROW_THREADS];
+    __shared__ float val[4096];
+    const long m = blockIdx.x, first = start[cenc_clip_of(start, nclips, m)];
+    const int tid = threadIdx.x;
+    float p = 0.0f;
+    for (int c = tid; c < C; c += ROW_THREADS) {
+        float acc = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+            const long src = m - (6 - j);
+            if (src >= first) acc = acc + x[src * C + c] * w[j * C + c];
+        }
+        acc = acc + b[c];
+        val[c] = acc;
+        p = p + acc;
+    }
+    const float mu = cenc_block_sum(p, red, tid) / (float)C;
+    float q = 0.0f;
+    for (int c = tid; c < C; c += ROW_THREADS) { const float d = val[c] - mu; q = q + d * d; }
+    const float inv = 1.0f / sqrtf(cenc_block_sum(q, red, tid) / (float)C + 1e-5f);
+    for (int c = tid; c < C; c += ROW_THREADS) y[m * C + c] = ((val[c] - mu) * inv) * lnw[c] + lnb[c];
+}
+
+// qkv [M][3 A] (A = heads x 64); tiles[b] = (the clip's first row, its frames, the tile's first query); rope [positions][32] (cos, sin);
+// out [M][A].  grid (query tiles, heads).  Thread (i = tid / 8, g = tid % 8) owns outputs 8 g .. 8 g + 7 of query i: per K / V tile the
+// 32 x 32 scores go through LDS, then the row's running max m, sum l and accumulators are updated over the tile's keys in order (the
+// eight threads of a row compute the same m and l).  Keys past the clip's last frame are never read.
+__global__ __launch_bounds__(ROW_THREADS) void cenc_attn_kernel(const float* __restrict__ qkv, const int4* __restrict__ tiles,
+                                                                const float2* __restrict__ rope, int heads, float* __restrict__ out) {
+    __shared__ float sq[AT_Q][64], sk[AT_K][65], sv[AT_K][64], sp[AT_Q][AT_K + 1];
+    const int tid = threadIdx.x, h = blockIdx.y, A = heads * 64;
+    const int4 tile = tiles[blockIdx.x];
+    const long row0 = tile.x;
+    const int F = tile.y, q0 = tile.z, nq = min(AT_Q, F - q0);
+    for (int i = tid; i < AT_Q * 32; i += ROW_THREADS) {               // MLXNN.RoPE traditional: false: element d pairs with d + 32
+        const int t = i >> 5, d = i & 31;
+        float a = 0.0f, b = 0.0f;
+        if (t < nq) {
+            const float* base = qkv + (row0 + q0 + t) * 3 * A + h * 64;
+            const float2 cs = rope[(q0 + t) * 32 + d];
+            const float q1 = base[d], q2 = base[d + 32];
+            a = q1 * cs.x - q2 * cs.y; b = q1 * cs.y + q2 * cs.x;
+        }
+        sq[t][d] = a; sq[t][d + 32] = b;
+    }
+    const int qi = tid >> 3, dg = (tid & 7) * 8;
+    float mx = -INFINITY, sum = 0.0f, acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.0f;
+    for (int k0 = 0; k0 < F; k0 += AT_K) {
+        const int nk = min(AT_K, F - k0);
+        __syncthreads();                                               // the previous tile is consumed (and sq is written)
+        for (int i = tid; i < nk * 32; i += ROW_THREADS) {
+            const int t = i >> 5, d = i & 31;
+            const float* base = qkv + (row0 + k0 + t) * 3 * A + A + h * 64;
+            const float2 cs = rope[(k0 + t) * 32 + d];
+            const float k1 = base[d], k2 = base[d + 32];
+            sk[t][d] = k1 * cs.x - k2 * cs.y; sk[t][d + 32] = k1 * cs.y + k2 * cs.x;
+        }
+        for (int i = tid; i < nk * 64; i += ROW_THREADS) sv[i >> 6][i & 63] = qkv[(row0 + k0 + (i >> 6)) * 3 * A + 2 * A + h * 64 + (i & 63)];
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < AT_K / 8; ++r) {
+            const int j = (tid & 7) + 8 * r;
+            if (j >= nk) continue;
+            float s = 0.0f;
+#pragma unroll 8
+            for (int d = 0; d < 64; ++d) s = fmaf(sq[qi][d], sk[j][d], s);
+            sp[qi][j] = s * 0.125f;
+        }
+        __syncthreads();
+        float tmax = sp[qi][0];
+        for (int j = 1; j < nk; ++j) tmax = fmaxf(tmax, sp[qi][j]);
+        const float nmx = fmaxf(mx, tmax), scale = expf(mx - nmx);     // first tile: exp(-inf) = 0 on zero accumulators
+        sum = sum * scale;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] = acc[e] * scale;
+        for (int j = 0; j < nk; ++j) {
+            const float p = expf(sp[qi][j] - nmx);
+            sum = sum + p;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] = fmaf(p, sv[j][dg + e], acc[e]);
+        }
+        mx = nmx;
+    }
+    if (qi < nq) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) out[(row0 + q0 + qi) * A + h * 64 + dg + e] = acc[e] / sum;
+    }
+}
+
+// ResidualVectorQuantizer.encode (:467-485) after the projection.  r [M][ldr]: the residual of chain 0 (rvq_first, 1 codebook) in
+// columns 0 .. D - 1, of chain 1 (rvq_rest, Q - 1 codebooks) in columns D .. 2 D - 1.  cb [stage][S][D], cbt [stage][D][S], csq
+// [stage][S] = |c|^2.  Per stage: code = argmin_n (|r|^2 - 2 r.c_n) + |c_n|^2 (:417-423), the lowest n among equal values, then
+// r -= cb[code].  codes [M][Q].  grid (frame tiles of 64, 2); a workgroup reads and writes only its own rows of r.
+__global__ __launch_bounds__(CG_THREADS) void cenc_vq_kernel(float* r, long M, int ldr, int D, int Q, const float* __restrict__ cb0,
+                                                             const float* __restrict__ cbt0, const float* __restrict__ csq0, int S0,
+                                                             const float* __restrict__ cb1, const float* __restrict__ cbt1,
+                                                             const float* __restrict__ csq1, int S1, int* __restrict__ codes) {
+    __shared__ __attribute__((aligned(16))) float As[CG_K][CG_T + 4];
+    __shared__ __attribute__((aligned(16))) float Bs[CG_K][CG_T];
+    __shared__ float rv[CG_T][17], part[CG_T][4], xsq[CG_T];
+    __shared__ int ri[CG_T][17], best[CG_T];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4, chain = blockIdx.y;
+    const long m0 = (long)blockIdx.x * CG_T;
+    const int stages = chain ? Q - 1 : 1, S = chain ? S1 : S0, col = chain ? D : 0;
+    for (int st = 0; st < stages; ++st) {
+        const float* cb = (chain ? cb1 : cb0) + (size_t)st * S * D;
+        const float* cbt = (chain ? cbt1 : cbt0) + (size_t)st * S * D;
+        const float* csq = (chain ? csq1 : csq0) + (size_t)st * S;
+        {   // |r|^2 per frame: four strided partials, then ((p0 + p1) + (p2 + p3))
+            const int f = tid >> 2, pt = tid & 3;
+            float p = 0.0f;
+            if (m0 + f < M)
+                for (int d = pt; d < D; d += 4) { const float v = r[(m0 + f) * ldr + col + d]; p = fmaf(v, v, p); }
+            part[f][pt] = p;
+            __syncthreads();
+            if (tid < CG_T) xsq[tid] = (part[tid][0] + part[tid][1]) + (part[tid][2] + part[tid][3]);
+        }
+        float bv[4];
+        int bi[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { bv[i] = INFINITY; bi[i] = 0; }
+        for (int n0 = 0; n0 < S; n0 += CG_T) {
+            float acc[4][4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc[i][q] = 0.0f;
+            for (int k0 = 0; k0 < D; k0 += CG_K) {
+                __syncthreads();                                       // the previous step's tiles are consumed; xsq is written
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) {
+                    const int idx = tid + rr * CG_THREADS, row = idx >> 4, kk = idx & 15, k = k0 + kk;
+                    As[kk][row] = (m0 + row < M && k < D) ? r[(m0 + row) * ldr + col + k] : 0.0f;
+                }
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) {
+                    const int idx = tid + rr * CG_THREADS, kk = idx >> 6, c = idx & 63, k = k0 + kk, n = n0 + c;
+                    Bs[kk][c] = (k < D && n < S) ? cbt[(size_t)k * S + n] : 0.0f;
+                }
+                __syncthreads();
+#pragma unroll
+                for (int kk = 0; kk < CG_K; ++kk) {
+                    const float4 a = lds_read_f4(&As[kk][ty * 4]);
+                    const float4 bq = lds_read_f4(&Bs[kk][tx * 4]);
+                    const float av[4] = {a.x, a.y, a.z, a.w}, bw[4] = {bq.x, bq.y, bq.z, bq.w};
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) acc[i][q] = fmaf(av[i], bw[q], acc[i][q]);
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {                              // ascending n: a thread keeps the lowest index among equals
+                const int n = n0 + tx * 4 + q;
+                if (n >= S) continue;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float v = (xsq[ty * 4 + i] - 2.0f * acc[i][q]) + csq[n];
+                    if (v < bv[i]) { bv[i] = v; bi[i] = n; }
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { rv[ty * 4 + i][tx] = bv[i]; ri[ty * 4 + i][tx] = bi[i]; }
+        __syncthreads();
+        if (tid < CG_T) {                                              // (value, index) pairs: the smaller value, then the smaller index
+            float v = rv[tid][0];
+            int n = ri[tid][0];
+            for (int t = 1; t < 16; ++t) {
+                const float v2 = rv[tid][t];
+                const int n2 = ri[tid][t];
+                if (v2 < v || (v2 == v && n2 < n)) { v = v2; n = n2; }
+            }
+            best[tid] = n;
+            if (m0 + tid < M) codes[(m0 + tid) * Q + chain + st] = n;
+        }
+        __syncthreads();
+        for (int idx = tid; idx < CG_T * D; idx += CG_THREADS) {
+            const int f = idx / D, d = idx - f * D;
+            if (m0 + f < M) r[(m0 + f) * ldr + col + d] = r[(m0 + f) * ldr + col + d] - cb[(size_t)best[f] * D + d];
+        }
+        __threadfence_block();
+        __syncthreads();
+    }
+}
+
+// ---- weights ------------------------------------------------------------------------------------------------------------------------
+namespace {
+struct Builder {
+    std::vector<float> h;
+    const CheckedWeights& w;
+    explicit Builder(const CheckedWeights& cw) : w(cw) {}
+    const std::vector<float>& t(const std::string& k) const { return w.t.at(k); }
+    size_t take(size_t n) { const size_t at = h.size(); h.resize(at + ((n + 3) & ~(size_t)3), 0.0f); return at; }
+    size_t vec(const std::string& k) { const auto& v = t(k); const size_t at = take(v.size()); std::copy(v.begin(), v.end(), h.begin() + at); return at; }
+};
+}  // namespace
+
+CodecEncQwen3TTS::CodecEncQwen3TTS(int device, const CheckedWeights& cw, const CodecGeom& g, const std::vector<bool>& embed_stored,
+                                   long max_samples, hipStream_t work)
+    : device_(device), g_(g), max_samples_(max_samples) {
+    codec_enc_check_geometry(g);
+    if (max_samples < 1 || max_samples > CENC_MAX_SAMPLES) throw std::invalid_argument("speech tokenizer encoder: max_samples in 1..2^24");
+    param_bytes_ = cw.disk_bytes;
+    Builder b(cw);
+    const int L = g.latent, H = g.hidden, Dd = g.decoder_dim, D = g.codebook_dim, A = g.heads * g.head_dim, I = 2 * H, Q = g.quantizers;
+    codec_enc_strides(g, stride_);
+    // Wt[j C_in + c][n] = W[n][c][j] of a conv [out][in][k] (k = 1: a Linear [out][in])
+    auto conv = [&](const std::string& key, int Cout, int Cin, int k, bool bias) {
+        Gemm gm; gm.K = k * Cin; gm.N = Cout; gm.Cin = Cin; gm.taps = k;
+        const auto& W = b.t(key + ".weight");
+        gm.wt = b.take((size_t)gm.K * gm.N);
+        for (int n = 0; n < Cout; ++n)
+            for (int c = 0; c < Cin; ++c)
+                for (int j = 0; j < k; ++j) b.h[gm.wt + ((size_t)j * Cin + c) * Cout + n] = W[((size_t)n * Cin + c) * k + j];
+        gm.has_bias = bias;
+        if (bias) gm.bias = b.vec(key + ".bias");
+        return gm;
+    };
+    auto snake = [&](const std::string& key) {          // exp(alpha) | 1 / exp(beta), in f32 as the reference forms them
+        Snake s;
+        const auto &al = b.t(key + ".alpha"), &be = b.t(key + ".beta");
+        s.a = b.take(al.size()); s.b = b.take(be.size());
+        for (size_t i = 0; i < al.size(); ++i) { b.h[s.a + i] = expf(al[i]); b.h[s.b + i] = 1.0f / expf(be[i]); }
+        return s;
+    };
+    // codebooks (TTSWeightLoading+Encoder.swift:121-139) as [S][D], transposed [D][S] for the score GEMM, and |c|^2 in f32
+    for (int chain = 0; chain < 2; ++chain) {
+        const int n = chain ? g.acoustic_size : g.semantic_size, stages = chain ? Q - 1 : 1;
+        cb_[chain] = b.take((size_t)stages * n * D);
+        cbt_[chain] = b.take((size_t)stages * n * D);
+        csq_[chain] = b.take((size_t)stages * n);
+        for (int st = 0; st < stages; ++st) {
+            const int q = chain + st;
+            const std::string p = codec_enc_codebook_prefix(q);
+            float* e = b.h.data() + cb_[chain] + (size_t)st * n * D;
+            if (embed_stored[q]) std::copy(b.t(p + ".embed").begin(), b.t(p + ".embed").end(), e);
+            else {
+                const auto &sum = b.t(p + ".embedding_sum"), &use = b.t(p + ".cluster_usage");
+                for (int i = 0; i < n; ++i)
+                    for (int d = 0; d < D; ++d) e[(size_t)i * D + d] = sum[(size_t)i * D + d] / std::max(use[i], 1e-7f);
+            }
+            float* et = b.h.data() + cbt_[chain] + (size_t)st * n * D;
+            float* sq = b.h.data() + csq_[chain] + (size_t)st * n;
+            for (int i = 0; i < n; ++i) {
+                float s = 0.0f;
+                for (int d = 0; d < D; ++d) { const float v = e[(size_t)i * D + d]; et[(size_t)d * n + i] = v; s = s + v * v; }
+                sq[i] = s;
+            }
+        }
+    }
+    {   // both input projections as one GEMM: columns [first | rest]
+        rvq_.K = H; rvq_.N = 2 * D; rvq_.Cin = H; rvq_.taps = 1;
+        rvq_.wt = b.take((size_t)H * 2 * D);
+        const auto &w1 = b.t("encoder.quantizer.rvq_first.input_proj.weight"), &w2 = b.t("encoder.quantizer.rvq_rest.input_proj.weight");
+        for (int c = 0; c < H; ++c)
+            for (int d = 0; d < D; ++d) {
+                b.h[rvq_.wt + (size_t)c * 2 * D + d] = w1[(size_t)c * D + d];
+                b.h[rvq_.wt + (size_t)c * 2 * D + D + d] = w2[(size_t)c * D + d];
+            }
+    }
+    int c = Dd / 16;
+    {   // [C][1][7] -> [7][C]
+        const auto& W = b.t("encoder.encoder.0.conv.weight");
+        in_w_ = b.take((size_t)7 * c);
+        for (int ch = 0; ch < c; ++ch)
+            for (int j = 0; j < 7; ++j) b.h[in_w_ + (size_t)j * c + ch] = W[(size_t)ch * 7 + j];
+        in_b_ = b.vec("encoder.encoder.0.conv.bias");
+    }
+    width_[0] = c;
+    for (int k = 0; k < 4; ++k) {
+        const std::string p = "encoder.encoder." + std::to_string(k + 1) + ".block.";
+        Block& bl = blocks_[k];
+        for (int j = 0; j < 3; ++j) {
+            const std::string u = p + std::to_string(j) + ".";
+            bl.u[j].s1 = snake(u + "act1"); bl.u[j].s2 = snake(u + "act2");
+            bl.u[j].c1 = conv(u + "conv1.conv", c, c, 7, true);
+            bl.u[j].c2 = conv(u + "conv2.conv", c, c, 1, true);
+        }
+        bl.s = snake(p + "3");
+        bl.sconv = conv(p + "4.conv", 2 * c, c, 2 * stride_[k], true);
+        c *= 2;
+        width_[k + 1] = c;
+    }
+    width_[4] = std::max(c, 4 * L); width_[5] = 4 * L; width_[6] = L;
+    enc5_ = conv("encoder.encoder.5.conv", L, Dd, 7, true);
+    for (int i = 0; i < 2; ++i) {
+        const std::string p = "encoder.downsample." + std::to_string(i) + ".";
+        Down& u = down_[i];
+        const auto& dw = b.t(p + "0.dwconv.conv.weight");                // [L][1][7] -> [7][L]
+        u.dw = b.take((size_t)7 * L);
+        for (int ch = 0; ch < L; ++ch)
+            for (int j = 0; j < 7; ++j) b.h[u.dw + (size_t)j * L + ch] = dw[(size_t)ch * 7 + j];
+        u.dwb = b.vec(p + "0.dwconv.conv.bias");
+        u.lnw = b.vec(p + "0.norm.weight"); u.lnb = b.vec(p + "0.norm.bias");
+        u.pw1 = conv(p + "0.pwconv1", 4 * L, L, 1, true);
+        u.pw2 = conv(p + "0.pwconv2", L, 4 * L, 1, true);
+        u.gamma = b.vec(p + "0.gamma");
+        u.sconv = conv(p + "1.conv", L, L, 2 * stride_[4 + i], true);
+    }
+    post_conv_ = conv("encoder.post_conv.conv", L, L, 3, true);
+    const std::string P = "encoder.pre_transformer.";
+    in_proj_ = conv(P + "input_proj", H, L, 1, true);
+    norm_ = b.vec(P + "norm.weight");
+    for (int l = 0; l < g.layers; ++l) {
+        const std::string p = P + "layers." + std::to_string(l) + ".";
+        Layer ly;
+        ly.n1 = b.vec(p + "input_layernorm.weight"); ly.n2 = b.vec(p + "post_attention_layernorm.weight");
+        ly.ls1 = b.vec(p + "self_attn_layer_scale.scale"); ly.ls2 = b.vec(p + "mlp_layer_scale.scale");
+        ly.qkv.K = H; ly.qkv.N = 3 * A; ly.qkv.Cin = H;
+        ly.qkv.wt = b.take((size_t)H * 3 * A);
+        int part = 0;
+        for (const char* k : {"q_proj", "k_proj", "v_proj"}) {
+            const auto& W = b.t(p + "self_attn." + k + ".weight");
+            for (int n = 0; n < A; ++n)
+                for (int ch = 0; ch < H; ++ch) b.h[ly.qkv.wt + (size_t)ch * 3 * A + part * A + n] = W[(size_t)n * H + ch];
+            ++part;
+        }
+        ly.o = conv(p + "self_attn.o_proj", H, A, 1, false);
+        ly.gu.K = H; ly.gu.N = 2 * I; ly.gu.Cin = H;
+        ly.gu.wt = b.take((size_t)H * 2 * I);
+        const auto &Wg = b.t(p + "mlp.gate_proj.weight"), &Wu = b.t(p + "mlp.up_proj.weight");
+        for (int n = 0; n < I; ++n)
+            for (int ch = 0; ch < H; ++ch) {
+                b.h[ly.gu.wt + (size_t)ch * 2 * I + 2 * n] = Wg[(size_t)n * H + ch];
+                b.h[ly.gu.wt + (size_t)ch * 2 * I + 2 * n + 1] = Wu[(size_t)n * H + ch];
+            }
+        ly.down = conv(p + "mlp.down_proj", H, I, 1, false);
+        layers_.push_back(ly);
+    }
+    // rows a pass can hold at every level: a clip of n samples has ceil(n / rate) rows, so max_samples / rate + one per clip
+    long rate = 1;
+    size_t big = 0;
+    for (int l = 0; l < CENC_LEVELS; ++l) {
+        rows_cap_[l] = (max_samples + rate - 1) / rate + CENC_MAX_CLIPS;
+        if (l == 0) rows_cap_[l] = max_samples;
+        big = std::max(big, (size_t)rows_cap_[l] * width_[l]);
+        if (l < 6) rate *= stride_[l];
+    }
+    const long max_frames = (max_samples + rate - 1) / rate;
+    rope_ = b.take((size_t)max_frames * 32 * 2);       // MLXNN.RoPE base 10000 over all 64 dimensions, positions 0 .. a clip's last frame
+    for (long t = 0; t < max_frames; ++t)
+        for (int d = 0; d < 32; ++d) {
+            const float inv = (float)pow(10000.0, -(double)d / 32.0), ang = (float)t * inv;
+            b.h[rope_ + ((size_t)t * 32 + d) * 2] = (float)cos((double)ang);
+            b.h[rope_ + ((size_t)t * 32 + d) * 2 + 1] = (float)sin((double)ang);
+        }
+    QASR_HIP(hipSetDevice(device_));
+    QASR_HIP(hipStreamCreateWithFlags(&own_, hipStreamNonBlocking));
+    work_ = work ? work : own_;
+    for (auto& e : ev_) QASR_HIP(hipEventCreate(&e));
+    d_w_.alloc(b.h.size() * sizeof(float));
+    QASR_HIP(hipMemcpy(d_w_.p, b.h.data(), b.h.size() * sizeof(float), hipMemcpyHostToDevice));
+    // every buffer of a pass, sized once
+    const size_t F = sizeof(float), R6 = (size_t)rows_cap_[6];
+    d_start_.alloc((size_t)CENC_LEVELS * (CENC_MAX_CLIPS + 1) * sizeof(int));
+    d_tiles_.alloc((R6 / AT_Q + CENC_MAX_CLIPS + 1) * 4 * sizeof(int));
+    d_pcm_.alloc((size_t)max_samples * F);
+    for (auto& buf : d_big_) buf.alloc(big * F);
+    d_x_.alloc(R6 * H * F); d_h_.alloc(R6 * H * F); d_qkv_.alloc(R6 * 3 * A * F); d_att_.alloc(R6 * A * F); d_g_.alloc(R6 * I * F);
+    d_r_.alloc(R6 * 2 * D * F); d_codes_.alloc(R6 * Q * sizeof(int));
+}
+
+CodecEncQwen3TTS::~CodecEncQwen3TTS() {
+    if (work_) (void)hipStreamSynchronize(work_);
+    for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
+    if (own_) (void)hipStreamDestroy(own_);
+}
+
+void CodecEncQwen3TTS::unload() {
+    if (!loaded_) return;
+    QASR_HIP(hipSetDevice(device_));
+    QASR_HIP(hipStreamSynchronize(work_));
+    for (DevBuf* b : {&d_w_, &d_start_, &d_tiles_, &d_pcm_, &d_big_[0], &d_big_[1], &d_big_[2], &d_x_, &d_h_, &d_qkv_, &d_att_, &d_g_, &d_r_,
+                      &d_codes_})
+        b->release();
+    loaded_ = false;
+}
+
+void CodecEncQwen3TTS::check_loaded() const {
+    if (!loaded_) throw NotLoaded("speech tokenizer encoder: model unloaded");
+}
+
+// ---- a pass -------------------------------------------------------------------------------------------------------------------------
+// uploads the pass's tables and samples: start[level][clip], the attention's query tiles, pcm back to back
+void CodecEncQwen3TTS::plan(const CodecEncClip* c, int n) {
+    QASR_HIP(hipStreamSynchronize(work_));             // the tables are rewritten
+    n_clips_ = n;
+    h_start_.assign((size_t)CENC_LEVELS * (CENC_MAX_CLIPS + 1), 0);
+    h_tiles_.clear();
+    long at[CENC_LEVELS] = {};
+    for (int i = 0; i < n; ++i) {
+        long len[CENC_LEVELS];
+        codec_enc_lengths(g_, c[i].n, len);
+        for (int l = 0; l < CENC_LEVELS; ++l) h_start_[(size_t)l * (CENC_MAX_CLIPS + 1) + i] = (int)at[l];
+        for (long q0 = 0; q0 < len[6]; q0 += AT_Q) {
+            h_tiles_.push_back((int)at[6]); h_tiles_.push_back((int)len[6]); h_tiles_.push_back((int)q0); h_tiles_.push_back(0);
+        }
+        for (int l = 0; l < CENC_LEVELS; ++l) at[l] += len[l];
+    }
+    for (int l = 0; l < CENC_LEVELS; ++l) {
+        h_start_[(size_t)l * (CENC_MAX_CLIPS + 1) + n] = (int)at[l];
+        M_[l] = at[l];
+        if (at[l] > rows_cap_[l]) throw std::length_error("speech tokenizer encoder: a pass exceeds its buffers");
+    }
+    n_tiles_ = (int)(h_tiles_.size() / 4);
+    if (h_tiles_.size() * sizeof(int) > d_tiles_.bytes) throw std::length_error("speech tokenizer encoder: a pass exceeds its tile table");
+    h_pcm_.resize((size_t)at[0]);
+    long off = 0;
+    for (int i = 0; i < n; ++i) { std::memcpy(h_pcm_.data() + off, c[i].pcm, (size_t)c[i].n * sizeof(float)); off += c[i].n; }
+    QASR_HIP(hipMemcpy(d_start_.p, h_start_.data(), h_start_.size() * sizeof(int), hipMemcpyHostToDevice));
+    QASR_HIP(hipMemcpy(d_tiles_.p, h_tiles_.data(), h_tiles_.size() * sizeof(int), hipMemcpyHostToDevice));
+    QASR_HIP(hipMemcpy(d_pcm_.p, h_pcm_.data(), h_pcm_.size() * sizeof(float), hipMemcpyHostToDevice));
+}
+
+template <bool SNAKE, int EPI>
+void CodecEncQwen3TTS::gemm(const Gemm& gm, const float* A, long M, int dil, int stride, int level, int in_level, const Snake* sn,
+                            const float* ls, const float* R, float* C, int ldc) {
+    const dim3 grid((unsigned)cdiv(M, CG_T), (unsigned)cdiv(gm.N, CG_T));
+    hipLaunchKernelGGL((cenc_gemm_kernel<SNAKE, EPI>), grid, dim3(CG_THREADS), 0, work_, A, M, gm.Cin, gm.taps, dil, stride,
+                       level < 0 ? (const int*)nullptr : starts(level), level < 0 ? (const int*)nullptr : starts(in_level), n_clips_,
+                       W(gm.wt), gm.K, gm.N, gm.has_bias ? W(gm.bias) : (const float*)nullptr, sn ? W(sn->a) : (const float*)nullptr,
+                       sn ? W(sn->b) : (const float*)nullptr, ls, R, C, ldc);
+}
+
+// d_pcm_ -> conv_out_ [frames][latent]; records ev_[1] .. ev_[6]
+void CodecEncQwen3TTS::dev_convs() {
+    const int L = g_.latent;
+    float *a = d_big_[0].as<float>(), *t = d_big_[1].as<float>(), *o = d_big_[2].as<float>();
+    int C = width_[0];
+    hipLaunchKernelGGL(cenc_in_kernel, dim3((unsigned)cdiv(M_[0] * C, ROW_THREADS)), dim3(ROW_THREADS), 0, work_, d_pcm_.as<float>(), M_[0],
+                       C, starts(0), n_clips_, W(in_w_), W(in_b_), a);
+    QASR_HIP(hipEventRecord(ev_[1], work_));
+    const int dil[3] = {1, 3, 9};
+    for (int k = 0; k < 4; ++k) {                      // three residual units, SnakeBeta, strided conv (:63-70)
+        const Block& bl = blocks_[k];
+        for (int j = 0; j < 3; ++j) {
+            gemm<true, E_LIN>(bl.u[j].c1, a, M_[k], dil[j], 1, k, k, &bl.u[j].s1, nullptr, nullptr, t, C);
+            gemm<true, E_RES>(bl.u[j].c2, t, M_[k], 1, 1, k, k, &bl.u[j].s2, nullptr, a, a, C);
+        }
+        gemm<true, E_LIN>(bl.sconv, a, M_[k + 1], 1, stride_[k], k + 1, k, &bl.s, nullptr, nullptr, o, 2 * C);
+        std::swap(a, o);
+        C *= 2;
+        QASR_HIP(hipEventRecord(ev_[2 + k], work_));
+    }
+    gemm<false, E_LIN>(enc5_, a, M_[4], 1, 1, 4, 4, nullptr, nullptr, nullptr, t, L);
+    std::swap(a, t);
+    for (int i = 0; i < 2; ++i) {                      // ConvNeXt, strided conv (:233-236)
+        const Down& u = down_[i];
+        const int lv = 4 + i;
+        hipLaunchKernelGGL(cenc_dwln_kernel, dim3((unsigned)M_[lv]), dim3(ROW_THREADS), 0, work_, a, L, starts(lv), n_clips_, W(u.dw), W(u.dwb),
+                           W(u.lnw), W(u.lnb), t);
+        gemm<false, E_GELU>(u.pw1, t, M_[lv], 1, 1, -1, -1, nullptr, nullptr, nullptr, o, 4 * L);
+        gemm<false, E_LSRES>(u.pw2, o, M_[lv], 1, 1, -1, -1, nullptr, W(u.gamma), a, a, L);
+        gemm<false, E_LIN>(u.sconv, a, M_[lv + 1], 1, stride_[lv], lv + 1, lv, nullptr, nullptr, nullptr, t, L);
+        std::swap(a, t);
+    }
+    gemm<false, E_LIN>(post_conv_, a, M_[6], 1, 1, 6, 6, nullptr, nullptr, nullptr, t, L);
+    conv_out_ = t;
+    QASR_HIP(hipEventRecord(ev_[6], work_));
+    QASR_HIP(hipGetLastError());
+}
+
+// conv_out_ -> d_h_ [frames][hidden]; records ev_[7]
+void CodecEncQwen3TTS::dev_transformer() {
+    const int H = g_.hidden, A = g_.heads * g_.head_dim;
+    const long M = M_[6];
+    float *x = d_x_.as<float>(), *h = d_h_.as<float>(), *qkv = d_qkv_.as<float>(), *att = d_att_.as<float>(), *gg = d_g_.as<float>();
+    gemm<false, E_LIN>(in_proj_, conv_out_, M, 1, 1, -1, -1, nullptr, nullptr, nullptr, x, H);
+    for (const Layer& ly : layers_) {
+        hipLaunchKernelGGL(cenc_rms_kernel, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(ly.n1), g_.eps, h);
+        gemm<false, E_LIN>(ly.qkv, h, M, 1, 1, -1, -1, nullptr, nullptr, nullptr, qkv, 3 * A);
+        hipLaunchKernelGGL(cenc_attn_kernel, dim3((unsigned)n_tiles_, (unsigned)g_.heads), dim3(ROW_THREADS), 0, work_, qkv,
+                           d_tiles_.as<int4>(), reinterpret_cast<const float2*>(W(rope_)), g_.heads, att);
+        gemm<false, E_LSRES>(ly.o, att, M, 1, 1, -1, -1, nullptr, W(ly.ls1), x, x, H);
+        hipLaunchKernelGGL(cenc_rms_kernel, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(ly.n2), g_.eps, h);
+        gemm<false, E_SWIGLU>(ly.gu, h, M, 1, 1, -1, -1, nullptr, nullptr, nullptr, gg, 2 * H);
+        gemm<false, E_LSRES>(ly.down, gg, M, 1, 1, -1, -1, nullptr, W(ly.ls2), x, x, H);
+    }
+    hipLaunchKernelGGL(cenc_rms_kernel, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(norm_), g_.eps, h);
+    QASR_HIP(hipEventRecord(ev_[7], work_));
+    QASR_HIP(hipGetLastError());
+}
+
+// d_h_ [F][hidden] -> d_codes_ [F][Q]; records ev_[8]
+void CodecEncQwen3TTS::dev_rvq(long F) {
+    const int D = g_.codebook_dim;
+    gemm<false, E_LIN>(rvq_, d_h_.as<float>(), F, 1, 1, -1, -1, nullptr, nullptr, nullptr, d_r_.as<float>(), 2 * D);
+    hipLaunchKernelGGL(cenc_vq_kernel, dim3((unsigned)cdiv(F, CG_T), 2), dim3(CG_THREADS), 0, work_, d_r_.as<float>(), F, 2 * D, D,
+                       g_.quantizers, W(cb_[0]), W(cbt_[0]), W(csq_[0]), g_.semantic_size, W(cb_[1]), W(cbt_[1]), W(csq_[1]),
+                       g_.acoustic_size, d_codes_.as<int>());
+    QASR_HIP(hipEventRecord(ev_[8], work_));
+    QASR_HIP(hipGetLastError());
+}
+
+// d_codes_ rows row0 .. row0 + frames of F -> codes [Q][frames]
+void CodecEncQwen3TTS::fetch_codes(long F, long row0, long frames, int32_t* codes) {
+    const int Q = g_.quantizers;
+    if (row0 == 0) {
+        h_codes_.resize((size_t)F * Q);
+        QASR_HIP(hipMemcpyAsync(h_codes_.data(), d_codes_.p, h_codes_.size() * sizeof(int32_t), hipMemcpyDeviceToHost, work_));
+        QASR_HIP(hipStreamSynchronize(work_));
+    }
+    for (long t = 0; t < frames; ++t)
+        for (int q = 0; q < Q; ++q) codes[(size_t)q * frames + t] = h_codes_[(size_t)(row0 + t) * Q + q];
+}
+
+void CodecEncQwen3TTS::pass(const CodecEncClip* c, int n, Mode mode) {
+    QASR_HIP(hipSetDevice(device_));
+    plan(c, n);
+    const size_t F = sizeof(float);
+    QASR_HIP(hipEventRecord(ev_[0], work_));
+    dev_convs();
+    int last = 6;
+    if (mode != CONV) { dev_transformer(); last = 7; }
+    if (mode == ENCODE) { dev_rvq(M_[6]); last = 8; }
+    const int* fs = h_start_.data() + (size_t)6 * (CENC_MAX_CLIPS + 1);
+    if (mode == ENCODE) {
+        for (int i = 0; i < n; ++i) fetch_codes(M_[6], fs[i], fs[i + 1] - fs[i], c[i].codes);
+    } else {
+        const int width = mode == CONV ? g_.latent : g_.hidden;
+        const float* src = mode == CONV ? conv_out_ : d_h_.as<float>();
+        for (int i = 0; i < n; ++i)
+            QASR_HIP(hipMemcpyAsync(c[i].out, src + (size_t)fs[i] * width, (size_t)(fs[i + 1] - fs[i]) * width * F, hipMemcpyDeviceToHost, work_));
+        QASR_HIP(hipStreamSynchronize(work_));
+    }
+    QASR_HIP(hipGetLastError());
+    for (int s = 0; s < last; ++s) {
+        float ms = 0;
+        QASR_HIP(hipEventElapsedTime(&ms, ev_[s], ev_[s + 1]));
+        timing_[s] += ms;
+    }
+}
+
+// ---- entry points -------------------------------------------------------------------------------------------------------------------
+void CodecEncQwen3TTS::run(const std::vector<CodecEncClip>& clips, Mode mode) {
+    check_loaded();
+    for (float& t : timing_) t = 0.0f;
+    for (size_t i = 0; i < clips.size(); ++i)
+        if (clips[i].n < 1 || clips[i].n > max_samples_)
+            throw std::invalid_argument("speech tokenizer encoder: item " + std::to_string(i) + " holds " + std::to_string(clips[i].n) +
+                                        " samples, a clip holds 1.." + std::to_string(max_samples_) + " (max_samples; the encoder is not chunked)");
+    for (size_t i = 0; i < clips.size();) {            // passes end at clip boundaries
+        size_t j = i;
+        long total = 0;
+        while (j < clips.size() && j - i < (size_t)CENC_MAX_CLIPS && total + clips[j].n <= max_samples_) total += clips[j++].n;
+        pass(clips.data() + i, (int)(j - i), mode);
+        i = j;
+    }
+}
+
+void CodecEncQwen3TTS::quantize(const float* h, long F, int32_t* codes) {
+    check_loaded();
+    for (float& t : timing_) t = 0.0f;
+    QASR_HIP(hipSetDevice(device_));
+    const int H = g_.hidden, Q = g_.quantizers;
+    std::vector<int32_t> part;
+    for (long f0 = 0; f0 < F; f0 += rows_cap_[6]) {    // frames are independent: any split gives the same codes
+        const long n = std::min(F - f0, rows_cap_[6]);
+        QASR_HIP(hipStreamSynchronize(work_));
+        QASR_HIP(hipMemcpyAsync(d_h_.p, h + (size_t)f0 * H, (size_t)n * H * sizeof(float), hipMemcpyHostToDevice, work_));
+        QASR_HIP(hipEventRecord(ev_[7], work_));
+        dev_rvq(n);
+        part.resize((size_t)n * Q);
+        fetch_codes(n, 0, n, part.data());
+        for (int q = 0; q < Q; ++q) std::memcpy(codes + (size_t)q * F + f0, part.data() + (size_t)q * n, (size_t)n * sizeof(int32_t));
+        float ms = 0;
+        QASR_HIP(hipEventElapsedTime(&ms, ev_[7], ev_[8]));
+        timing_[7] += ms;
+    }
+}
+
+}  // namespace qasr

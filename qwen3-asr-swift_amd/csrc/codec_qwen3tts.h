@@ -28,6 +28,8 @@ struct CodecGeom {                     // SpeechTokenizerDecoderConfig's default
 };
 // throws std::invalid_argument with the offending field
 void codec_check_geometry(const CodecGeom& g);
+// model_dir/config.json's "decoder_config" over the defaults (api_codec.cpp); throws WeightLoadError with messages starting "<who>: "
+CodecGeom codec_read_geometry(const std::string& dir, const char* who);
 // key -> shape of every tensor the decoder reads; embed_stored[q]: codebook q (0 = rvq_first) is stored under `embed`, else under
 // embedding_sum + cluster_usage
 std::vector<std::pair<std::string, std::vector<int64_t>>> codec_tensor_shapes(const CodecGeom& g, const std::vector<bool>& embed_stored);

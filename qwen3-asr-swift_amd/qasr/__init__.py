@@ -4,3 +4,13 @@ The compute path lives entirely in the C-ABI library (csrc/); this package is th
 Python harness used by tests and bench.py.  There is no CPU fallback: importing `qasr.model`
 on a machine without the built library or without a GPU raises.
 """
+
+__all__ = ["SpeechTokenizerEncoder"]
+
+
+def __getattr__(name):
+    # resolved on first use: qasr.codec loads the built library
+    if name == "SpeechTokenizerEncoder":
+        from .codec import SpeechTokenizerEncoder
+        return SpeechTokenizerEncoder
+    raise AttributeError(f"module 'qasr' has no attribute {name!r}")

@@ -291,6 +291,24 @@ SIGNATURES = {
     "qasr_codec_quantizer_decode": (C.c_int, [_E, _I, C.c_size_t, C.c_size_t, _F]),
     "qasr_codec_pre_transformer": (C.c_int, [_E, _F, C.c_size_t, C.c_size_t, _F]),
     "qasr_codec_timing": (C.c_int, [_E, _F]),
+    "qasr_codec_enc_create": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t, _E, _P(_E)]),
+    "qasr_codec_enc_destroy": (None, [_E]),
+    "qasr_codec_enc_last_error": (C.c_char_p, [_E]),
+    "qasr_codec_enc_is_loaded": (C.c_int, [_E]),
+    "qasr_codec_enc_unload": (C.c_int, [_E]),
+    "qasr_codec_enc_memory_footprint": (C.c_size_t, [_E]),
+    "qasr_codec_enc_num_quantizers": (C.c_int, [_E]),
+    "qasr_codec_enc_hidden_size": (C.c_int, [_E]),
+    "qasr_codec_enc_latent_dim": (C.c_int, [_E]),
+    "qasr_codec_enc_num_frames": (C.c_size_t, [C.c_size_t]),
+    "qasr_codec_enc_encode": (C.c_int, [_E, _F, C.c_size_t, _I]),
+    "qasr_codec_enc_encode_batch": (C.c_int, [_E, _P(_F), _P(C.c_size_t), C.c_size_t, _P(_I)]),
+    "qasr_codec_enc_conv": (C.c_int, [_E, _F, C.c_size_t, _F]),
+    "qasr_codec_enc_conv_batch": (C.c_int, [_E, _P(_F), _P(C.c_size_t), C.c_size_t, _P(_F)]),
+    "qasr_codec_enc_latent": (C.c_int, [_E, _F, C.c_size_t, _F]),
+    "qasr_codec_enc_latent_batch": (C.c_int, [_E, _P(_F), _P(C.c_size_t), C.c_size_t, _P(_F)]),
+    "qasr_codec_enc_quantize": (C.c_int, [_E, _F, C.c_size_t, _I]),
+    "qasr_codec_enc_timing": (C.c_int, [_E, _F]),
     "qasr_transducer_default_config": (C.c_int, [C.c_char_p, _P(QasrTransducerConfig)]),
     "qasr_tdt_greedy_decode": (C.c_int, [_P(QasrTransducerConfig), _P(QasrTransducerCallbacks), C.c_int32, _I, _F, C.c_int32, _F]),
     "qasr_rnnt_greedy_decode": (C.c_int, [_P(QasrTransducerConfig), _P(QasrTransducerCallbacks), C.c_int32, C.c_int32, _I, _F, C.c_int32, _I]),

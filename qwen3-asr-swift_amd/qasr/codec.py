@@ -156,3 +156,127 @@ class SpeechTokenizerDecoder:
         out = np.zeros_like(a)
         self._check(self.lib.qasr_codec_pre_transformer(self.h, _fptr(a), a.shape[0], a.shape[1], _fptr(out)))
         return out[0] if single else out
+
+
+ENC_STAGES = ("input", "block1", "block2", "block3", "block4", "downsample", "pre_transformer", "quantizer")
+
+
+def num_frames(n: int) -> int:
+    """Frames of a clip of n samples: ceil(n / 1920) (qasr_codec_enc_num_frames; host only)."""
+    return int(_lib.load(strict=True).qasr_codec_enc_num_frames(int(n)))
+
+
+class SpeechTokenizerEncoder:
+    """SpeechTokenizerEncoder on the device (Sources/Qwen3TTS/SpeechTokenizerEncoder.swift; include/qasr.h, qasr_codec_enc_*):
+    24 kHz mono float32 PCM -> int32 codes [16, ceil(n / 1920)].  f32 throughout; no CPU fallback."""
+    sample_rate = SAMPLE_RATE
+
+    def __init__(self, handle):
+        self.lib, self.h = _lib.load(strict=True), handle
+
+    @classmethod
+    def from_pretrained(cls, model_dir, device=0, order_with=None, max_samples=0):
+        """model_dir/model.safetensors in the checkpoint's encoder.* keys (the decoder.* keys may sit beside them) and config.json when
+        the geometry is not the default.  max_samples: samples one device pass holds (0 = 720000); a longer clip is refused, a longer
+        batch runs in several passes with identical results."""
+        lib = _lib.load(strict=True)
+        eng = getattr(order_with, "h", order_with)
+        h = C.c_void_p()
+        rc = lib.qasr_codec_enc_create(int(device), str(model_dir).encode(), int(max_samples), eng, C.byref(h))
+        if rc != 0:
+            raise QasrError(f"qasr error {rc}: {lib.qasr_codec_enc_last_error(None).decode()}")
+        return cls(h)
+
+    def close(self):
+        if self.h:
+            self.lib.qasr_codec_enc_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def _check(self, rc):
+        if rc != 0:
+            raise QasrError(f"qasr error {rc}: {self.lib.qasr_codec_enc_last_error(self.h).decode()}")
+
+    @property
+    def is_loaded(self) -> bool:
+        return bool(self.lib.qasr_codec_enc_is_loaded(self.h))
+
+    def unload(self):
+        self._check(self.lib.qasr_codec_enc_unload(self.h))
+
+    @property
+    def memory_footprint(self) -> int:
+        return int(self.lib.qasr_codec_enc_memory_footprint(self.h))
+
+    @property
+    def num_quantizers(self) -> int:
+        return int(self.lib.qasr_codec_enc_num_quantizers(self.h))
+
+    @property
+    def hidden_size(self) -> int:
+        return int(self.lib.qasr_codec_enc_hidden_size(self.h))
+
+    @property
+    def latent_dim(self) -> int:
+        return int(self.lib.qasr_codec_enc_latent_dim(self.h))
+
+    def timing(self) -> Dict[str, float]:
+        """Device milliseconds of the last call per stage."""
+        ms = (C.c_float * len(ENC_STAGES))()
+        self._check(self.lib.qasr_codec_enc_timing(self.h, ms))
+        return dict(zip(ENC_STAGES, (float(v) for v in ms)))
+
+    def _batch(self, fn, clips, width):
+        """clips -> one array per clip: int32 [Q, frames] (width None) or float32 [frames, width]."""
+        items = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1) for p in clips]
+        B = len(items)
+        if B == 0:
+            return []
+        frames = [num_frames(a.size) for a in items]
+        if width is None:
+            outs = [np.zeros((self.num_quantizers, f), dtype=np.int32) for f in frames]
+            op = (_I * B)(*[_iptr(o) for o in outs])
+        else:
+            outs = [np.zeros((f, width), dtype=np.float32) for f in frames]
+            op = (_F * B)(*[_fptr(o) for o in outs])
+        pp = (_F * B)(*[_fptr(a) for a in items])
+        self._check(fn(self.h, pp, (C.c_size_t * B)(*[a.size for a in items]), B, op))
+        return outs
+
+    # ---- whole path ----
+    def encode(self, pcm) -> np.ndarray:
+        """encode(samples:): pcm [n] -> codes [16, ceil(n / 1920)]."""
+        a = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1)
+        out = np.zeros((self.num_quantizers, num_frames(a.size)), dtype=np.int32)
+        self._check(self.lib.qasr_codec_enc_encode(self.h, _fptr(a), a.size, _iptr(out)))
+        return out
+
+    def encode_batch(self, clips: Sequence) -> List[np.ndarray]:
+        """Clips of any lengths in one call; each is bit-identical to encode() of it alone."""
+        return self._batch(self.lib.qasr_codec_enc_encode_batch, clips, None)
+
+    # ---- stages ----
+    def conv(self, pcm) -> np.ndarray:
+        """The convolutional front up to post_conv: pcm [n] -> [frames, latent]."""
+        return self.conv_batch([pcm])[0]
+
+    def conv_batch(self, clips: Sequence) -> List[np.ndarray]:
+        return self._batch(self.lib.qasr_codec_enc_conv_batch, clips, self.latent_dim)
+
+    def latent(self, pcm) -> np.ndarray:
+        """... and the unmasked pre-transformer with its final norm: pcm [n] -> [frames, hidden]."""
+        return self.latent_batch([pcm])[0]
+
+    def latent_batch(self, clips: Sequence) -> List[np.ndarray]:
+        return self._batch(self.lib.qasr_codec_enc_latent_batch, clips, self.hidden_size)
+
+    def quantize(self, h) -> np.ndarray:
+        """EncoderRVQ.encode: h [F, hidden] -> codes [16, F]."""
+        a = np.ascontiguousarray(h, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] != self.hidden_size:
+            raise QasrError(f"qasr error 1: h is [F, {self.hidden_size}]")
+        out = np.zeros((self.num_quantizers, a.shape[0]), dtype=np.int32)
+        self._check(self.lib.qasr_codec_enc_quantize(self.h, _fptr(a), a.shape[0], _iptr(out)))
+        return out

@@ -595,3 +595,108 @@ def write_speech_tokenizer_safetensors(sd: dict, model_dir: str, geometry=None, 
         with open(os.path.join(model_dir, "config.json"), "w") as f:
             json.dump({"decoder_config": cfg}, f)
     return model_dir
+
+
+# ---- Qwen3-TTS speech tokenizer encoder (SpeechTokenizerEncoder.swift, TTSWeightLoading+Encoder.swift) ----------------------------
+def speech_tokenizer_encoder_tensor_shapes(geometry=None) -> dict:
+    """key -> shape of every encoder.* tensor in the checkpoint's names and PyTorch layouts (TTSWeightLoading+Encoder.swift).  The channel
+    schedule is the decoder's reversed (decoder_dim / 16 .. decoder_dim), the strides upsample_rates reversed then upsampling_ratios
+    reversed.  input_proj is the [hidden, codebook_dim, 1] matrix ResidualVectorQuantizer.encode multiplies by.  A codebook appears
+    under its `embed` key; the loader also takes embedding_sum + cluster_usage in its place."""
+    g = geometry or CODEC_REAL
+    L, H, Dd, D, A = g["latent_dim"], g["hidden_size"], g["decoder_dim"], g["codebook_dim"], g["num_heads"] * g["head_dim"]
+    strides = tuple(reversed(g["upsample_rates"])) + tuple(reversed(g["upsampling_ratios"]))
+    s = {}
+    for name, n, size in (("rvq_first", 1, g["semantic_codebook_size"]), ("rvq_rest", g["num_quantizers"] - 1, g["acoustic_codebook_size"])):
+        for i in range(n):
+            s[f"encoder.quantizer.{name}.vq.layers.{i}._codebook.embed"] = (size, D)
+        s[f"encoder.quantizer.{name}.input_proj.weight"] = (H, D, 1)
+    c = Dd // 16
+    s["encoder.encoder.0.conv.weight"], s["encoder.encoder.0.conv.bias"] = (c, 1, 7), (c,)
+    for b in range(4):
+        p = f"encoder.encoder.{b + 1}.block."
+        for j in range(3):
+            for a in ("act1", "act2"):
+                s[p + f"{j}.{a}.alpha"] = s[p + f"{j}.{a}.beta"] = (c,)
+            s[p + f"{j}.conv1.conv.weight"], s[p + f"{j}.conv2.conv.weight"] = (c, c, 7), (c, c, 1)
+            s[p + f"{j}.conv1.conv.bias"] = s[p + f"{j}.conv2.conv.bias"] = (c,)
+        s[p + "3.alpha"] = s[p + "3.beta"] = (c,)
+        s[p + "4.conv.weight"], s[p + "4.conv.bias"] = (2 * c, c, 2 * strides[b]), (2 * c,)
+        c *= 2
+    s["encoder.encoder.5.conv.weight"], s["encoder.encoder.5.conv.bias"] = (L, Dd, 7), (L,)
+    for i in range(2):
+        p = f"encoder.downsample.{i}."
+        s[p + "0.dwconv.conv.weight"], s[p + "0.dwconv.conv.bias"] = (L, 1, 7), (L,)
+        s[p + "0.norm.weight"] = s[p + "0.norm.bias"] = s[p + "0.gamma"] = s[p + "0.pwconv2.bias"] = (L,)
+        s[p + "0.pwconv1.weight"], s[p + "0.pwconv1.bias"] = (4 * L, L), (4 * L,)
+        s[p + "0.pwconv2.weight"] = (L, 4 * L)
+        s[p + "1.conv.weight"], s[p + "1.conv.bias"] = (L, L, 2 * strides[4 + i]), (L,)
+    s["encoder.post_conv.conv.weight"], s["encoder.post_conv.conv.bias"] = (L, L, 3), (L,)
+    P = "encoder.pre_transformer."
+    s[P + "input_proj.weight"], s[P + "input_proj.bias"] = (H, L), (H,)
+    s[P + "output_proj.weight"], s[P + "output_proj.bias"] = (L, H), (L,)
+    s[P + "norm.weight"] = (H,)
+    for l in range(g["num_layers"]):
+        p = P + f"layers.{l}."
+        for k in ("q_proj", "k_proj", "v_proj"):
+            s[p + f"self_attn.{k}.weight"] = (A, H)
+        s[p + "self_attn.o_proj.weight"] = (H, A)
+        s[p + "input_layernorm.weight"] = s[p + "post_attention_layernorm.weight"] = (H,)
+        s[p + "mlp.gate_proj.weight"] = s[p + "mlp.up_proj.weight"] = (2 * H, H)
+        s[p + "mlp.down_proj.weight"] = (H, 2 * H)
+        s[p + "self_attn_layer_scale.scale"] = s[p + "mlp_layer_scale.scale"] = (H,)
+    return s
+
+
+def synth_speech_tokenizer_encoder_state_dict(seed: int = 0, geometry=None) -> dict:
+    """Seeded encoder weights {key: float32 array} by the decoder's drawing rules (synth_speech_tokenizer_state_dict), from an rng of
+    their own: layer scales around 0.5, alpha and beta in [-0.5, 0.5], norm weights away from 1, fan-in scaled matrices (residual-unit
+    convs at gain 0.6) that keep the signal O(1) down the chain, even codebooks stored as `embed`, odd ones as embedding_sum +
+    cluster_usage with a few usages below the loader's 1e-7 clamp.  The input projections of the quantizers have unit gain, so a
+    residual is on the scale of the codebook entries (std 0.5 per coordinate)."""
+    g = geometry or CODEC_REAL
+    rng = np.random.default_rng(73003 + seed)
+    sd = {}
+    for key, shape in speech_tokenizer_encoder_tensor_shapes(g).items():
+        leaf = key.rsplit(".", 1)[-1]
+        if leaf == "embed":
+            e = rng.standard_normal(shape) * 0.5
+            q = int(key.split(".layers.")[1].split(".")[0]) + (0 if "rvq_first" in key else 1)
+            if q % 2 == 0:
+                sd[key] = e
+            else:
+                usage = 0.5 + 4.0 * rng.random(shape[0])
+                usage[rng.integers(0, shape[0], size=max(2, shape[0] // 16))] = 1e-9
+                usage[:2] = 0.0
+                sd[key[:-5] + "cluster_usage"] = usage
+                sd[key[:-5] + "embedding_sum"] = e * np.maximum(usage, 1e-7)[:, None]
+        elif leaf in ("alpha", "beta"):
+            sd[key] = rng.uniform(-0.5, 0.5, shape)
+        elif leaf in ("scale", "gamma"):
+            sd[key] = 0.5 + 0.1 * rng.standard_normal(shape)
+        elif leaf == "bias":
+            sd[key] = 0.05 * rng.standard_normal(shape)
+        elif len(shape) == 1:                                          # norm weights
+            sd[key] = 1.0 + 0.2 * rng.standard_normal(shape)
+        else:
+            if "dwconv" in key:
+                fan, gain = shape[2], 1.0
+            elif "quantizer" in key:
+                fan, gain = shape[0], 1.0                             # h @ w sums over hidden
+            elif len(shape) == 3:
+                fan, gain = shape[1] * shape[2], (0.6 if ".conv1." in key or ".conv2." in key else 1.0)
+            else:
+                fan, gain = shape[1], 1.0
+            sd[key] = gain * rng.standard_normal(shape) / np.sqrt(fan)
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in sd.items()}
+
+
+def merge_speech_tokenizer_state_dicts(decoder_sd: dict, encoder_sd: dict) -> dict:
+    """One state dict holding both halves (decoder.* and encoder.* keys), as the real model.safetensors does; write it with
+    write_speech_tokenizer_safetensors."""
+    both = dict(decoder_sd)
+    for k, v in encoder_sd.items():
+        if k in both:
+            raise ValueError("key in both halves: " + k)
+        both[k] = v
+    return both
