@@ -772,6 +772,51 @@ int qasr_codec_enc_quantize(qasr_codec_enc* c, const float* h, size_t F, int32_t
  * pre-transformer, quantizer */
 int qasr_codec_enc_timing(const qasr_codec_enc* c, float* ms);
 
+/* ---- Qwen3-TTS ECAPA-TDNN speaker encoder (csrc/xvec_qwen3tts.hip, csrc/api_xvec.cpp) -----------------------------------------------
+ * Reference: Sources/Qwen3TTS/SpeakerEncoder.swift.  24 kHz mono PCM of a voice-cloning reference clip -> one x-vector, what
+ * Qwen3TTS.swift:222-223 and Qwen3TTS+ICL.swift:93-94 compute from the clip beside its codes (qasr_codec_enc_*).  What each entry
+ * replaces:
+ *   TTSWeightLoader.loadSpeakerEncoderWeights (TTSWeightLoading.swift:385-453), local directory -> qasr_xvec_create
+ *   SpeakerMel.compute (SpeakerEncoder.swift:245-388)                                            -> qasr_xvec_mel
+ *   SpeakerEncoder.callAsFunction (:214-238)                                                     -> qasr_xvec_embed_mel
+ *   speakerEncoder(SpeakerMel.compute(audio:))                                                   -> qasr_xvec_embed / _embed_batch
+ * A clip of n >= 1 samples gives n / 256 + 1 frames of 128 log-mel bins (reflect pad 512 with the reference's clamped indices, periodic
+ * Hann 1024, DFT magnitudes, unnormalised HTK triangles 0 .. 12 kHz, log(max(., 1e-5))).  Every Conv1d pads with zeros inside its clip.
+ * The embedding is not normalised (the reference does not).  Precision: f32 throughout.  A clip's log-mel and embedding are
+ * bit-identical alone, in any batch and place, under any split into passes, and run to run.  One object, one
+ * thread at a time.  Not covered: the Talker, the code predictor, resampling, bf16 forms. */
+typedef struct qasr_xvec qasr_xvec;
+/* model_dir: every *.safetensors file of it is searched for the speaker_encoder.* keys (:389-397: blocks.0.conv, blocks.{1,2,3}.{tdnn1.conv,
+ * tdnn2.conv, res2net_block.blocks.{0..6}.conv, se_block.conv1, se_block.conv2}, mfa.conv, asp.tdnn.conv, asp.conv, fc; .weight
+ * [out][k][in] as stored (:436-437), .bias); F32, F16 or BF16, widened at upload.  Other keys are neither read nor an error.  The
+ * embedding width is fc.weight's first dimension.  Everything is checked before any HIP call: a missing key, or no speaker_encoder.
+ * key at all -> QASR_ERR_IO, a wrong shape or dtype -> QASR_ERR_INVALID, the key named in qasr_xvec_last_error(NULL).  max_samples:
+ * samples one device pass holds (0 = 64 x 10 s; at most 2^28); every buffer is sized from it at create: about 82 bytes of device
+ * memory per sample (4864 f32 per frame of activations, the PCM, the tile partials) plus 0.1 GB that does not depend on it (f32
+ * weights, room for 1024 clips), so 1.4 GB at the default and 0.12 GB for one 10 s clip (max_samples = 240000).  order_with: as for
+ * qasr_seg_create. */
+int qasr_xvec_create(int device, const char* model_dir, size_t max_samples, qasr_engine* order_with, qasr_xvec** out);
+void qasr_xvec_destroy(qasr_xvec* x);
+const char* qasr_xvec_last_error(const qasr_xvec* x);               /* x may be NULL: last create() failure */
+int qasr_xvec_is_loaded(const qasr_xvec* x);
+int qasr_xvec_unload(qasr_xvec* x);                                 /* later device calls return QASR_ERR_NOT_LOADED */
+size_t qasr_xvec_memory_footprint(const qasr_xvec* x);              /* parameter bytes as stored, 0 unloaded */
+int qasr_xvec_embedding_dim(const qasr_xvec* x);                    /* fc.weight's rows: 1024 in the reference (:204-206) */
+int qasr_xvec_input_sample_rate(void);                              /* 24000 (:259) */
+size_t qasr_xvec_num_frames(size_t n);                              /* n / 256 + 1 (:305), 0 for 0.  Pure CPU. */
+/* Qwen3TTS.swift:222-223: pcm [n] -> out [E].  sample_rate != 24000 -> QASR_ERR_UNSUPPORTED (the reference resamples with
+ * AVAudioConverter, :249-251); n == 0 -> QASR_ERR_EMPTY_AUDIO; n > max_samples -> QASR_ERR_CAPACITY; NULL -> QASR_ERR_INVALID;
+ * after qasr_xvec_unload every argument gives QASR_ERR_NOT_LOADED. */
+int qasr_xvec_embed(qasr_xvec* x, const float* pcm, size_t n, int sample_rate, float* out);
+/* B clips of any lengths at 24 kHz, cut into passes of at most max_samples samples at clip boundaries: out [B][E]; each row is
+ * bit-identical to qasr_xvec_embed of that clip */
+int qasr_xvec_embed_batch(qasr_xvec* x, const float* const* pcm, const size_t* n, size_t B, float* out);
+/* stage entry points: SpeakerMel.compute (:247-278), out[b] [n[b] / 256 + 1][128]; the network alone (:214-238) on mel [T][128] */
+int qasr_xvec_mel(qasr_xvec* x, const float* const* pcm, const size_t* n, size_t B, float* const* out);
+int qasr_xvec_embed_mel(qasr_xvec* x, const float* mel, size_t T, float* out);
+/* ms[6]: device time of the last call, HIP events on the work stream: front end, initial conv, blocks 1..3, MFA + pooling + fc */
+int qasr_xvec_timing(const qasr_xvec* x, float* ms);
+
 /* transducer greedy loops (pure CPU).  The caller owns the networks and their state:
  *   decoder_step(ctx, token)  advance the prediction network with `token` (the loops prime it with the blank id where the reference does)
  *   joint(ctx, frame, token_logits[vocab_size + 1], duration_logits[n_durations] or NULL)  logits for encoder frame `frame` and the

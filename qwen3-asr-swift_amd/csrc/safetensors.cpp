@@ -136,6 +136,14 @@ CheckedWeights load_checked_f32(const std::string& dir, const char* who,
     std::unique_ptr<SafeTensorsDir> st;
     try { st = std::make_unique<SafeTensorsDir>(dir, file ? file : ""); }
     catch (const std::exception& ex) { throw WeightLoadError(QASR_ERR_IO, pre + ex.what()); }
+    return load_checked_f32(*st, who, shapes, refuse_unknown_keys, optional_default);
+}
+
+CheckedWeights load_checked_f32(const SafeTensorsDir& dir, const char* who,
+                                const std::vector<std::pair<std::string, std::vector<int64_t>>>& shapes, bool refuse_unknown_keys,
+                                float (*optional_default)(const std::string&)) {
+    const std::string pre = std::string(who) + ": ";
+    const SafeTensorsDir* st = &dir;
     if (refuse_unknown_keys)                               // update(parameters:verify: .noUnusedKeys)
         for (const auto& kv : st->entries) {
             bool known = false;

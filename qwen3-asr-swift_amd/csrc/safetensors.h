@@ -48,5 +48,9 @@ struct WeightLoadError : std::runtime_error {      // code: QASR_ERR_IO (missing
 CheckedWeights load_checked_f32(const std::string& dir, const char* who,
                                 const std::vector<std::pair<std::string, std::vector<int64_t>>>& shapes, bool refuse_unknown_keys,
                                 float (*optional_default)(const std::string&) = nullptr, const char* file = nullptr);
+// the same checks over an opened directory: for a checkpoint whose tensors lie in any of the directory's *.safetensors files
+CheckedWeights load_checked_f32(const SafeTensorsDir& dir, const char* who,
+                                const std::vector<std::pair<std::string, std::vector<int64_t>>>& shapes, bool refuse_unknown_keys,
+                                float (*optional_default)(const std::string&) = nullptr);
 
 }  // namespace qasr

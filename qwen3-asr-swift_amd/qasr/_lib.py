@@ -309,6 +309,20 @@ SIGNATURES = {
     "qasr_codec_enc_latent_batch": (C.c_int, [_E, _P(_F), _P(C.c_size_t), C.c_size_t, _P(_F)]),
     "qasr_codec_enc_quantize": (C.c_int, [_E, _F, C.c_size_t, _I]),
     "qasr_codec_enc_timing": (C.c_int, [_E, _F]),
+    "qasr_xvec_create": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t, _E, _P(_E)]),
+    "qasr_xvec_destroy": (None, [_E]),
+    "qasr_xvec_last_error": (C.c_char_p, [_E]),
+    "qasr_xvec_is_loaded": (C.c_int, [_E]),
+    "qasr_xvec_unload": (C.c_int, [_E]),
+    "qasr_xvec_memory_footprint": (C.c_size_t, [_E]),
+    "qasr_xvec_embedding_dim": (C.c_int, [_E]),
+    "qasr_xvec_input_sample_rate": (C.c_int, []),
+    "qasr_xvec_num_frames": (C.c_size_t, [C.c_size_t]),
+    "qasr_xvec_embed": (C.c_int, [_E, _F, C.c_size_t, C.c_int, _F]),
+    "qasr_xvec_embed_batch": (C.c_int, [_E, _P(_F), _P(C.c_size_t), C.c_size_t, _F]),
+    "qasr_xvec_mel": (C.c_int, [_E, _P(_F), _P(C.c_size_t), C.c_size_t, _P(_F)]),
+    "qasr_xvec_embed_mel": (C.c_int, [_E, _F, C.c_size_t, _F]),
+    "qasr_xvec_timing": (C.c_int, [_E, _F]),
     "qasr_transducer_default_config": (C.c_int, [C.c_char_p, _P(QasrTransducerConfig)]),
     "qasr_tdt_greedy_decode": (C.c_int, [_P(QasrTransducerConfig), _P(QasrTransducerCallbacks), C.c_int32, _I, _F, C.c_int32, _F]),
     "qasr_rnnt_greedy_decode": (C.c_int, [_P(QasrTransducerConfig), _P(QasrTransducerCallbacks), C.c_int32, C.c_int32, _I, _F, C.c_int32, _I]),

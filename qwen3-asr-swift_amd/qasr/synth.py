@@ -700,3 +700,61 @@ def merge_speech_tokenizer_state_dicts(decoder_sd: dict, encoder_sd: dict) -> di
             raise ValueError("key in both halves: " + k)
         both[k] = v
     return both
+
+
+def tts_speaker_encoder_tensor_shapes(embedding_dim: int = 1024) -> dict:
+    """key -> shape of every tensor of the Qwen3-TTS ECAPA-TDNN speaker encoder (SpeakerEncoder.swift:176-209; conv weights
+    [out, k, in] as the checkpoint stores them, TTSWeightLoading.swift:436-437), keys without the `speaker_encoder.` prefix."""
+    s = {}
+
+    def conv(k, out, taps, cin):
+        s[k + ".weight"], s[k + ".bias"] = (out, taps, cin), (out,)
+
+    conv("blocks.0.conv", 512, 5, 128)
+    for b in (1, 2, 3):
+        p = f"blocks.{b}."
+        conv(p + "tdnn1.conv", 512, 1, 512)
+        for j in range(7):
+            conv(p + f"res2net_block.blocks.{j}.conv", 64, 3, 64)
+        conv(p + "tdnn2.conv", 512, 1, 512)
+        conv(p + "se_block.conv1", 128, 1, 512)
+        conv(p + "se_block.conv2", 512, 1, 128)
+    conv("mfa.conv", 1536, 1, 1536)
+    conv("asp.tdnn.conv", 128, 1, 4608)
+    conv("asp.conv", 1536, 1, 128)
+    conv("fc", int(embedding_dim), 1, 3072)
+    return s
+
+
+def synth_tts_speaker_encoder_state_dict(seed: int = 0, embedding_dim: int = 1024) -> dict:
+    """Seeded speaker-encoder weights {key: float32 array}: every matrix N(0, 1 / fan_in) times a gain (sqrt 2 in front of a ReLU, 0.25
+    for the initial conv, whose input is log-mel of several units), so activations stay O(1) through the three residual blocks, the
+    squeeze-excitation gates sit around one half and the attention logits spread over a few units; small biases."""
+    rng = np.random.default_rng(88117 + seed)
+    sd = {}
+    for key, shape in tts_speaker_encoder_tensor_shapes(embedding_dim).items():
+        if key.endswith(".bias"):
+            sd[key] = 0.05 * rng.standard_normal(shape)
+            continue
+        fan = shape[1] * shape[2]
+        if key.startswith("blocks.0."):
+            gain = 0.25
+        elif "se_block" in key or key.startswith("asp.") or key.startswith("fc."):
+            gain = 1.0
+        else:
+            gain = math.sqrt(2.0)
+        if key.startswith("asp.conv"):
+            gain = 3.0                                                 # tanh outputs are below one: logits a few units apart
+        sd[key] = gain * rng.standard_normal(shape) / math.sqrt(fan)
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in sd.items()}
+
+
+def write_tts_speaker_encoder_safetensors(sd: dict, model_dir: str, dtype: str = "F32", drop=(), reshape=None, extra=()) -> str:
+    """Writes `sd` under `speaker_encoder.` keys as model_dir/model.safetensors (dtype F32 | F16 | BF16; F64 for the dtype error).
+    `drop`: written keys left out, `reshape`: {written key: shape} written with a wrong shape, `extra`: (key, array) pairs added as they
+    are (the main checkpoint's other tensors, e.g. talker.*).  Returns model_dir."""
+    d = {"speaker_encoder." + k: v for k, v in sd.items()}
+    for k, v in (extra.items() if isinstance(extra, dict) else extra):
+        d[k] = np.asarray(v, dtype=np.float32)
+    _write_safetensors(d, model_dir, dtype, drop, reshape)
+    return model_dir
