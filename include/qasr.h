@@ -817,6 +817,76 @@ int qasr_xvec_embed_mel(qasr_xvec* x, const float* mel, size_t T, float* out);
 /* ms[6]: device time of the last call, HIP events on the work stream: front end, initial conv, blocks 1..3, MFA + pooling + fc */
 int qasr_xvec_timing(const qasr_xvec* x, float* ms);
 
+/* ---- Qwen3-TTS Talker + code predictor (Sources/Qwen3TTS/Talker.swift, CodePredictor.swift, Sampling.swift, Qwen3TTS.swift) -------------
+ * Text ids (the chat template of prepareTextTokens around them), a language id, optionally a speaker token id or an x-vector (qasr_xvec_*)
+ * and an instruct prefix -> 16 code streams at 12.5 Hz, which qasr_codec_decode turns into 24 kHz audio.  MLX affine 4 / 8 bit
+ * checkpoints only (keys talker.* and talker.code_predictor.* in any *.safetensors of the directory); a float checkpoint is refused.
+ * Rows of a call are independent: own prompt length, position, trailing text, history and finished flag; a row's codes are the same
+ * bits alone, in any batch, at any slot and under any max_batch.  One object, one thread at a time.
+ * HBM: the packed weights (0.6B 4-bit: about 0.5 GB with the bf16 embedding tables) plus the Talker KV cache, 2 images x layers x
+ * kv_heads x head_dim x 2 bytes x positions per row: 28 x 8 x 128 x 2 x 2 = 114,688 bytes per position; positions = max_instruct + 11
+ * prompt + max_frames + 1, rounded up to 32 (544 by default; the 510 a row can reach are 3.8 GB of it at max_batch 64, the allocation 4.0 GB).
+ * Not covered: ICL voice cloning, streaming, top_p < 1, the text tokenizer. */
+typedef struct qasr_tts qasr_tts;
+typedef struct qasr_tts_config {
+    int32_t hidden, layers, heads, kv_heads, head_dim, inter;          /* Talker: 1024 28 16 8 128 3072 (1.7B: 2048 .. 6144) */
+    int32_t text_vocab, text_hidden, codec_vocab;                      /* 151936 2048 3072 */
+    int32_t cp_hidden, cp_embedding_dim, cp_layers, cp_heads, cp_kv_heads, cp_head_dim, cp_inter, cp_vocab;   /* 1024 1024 5 16 8 128 3072 2048 */
+    float rms_eps, rope_theta, cp_rms_eps, cp_rope_theta;              /* 1e-6 1e6 1e-6 1e6 */
+    int32_t bits, group_size;                                          /* 4 | 8, 64 */
+    int32_t codec_pad, codec_bos, codec_eos, codec_think, codec_nothink, codec_think_bos, codec_think_eos;   /* 2148 2149 2150 2154 2155 2156 2157 */
+    int32_t suppress_lo, suppress_hi;                                  /* [2048, 3072): never sampled, except codec_eos */
+    int32_t tts_pad, tts_bos, tts_eos;                                 /* text side: 151671 151672 151673 */
+    int32_t max_batch;                                                 /* rows of one call, 1 .. 64 (default 8) */
+    int32_t max_frames;                                                /* 1 .. 500 (default and cap: the reference's safeMaxTokens) */
+    int32_t max_text, max_instruct;                                    /* ids per row (defaults 512, 0) */
+    int32_t device;
+} qasr_tts_config;
+typedef struct qasr_tts_sampling {          /* SamplingConfig (Sampling.swift:5-30); minP is declared and never read there: no field */
+    float temperature;                      /* 0.9; <= 0: greedy (the first maximum) */
+    int32_t top_k;                          /* 50; <= 0 or >= vocabulary: off */
+    float top_p;                            /* 1.0; < 1 is refused (QASR_ERR_UNSUPPORTED): the reference's branch masks the likeliest tokens */
+    float repetition_penalty;               /* 1.05; 1.0 = the reference's batch path */
+    int32_t max_tokens;                     /* frames, capped by the handle's max_frames; <= 0: max_frames */
+    float eos_logit_bias;                   /* 0 */
+} qasr_tts_sampling;
+typedef struct qasr_tts_request {
+    size_t B;
+    const int32_t* const* text; const int32_t* text_len;        /* [B]: templated ids, at least 9 */
+    const int32_t* language;                                    /* [B]: codec language ids */
+    const int32_t* speaker;                                     /* [B] or NULL; < 0: none */
+    const float* const* xvector;                                /* [B] or NULL; NULL entry: none; `hidden` floats each */
+    const int32_t* const* instruct; const int32_t* instruct_len;/* [B] or NULL; prepareInstructTokens' ids */
+    const int64_t* row_index;                                   /* [B] or NULL (0 .. B-1): the caller's index of the row, which keys its random stream */
+} qasr_tts_request;
+/* model: "0.6B" | "1.7B" (or a model id containing "1.7B"), bits 4 | 8: Qwen3TTSConfig.config(for:bits:) with the CodecTokens ids */
+int qasr_tts_default_config(const char* model, int bits, qasr_tts_config* out);
+void qasr_tts_default_sampling(int greedy, qasr_tts_sampling* out);
+/* missing file or key -> QASR_ERR_IO; wrong shape / dtype, a float checkpoint, a geometry the kernels do not serve (widths not multiples
+ * of 64, head_dim != 128, heads != 2 kv_heads, cp_embedding_dim != hidden, vocabularies over 4096 codes) -> QASR_ERR_INVALID */
+int qasr_tts_create(const char* model_dir, const qasr_tts_config* cfg, qasr_tts** out);
+void qasr_tts_free(qasr_tts* t);
+const char* qasr_tts_last_error(const qasr_tts* t);                /* t may be NULL: last create() failure */
+size_t qasr_tts_memory_footprint(const qasr_tts* t);               /* parameter bytes as stored */
+size_t qasr_tts_device_bytes(const qasr_tts* t);                   /* every device allocation of the handle */
+int qasr_tts_poll_interval(void);                                  /* frames between two host reads of the finished flags (8) */
+/* codes [B][16][max_frames] int32 (max_frames = the handle's; entries past n_frames[b] are -1), n_frames [B].  A row whose first token
+ * is EOS has 0 frames.  B > max_batch -> QASR_ERR_CAPACITY; a text shorter than 9 ids, an id outside its vocabulary, a NULL buffer ->
+ * QASR_ERR_INVALID; too many text / instruct ids -> QASR_ERR_CAPACITY; top_p < 1 -> QASR_ERR_UNSUPPORTED. */
+int qasr_tts_generate(qasr_tts* t, const qasr_tts_request* rq, const qasr_tts_sampling* s, uint64_t seed, int32_t* codes, int32_t* n_frames);
+/* teacher-forced pass: forced codes [B][16][T], T <= max_frames -> talker_logits [B][T][codec_vocab], cp_logits [B][T][15][cp_vocab],
+ * hidden [B][T][hidden] (post-norm), any of them NULL.  No sampling decides what is fed. */
+int qasr_tts_forced(qasr_tts* t, const qasr_tts_request* rq, const int32_t* codes, size_t T, float* talker_logits, float* cp_logits,
+                    float* hidden);
+/* the host twin of the device sampler on one row of logits [V]: talker != 0 applies the suppress range, the penalty over history[n_history]
+ * and the EOS rules with cfg's ids (cfg NULL: the defaults), else sampleTokenLazy.  Returns the token or -status.  Pure CPU. */
+int qasr_tts_sample_host(const qasr_tts_config* cfg, const float* logits, int32_t V, int talker, const qasr_tts_sampling* s,
+                         const int32_t* history, int32_t n_history, uint64_t seed, int64_t row_index, int32_t frame, int32_t group);
+/* generate, then the caller's codec handle: pcm[b] holds 1920 x max_frames floats, n_samples[b] = 1920 x n_frames[b] of them are written.
+ * codes / n_frames as qasr_tts_generate, may be NULL. */
+int qasr_tts_synthesize(qasr_tts* t, qasr_codec* codec, const qasr_tts_request* rq, const qasr_tts_sampling* s, uint64_t seed,
+                        float* const* pcm, size_t* n_samples, int32_t* codes, int32_t* n_frames);
+
 /* transducer greedy loops (pure CPU).  The caller owns the networks and their state:
  *   decoder_step(ctx, token)  advance the prediction network with `token` (the loops prime it with the blank id where the reference does)
  *   joint(ctx, frame, token_logits[vocab_size + 1], duration_logits[n_durations] or NULL)  logits for encoder frame `frame` and the

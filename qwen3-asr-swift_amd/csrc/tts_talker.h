@@ -1,0 +1,131 @@
+// tts_talker.h -- the Qwen3-TTS Talker and code predictor on the device (kernels and host object in tts_talker.hip, host sampler twin in
+// tts_sampler.cpp, C ABI in api_tts.cpp): text ids + language (+ speaker token | x-vector, + instruct ids) -> 16 code streams at 12.5 Hz.
+//
+// Reference: Sources/Qwen3TTS/Talker.swift, CodePredictor.swift, Sampling.swift, Qwen3TTS.swift (buildCodecPrefix, buildPrefillEmbeddings,
+// generateWithCodePredictor, predictCodebooksForTimestep), TTSWeightLoading.swift:24-158 (keys).  MLX affine 4 / 8 bit Linears stay packed
+// (dec_quant.h); bf16 activations between layers, f32 accumulation, f32 norms / softmax / logits.  Nothing here is shared with the Engine
+// class: the layer GEMVs and the Talker's attention are the decode step's launch functions (decode_gemv_q_launch,
+// decode_attention_launch), everything else is in tts_talker.hip.  DESIGN.md section 18.
+#pragma once
+#include "engine.h"
+#include "dec_quant.h"
+#include "safetensors.h"
+#include "qasr.h"
+#include <map>
+#include <memory>
+#include <set>
+#include <string>
+#include <vector>
+
+namespace qasr {
+
+constexpr int TTS_GROUPS = 16;          // code streams of a frame: code 0 from the Talker, 1 .. 15 from the code predictor
+constexpr int TTS_MAX_FRAMES = 500;     // the reference's safeMaxTokens (Qwen3TTS.swift:1407)
+constexpr int TTS_POLL = 8;             // frames between two host reads of the finished flags
+constexpr int TTS_MAX_VOCAB = 4096;     // logits of one sampler workgroup (LDS image)
+constexpr int TTS_TEMPLATE = 9;         // <|im_start|>assistant\n ... <|im_end|>\n<|im_start|>assistant\n
+
+// ---- the sampler, stated once for the device kernel and the host twin (tts_sampler.cpp) ------------------------------------------
+struct TtsSampleParams {
+    float temperature, repetition_penalty, eos_logit_bias;
+    int top_k;
+    int suppress_lo, suppress_hi, eos;   // Talker mode only (eos < 0: code-predictor mode, steps 1, 2, 5, 7 are skipped)
+    unsigned long long seed;
+};
+// the random stream: counter-based splitmix64; the counter depends on (seed, caller row, frame, group, vocabulary index) only
+__host__ __device__ inline unsigned long long tts_splitmix64(unsigned long long z) {
+    z += 0x9e3779b97f4a7c15ull;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+__host__ __device__ inline unsigned long long tts_stream_key(unsigned long long seed, long long row, int frame, int group) {
+    const unsigned long long a = tts_splitmix64(seed ^ 0x5174735454533031ull);
+    const unsigned long long b = tts_splitmix64(a + (unsigned long long)row);
+    return tts_splitmix64(b + (((unsigned long long)(unsigned)frame) << 8) + (unsigned long long)group);
+}
+// u in [1e-6, 1] as dec_sampler.hip draws it
+__host__ __device__ inline float tts_uniform(unsigned long long key, int i) {
+    const double r = (double)(tts_splitmix64(key + (unsigned long long)i) >> 11) * (1.0 / 9007199254740992.0);
+    return (float)(1e-6 + r * (1.0 - 1e-6));
+}
+// sampleToken / sampleTokenLazy (Sampling.swift:36-160) on one row of f32 logits; `seen` [V] marks the row's distinct code-0 history (may be
+// null); returns the token.  Pure host code.
+int tts_sample_host(const float* logits, int V, const TtsSampleParams& p, const unsigned char* seen, long long row, int frame, int group);
+
+struct TtsRow {                         // one row of a request, checked by the C ABI
+    const int32_t* text; int n_text;
+    int language, speaker;              // speaker < 0: none
+    const float* xvector;               // [hidden] or null
+    const int32_t* instruct; int n_instruct;
+    long long index;                    // the caller's row index (random stream)
+};
+
+struct TtsForcedOut {                   // qasr_tts_forced: any pointer may be null
+    const int32_t* codes; int T;        // [B][16][T]
+    float* talker_logits;               // [B][T][codec_vocab]
+    float* cp_logits;                   // [B][T][15][cp_vocab]
+    float* hidden;                      // [B][T][hidden]
+};
+
+class TtsTalker {
+  public:
+    // every key, shape and dtype is checked on the host before any HIP call (WeightLoadError); `cfg` is complete (api_tts.cpp)
+    TtsTalker(const qasr_tts_config& cfg, const SafeTensorsDir& st);
+    ~TtsTalker();
+    const qasr_tts_config& config() const { return cfg_; }
+    size_t footprint() const { return param_bytes_; }
+    size_t device_bytes() const { return device_bytes_; }
+    // codes [B][16][max_frames] (row stride 16 * max_frames), n_frames [B]
+    void generate(const std::vector<TtsRow>& rows, const qasr_tts_sampling& s, unsigned long long seed, int max_frames, int32_t* codes,
+                  int32_t* n_frames);
+    void forced(const std::vector<TtsRow>& rows, const TtsForcedOut& f);
+    static void check_geometry(const qasr_tts_config& c);      // std::invalid_argument for what the kernels do not serve
+    struct Knobs;                        // device-side per-call values (tts_talker.hip)
+
+  private:
+    struct QLin { QuantImg img; const float* bias = nullptr; int N = 0, K = 0; };
+    struct Layer { QLin qkv, o, gu, down; const bf16_t *ln1, *ln2, *qn, *kn; };
+    struct Net { std::vector<Layer> layers; const bf16_t* norm = nullptr; int H, heads, kv, hd, I; float eps; };
+    QLin load_qlin(const SafeTensorsDir& st, const std::vector<std::string>& stems, int K, bool bias, int interleave);
+    const bf16_t* load_bf16(const SafeTensorsDir& st, const std::string& key, std::vector<int64_t> shape);
+    void load_net(const SafeTensorsDir& st, const std::string& prefix, Net& n, int layers);
+    void load_all(const SafeTensorsDir& st);
+    void* dev_upload(const void* src, size_t bytes);
+    void prefill(const std::vector<TtsRow>& rows);
+    void layer_steps(const Net& n, bf16_t* x, int B, bool talker, int cp_pos, bool kv_only_last);
+    void issue_frame(int B, bool forced_mode);
+    void run_frame(int B);
+    void set_knobs(const qasr_tts_sampling& s, unsigned long long seed);
+    void drop_graphs();
+
+    qasr_tts_config cfg_;
+    bool dry_ = false;                   // load_all checks on the host only
+    hipStream_t stream_ = nullptr;
+    size_t param_bytes_ = 0, device_bytes_ = 0;
+    std::vector<std::unique_ptr<DevBuf>> bufs_;
+    Net tk_, cp_;
+    QLin head_, fc1_, fc2_, proj_, lm_[TTS_GROUPS - 1];
+    const bf16_t *codec_emb_ = nullptr, *text_emb_ = nullptr, *cp_emb_[TTS_GROUPS - 1] = {};
+    const bf16_t** d_cp_emb_ = nullptr;
+    int max_ctx_ = 0, max_prefill_ = 0, max_tp_ = 0;
+    float *d_rope_cos_ = nullptr, *d_rope_sin_ = nullptr, *d_cp_cos_ = nullptr, *d_cp_sin_ = nullptr, *d_rope_rows_ = nullptr;
+    bf16_t *d_k_ = nullptr, *d_vf_ = nullptr, *d_cpk_ = nullptr, *d_cpv_ = nullptr;
+    bf16_t *d_x_ = nullptr, *d_hn_ = nullptr, *d_qkv_ = nullptr, *d_attn_ = nullptr, *d_act_ = nullptr, *d_scratch_ = nullptr;
+    bf16_t *d_cpa_ = nullptr, *d_cpb_ = nullptr, *d_cx_ = nullptr, *d_chn_ = nullptr;
+    bf16_t *d_tp_in_ = nullptr, *d_tp_mid_ = nullptr, *d_tp_ = nullptr, *d_pf_ = nullptr;
+    float *d_logits_ = nullptr, *d_cp_logits_ = nullptr, *d_xvec_ = nullptr;
+    int *d_state_ = nullptr, *d_codes_ = nullptr, *d_tp_ids_ = nullptr, *d_pf_text_ = nullptr, *d_pf_codec_ = nullptr, *d_trail_ = nullptr;
+    long long* d_row_index_ = nullptr;
+    unsigned char* d_seen_ = nullptr;
+    Knobs* d_knobs_ = nullptr;
+    float *d_f_tlog_ = nullptr, *d_f_cplog_ = nullptr, *d_f_hid_ = nullptr;    // forced-pass outputs (sized per call)
+    int* d_f_codes_ = nullptr;
+    int forced_T_host_ = 0;
+    std::unique_ptr<DevBuf> forced_buf_[4];
+    std::map<int, hipGraphExec_t> graphs_;                    // the frame's launch sequence per batch size
+    std::set<int> warmed_;                                     // batch sizes whose first frame ran eagerly (kernel attributes are set outside a capture)
+    unsigned graph_epoch_ = 0;
+};
+
+}  // namespace qasr

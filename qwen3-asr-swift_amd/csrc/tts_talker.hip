@@ -1,0 +1,929 @@
+// tts_talker.hip -- the Qwen3-TTS Talker and code predictor (declarations and references: tts_talker.h).
+//
+// A frame for all rows is one linear sequence of launches on one stream, captured once per batch size and replayed per frame; what
+// changes between calls (sampling values, seed) lives in a device-side Knobs record, what changes between frames (position, frame
+// index, finished flags) in per-row device state.  New kernels of this file: the code predictor's attention over its <= 16 cached
+// positions (the frame's K / V of a head staged in LDS), the sampler (with the gather of the next code-predictor input fused behind
+// the pick), the embedding sum that builds the next Talker input, the prefill embedding builder, and a wave-per-column quantised
+// GEMV with f32 output for the heads and the biased projections.  The layer GEMVs and the Talker's attention are the decode step's.
+#include "tts_talker.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+namespace qasr {
+
+struct TtsState { int *ctx_len, *finished, *n_frames, *frame_of, *trail_len, *pf_len; };
+struct TtsTalker::Knobs { TtsSampleParams talker, cp; };
+
+// ------------------------------------------------------------------------------------------------
+// y[r][n] = act(sum_g (scale * sum q x + bias * sum x) + b[n]): one wave per output column, eight batch rows per workgroup share the
+// decoded weights.  A lane owns the 8-element chunks lane, lane + 64, ... of the row (chunk c lies in group c / 8) and adds
+// scale * dot + bias * xsum of each to its f32 partial; the 64 partials are summed by wave_sum.  The order does not depend on R.
+// ------------------------------------------------------------------------------------------------
+template <bool SILU>
+__global__ __launch_bounds__(256) void tts_gemv_rows_kernel(QuantRaw q, const bf16_t* __restrict__ X, int R, const float* __restrict__ bias,
+                                                            float* __restrict__ outf, bf16_t* __restrict__ outb, long ldo) {
+    const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6), r0 = blockIdx.y * 8;
+    if (n >= q.N) return;
+    const int nch = q.K / 8, G = q.K / 64;
+    float acc[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) acc[r] = 0.0f;
+    for (int c = lane; c < nch; c += 64) {
+        unsigned e[8];
+        if (q.bits == 4) {
+            const uint32_t w = q.wq[(long)n * nch + c];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) e[j] = (w >> (4 * j)) & 0xFu;
+        } else {
+            const uint2 w = *reinterpret_cast<const uint2*>(q.wq + (long)n * (q.K / 4) + 2 * c);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { e[j] = (w.x >> (8 * j)) & 0xFFu; e[4 + j] = (w.y >> (8 * j)) & 0xFFu; }
+        }
+        const long gi = (long)n * G + (c >> 3);
+        const float s = q.sb_f32 ? reinterpret_cast<const float*>(q.scales)[gi] : bf16_to_f32(reinterpret_cast<const bf16_t*>(q.scales)[gi]);
+        const float b = q.sb_f32 ? reinterpret_cast<const float*>(q.biases)[gi] : bf16_to_f32(reinterpret_cast<const bf16_t*>(q.biases)[gi]);
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            if (r0 + r >= R) break;
+            const uint4 xv = *reinterpret_cast<const uint4*>(X + (long)(r0 + r) * q.K + (long)c * 8);
+            const bf16_t* xe = reinterpret_cast<const bf16_t*>(&xv);
+            float dot = 0.0f, xs = 0.0f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float x = bf16_to_f32(xe[j]);
+                dot = fmaf((float)e[j], x, dot);
+                xs += x;
+            }
+            acc[r] += s * dot + b * xs;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        if (r0 + r >= R) break;
+        float v = wave_sum(acc[r]);
+        if (lane == 0) {
+            if (bias) v += bias[n];
+            if (SILU) v = v / (1.0f + expf(-v));
+            if (outf) outf[(long)(r0 + r) * ldo + n] = v;
+            else outb[(long)(r0 + r) * ldo + n] = f32_to_bf16(v);
+        }
+    }
+}
+
+static void gemv_rows(const QuantRaw& q, const bf16_t* X, int R, const float* bias, float* outf, bf16_t* outb, long ldo, bool silu,
+                      hipStream_t s) {
+    if (R <= 0) return;
+    const dim3 grid(cdiv(q.N, 4), cdiv(R, 8));
+    if (silu) hipLaunchKernelGGL(tts_gemv_rows_kernel<true>, grid, dim3(256), 0, s, q, X, R, bias, outf, outb, ldo);
+    else hipLaunchKernelGGL(tts_gemv_rows_kernel<false>, grid, dim3(256), 0, s, q, X, R, bias, outf, outb, ldo);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Code-predictor attention at position pos (0 .. 15) of the frame: one wave per (kv head, batch row).  The head's cached keys and values
+// of positions < pos go to LDS (at most 2 x 16 x 128 bf16 = 8 KiB), the token's own k (q/k RMSNorm + RoPE at the rounding points of
+// dec_rope.h) and v are appended to LDS and to the cache, then every query head of the kv head: scores in f32 (lane d owns the pair
+// d, d + 64; sum over the wave), f32 softmax, p . V in f32 in ascending key order, one rounding to bf16.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void tts_cp_attn_kernel(const bf16_t* __restrict__ qkv, int pos, int heads, int kv_heads,
+                                                         const bf16_t* __restrict__ qn, const bf16_t* __restrict__ kn, float eps,
+                                                         const float* __restrict__ cos_t, const float* __restrict__ sin_t,
+                                                         bf16_t* __restrict__ kc, bf16_t* __restrict__ vc, bf16_t* __restrict__ out, float scale) {
+    constexpr int HD = 128, HALF = 64, MAXP = TTS_GROUPS;
+    __shared__ bf16_t s_k[MAXP][HD], s_v[MAXP][HD];
+    const int kvh = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
+    const int rep = heads / kv_heads, nh = heads + 2 * kv_heads;
+    const bf16_t* row = qkv + (long)b * nh * HD;
+    bf16_t* kb = kc + ((long)b * kv_heads + kvh) * MAXP * HD;
+    bf16_t* vb = vc + ((long)b * kv_heads + kvh) * MAXP * HD;
+    for (int j = 0; j < pos; ++j) {
+        s_k[j][lane] = kb[j * HD + lane];
+        s_k[j][lane + HALF] = kb[j * HD + lane + HALF];
+        s_v[j][lane] = vb[j * HD + lane];
+        s_v[j][lane + HALF] = vb[j * HD + lane + HALF];
+    }
+    const float c = cos_t[pos * HALF + lane], sn = sin_t[pos * HALF + lane];
+    {
+        const bf16_t* src = row + (long)(heads + kvh) * HD;
+        const float x1 = bf16_to_f32(src[lane]), x2 = bf16_to_f32(src[lane + HALF]);
+        const float inv = rsqrtf(lane_sum<64>(x1 * x1 + x2 * x2) / (float)HD + eps);
+        float o1, o2;
+        norm_rope_pair(x1, x2, bf16_to_f32(kn[lane]), bf16_to_f32(kn[lane + HALF]), inv, c, sn, o1, o2);
+        const bf16_t k1 = f32_to_bf16(o1), k2 = f32_to_bf16(o2);
+        s_k[pos][lane] = k1; s_k[pos][lane + HALF] = k2;
+        kb[pos * HD + lane] = k1; kb[pos * HD + lane + HALF] = k2;
+        const bf16_t* vs = row + (long)(heads + kv_heads + kvh) * HD;
+        const bf16_t v1 = vs[lane], v2 = vs[lane + HALF];
+        s_v[pos][lane] = v1; s_v[pos][lane + HALF] = v2;
+        vb[pos * HD + lane] = v1; vb[pos * HD + lane + HALF] = v2;
+    }
+    __syncthreads();
+    for (int r = 0; r < rep; ++r) {
+        const int h = kvh * rep + r;
+        const bf16_t* src = row + (long)h * HD;
+        const float x1 = bf16_to_f32(src[lane]), x2 = bf16_to_f32(src[lane + HALF]);
+        const float inv = rsqrtf(lane_sum<64>(x1 * x1 + x2 * x2) / (float)HD + eps);
+        float q1, q2;
+        norm_rope_pair(x1, x2, bf16_to_f32(qn[lane]), bf16_to_f32(qn[lane + HALF]), inv, c, sn, q1, q2);
+        float sc[MAXP], m = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < MAXP; ++j) {
+            sc[j] = -INFINITY;
+            if (j <= pos) {
+                sc[j] = lane_sum<64>(q1 * bf16_to_f32(s_k[j][lane]) + q2 * bf16_to_f32(s_k[j][lane + HALF])) * scale;
+                m = fmaxf(m, sc[j]);
+            }
+        }
+        float l = 0.0f, o1 = 0.0f, o2 = 0.0f;
+#pragma unroll
+        for (int j = 0; j < MAXP; ++j) {
+            if (j <= pos) {
+                const float p = expf(sc[j] - m);
+                l += p;
+                o1 += p * bf16_to_f32(s_v[j][lane]);
+                o2 += p * bf16_to_f32(s_v[j][lane + HALF]);
+            }
+        }
+        bf16_t* dst = out + ((long)b * heads + h) * HD;
+        dst[lane] = f32_to_bf16(o1 / l);
+        dst[lane + HALF] = f32_to_bf16(o2 / l);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The sampler: one workgroup per batch row, the row's logits in LDS.  Steps as tts_sampler.cpp (the host twin) numbers them.  Top-k's
+// threshold, the k-th largest value, is found exactly by bisection over the 32 bits of an order-preserving integer key (count of
+// keys >= candidate, one barrier per bit).  Behind the pick: the code is stored (Talker: EOS finishes the row instead), and the
+// embedding row of the picked token is gathered as the next code-predictor input (Talker: the hidden state is copied next to it).
+// ------------------------------------------------------------------------------------------------
+struct TtsSampleArgs {
+    const float* logits; int V;
+    int group;                          // code stream 0 .. 15; 0 = the Talker's
+    const TtsTalker::Knobs* knobs;
+    TtsState st;
+    unsigned char* seen;                // [B][V], Talker only
+    const long long* row_index;
+    int* codes; int stride;             // [B][16][stride]
+    const int* forced; int forced_T;    // [B][16][T] or null
+    const bf16_t* emb; int E;           // [V][E]
+    bf16_t* emb_out;                    // [B][E]
+    const bf16_t* hn; bf16_t* hn_out;   // [B][E] or null
+};
+
+__device__ __forceinline__ unsigned tts_order_key(float v) {
+    const unsigned u = __float_as_uint(v + 0.0f);                      // -0 -> +0: the host compares values
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// first maximum of the workgroup's (value, index) pairs; every thread passes its own best with the lowest index among equals
+__device__ __forceinline__ int tts_block_argmax(float v, int i, float* r_v, int* r_i) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(v, o, 64);
+        const int oi = __shfl_xor(i, o, 64);
+        if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+    }
+    __syncthreads();
+    if ((tid & 63) == 0) { r_v[tid >> 6] = v; r_i[tid >> 6] = i; }
+    __syncthreads();
+    float bv = r_v[0];
+    int bi = r_i[0];
+    for (int w = 1; w < 16; ++w)
+        if (r_v[w] > bv || (r_v[w] == bv && r_i[w] < bi)) { bv = r_v[w]; bi = r_i[w]; }
+    return bi;
+}
+
+__global__ __launch_bounds__(1024) void tts_sample_kernel(TtsSampleArgs a) {
+    __shared__ float s_v[TTS_MAX_VOCAB];
+    __shared__ float r_v[16];
+    __shared__ int r_i[16], s_cnt[2][16];
+    const int b = blockIdx.x, tid = threadIdx.x, V = a.V;
+    const bool talker = a.group == 0;
+    const TtsSampleParams p = talker ? a.knobs->talker : a.knobs->cp;
+    const int frame = a.st.frame_of[b];
+    const bool fin = a.st.finished[b] != 0;
+    const float* row = a.logits + (long)b * V;
+    for (int i = tid; i < V; i += 1024) {
+        float v = row[i];
+        if (talker) {
+            if (i >= p.suppress_lo && i < p.suppress_hi && i != p.eos) v = -1e9f;                                      // 1
+            if (p.repetition_penalty != 1.0f && a.seen[(long)b * V + i])                                                // 2
+                v = v < 0.0f ? v * p.repetition_penalty : v / p.repetition_penalty;
+        }
+        s_v[i] = v;
+    }
+    __syncthreads();
+    int tok;
+    if (a.forced) {
+        tok = a.forced[((long)b * TTS_GROUPS + a.group) * a.forced_T + frame];
+    } else if (p.temperature <= 0.0f) {                                                                                 // 3
+        float bv = -INFINITY;
+        int bi = 0x7fffffff;
+        for (int i = tid; i < V; i += 1024)
+            if (s_v[i] > bv || bi == 0x7fffffff) { bv = s_v[i]; bi = i; }
+        tok = tts_block_argmax(bv, bi, r_v, r_i);
+    } else {
+        float val[TTS_MAX_VOCAB / 1024];
+        unsigned key[TTS_MAX_VOCAB / 1024];
+#pragma unroll
+        for (int e = 0; e < TTS_MAX_VOCAB / 1024; ++e) {
+            const int i = tid + e * 1024;
+            val[e] = i < V ? s_v[i] / p.temperature : 0.0f;                                                            // 4
+            key[e] = i < V ? tts_order_key(val[e]) : 0u;                // 0 is below every real key
+        }
+        const bool eos_ok = talker && p.eos < V;
+        const float eos_saved = eos_ok ? s_v[p.eos] / p.temperature : 0.0f;                                            // 5
+        if (p.top_k > 0 && p.top_k < V) {                                                                               // 6
+            unsigned prefix = 0u;
+            for (int bit = 31; bit >= 0; --bit) {
+                const unsigned cand = prefix | (1u << bit);
+                int c = 0;
+#pragma unroll
+                for (int e = 0; e < TTS_MAX_VOCAB / 1024; ++e) c += key[e] >= cand ? 1 : 0;
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+                if ((tid & 63) == 0) s_cnt[bit & 1][tid >> 6] = c;
+                __syncthreads();
+                int total = 0;
+                for (int w = 0; w < 16; ++w) total += s_cnt[bit & 1][w];
+                if (total >= p.top_k) prefix = cand;
+            }
+#pragma unroll
+            for (int e = 0; e < TTS_MAX_VOCAB / 1024; ++e)
+                if (key[e] < prefix) val[e] = -1e9f;
+        }
+        const unsigned long long skey = tts_stream_key(p.seed, a.row_index[b], frame, a.group);
+        float bv = -INFINITY;
+        int bi = 0x7fffffff;
+#pragma unroll
+        for (int e = 0; e < TTS_MAX_VOCAB / 1024; ++e) {
+            const int i = tid + e * 1024;
+            if (i >= V) continue;
+            float v = val[e];
+            if (eos_ok && i == p.eos) v = p.eos_logit_bias != 0.0f ? eos_saved + p.eos_logit_bias : eos_saved;          // 7
+            v = v - logf(-logf(tts_uniform(skey, i)));                                                                 // 8
+            if (v > bv || bi == 0x7fffffff) { bv = v; bi = i; }
+        }
+        tok = tts_block_argmax(bv, bi, r_v, r_i);
+    }
+    if (tok < 0 || tok >= V) tok = 0;                                   // all-NaN logits: keep the gather inside its table
+    if (tid == 0 && !fin) {
+        if (talker && !a.forced && tok == p.eos) {
+            a.st.finished[b] = 1;
+            a.st.n_frames[b] = frame;
+        } else {
+            a.codes[((long)b * TTS_GROUPS + a.group) * a.stride + frame] = tok;
+            if (talker) a.seen[(long)b * V + tok] = 1;
+        }
+    }
+    for (int i = tid; i < a.E; i += 1024) {
+        a.emb_out[(long)b * a.E + i] = a.emb[(long)tok * a.E + i];
+        if (a.hn_out) a.hn_out[(long)b * a.E + i] = a.hn[(long)b * a.E + i];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The next Talker input of a row: text side (the row's next trailing text embedding, tts_pad once they ran out) + codec_embedding(code 0)
+// + the 15 code-predictor embeddings, added in that order in f32, rounded once to bf16.  Then the row's state moves on: position and
+// frame count unless it is finished, the frame index always, and the RoPE row of the new position for the Talker's attention.
+// ------------------------------------------------------------------------------------------------
+struct TtsNextArgs {
+    TtsState st;
+    const int* codes; int stride;
+    const int* forced; int forced_T;
+    const bf16_t* tp; const int* trail; int max_trail;
+    const bf16_t* codec_emb; const bf16_t* const* cp_emb;
+    int H, codec_vocab, cp_vocab;
+    bf16_t* x;
+    const float *cos_t, *sin_t;
+    float *cos_rows, *sin_rows;
+    int half;
+};
+
+__global__ __launch_bounds__(256) void tts_next_input_kernel(TtsNextArgs a) {
+    __shared__ int s_c[TTS_GROUPS];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int frame = a.st.frame_of[b], ctx = a.st.ctx_len[b];
+    const bool fin = a.st.finished[b] != 0;
+    if (tid < TTS_GROUPS) {
+        int c = a.forced ? a.forced[((long)b * TTS_GROUPS + tid) * a.forced_T + frame] : a.codes[((long)b * TTS_GROUPS + tid) * a.stride + frame];
+        const int lim = tid == 0 ? a.codec_vocab : a.cp_vocab;
+        s_c[tid] = (fin || c < 0 || c >= lim) ? 0 : c;                  // a finished row computes on, its values are never read
+    }
+    __syncthreads();
+    const int ti = frame < a.st.trail_len[b] ? a.trail[(long)b * a.max_trail + frame] : 0;      // row 0 of tp: tts_pad
+    for (int i = tid; i < a.H; i += 256) {
+        float s = bf16_to_f32(a.tp[(long)ti * a.H + i]);
+        s += bf16_to_f32(a.codec_emb[(long)s_c[0] * a.H + i]);
+        for (int g = 0; g < TTS_GROUPS - 1; ++g) s += bf16_to_f32(a.cp_emb[g][(long)s_c[g + 1] * a.H + i]);
+        a.x[(long)b * a.H + i] = f32_to_bf16(s);
+    }
+    const int nctx = fin ? ctx : ctx + 1;
+    for (int t = tid; t < a.half; t += 256) {
+        a.cos_rows[(long)b * a.half + t] = a.cos_t[(long)nctx * a.half + t];
+        a.sin_rows[(long)b * a.half + t] = a.sin_t[(long)nctx * a.half + t];
+    }
+    if (tid == 0) {
+        if (!fin) { a.st.ctx_len[b] = nctx; a.st.n_frames[b] = frame + 1; }
+        a.st.frame_of[b] = frame + 1;
+    }
+}
+
+// ---- prefill: text rows gathered for the text projection, the prompt assembled, one prompt position fed per step ------------------
+__global__ __launch_bounds__(256) void tts_gather_rows_kernel(const bf16_t* __restrict__ table, const int* __restrict__ ids, int W,
+                                                              bf16_t* __restrict__ out) {
+    const long r = blockIdx.x;
+    for (int i = threadIdx.x; i < W; i += 256) out[r * W + i] = table[(long)ids[r] * W + i];
+}
+
+// pf[b][p] = bf16(text side + codec side): text side = tp[pf_text] (or nothing), codec side = codec_embedding[pf_codec] | the x-vector (-2)
+__global__ __launch_bounds__(256) void tts_prefill_build_kernel(const int* __restrict__ pf_text, const int* __restrict__ pf_codec, int P,
+                                                                const bf16_t* __restrict__ tp, const bf16_t* __restrict__ codec_emb,
+                                                                const float* __restrict__ xvec, int H, bf16_t* __restrict__ pf) {
+    const int p = blockIdx.x, b = blockIdx.y;
+    const int ti = pf_text[(long)b * P + p], ci = pf_codec[(long)b * P + p];
+    for (int i = threadIdx.x; i < H; i += 256) {
+        float s = ti >= 0 ? bf16_to_f32(tp[(long)ti * H + i]) : 0.0f;
+        if (ci >= 0) s += bf16_to_f32(codec_emb[(long)ci * H + i]);
+        else if (ci == -2) s += xvec[(long)b * H + i];
+        pf[((long)b * P + p) * H + i] = f32_to_bf16(s);
+    }
+}
+
+// step s of the prompt pass over prompts that END together: row b feeds its position s - (P - len[b]); before its first position it
+// recomputes position 0, which its real first step then overwrites
+__global__ __launch_bounds__(256) void tts_prefill_feed_kernel(TtsState st, int s, int P, const bf16_t* __restrict__ pf, int pf_ld, int H,
+                                                               bf16_t* __restrict__ x, const float* __restrict__ cos_t,
+                                                               const float* __restrict__ sin_t, float* __restrict__ cos_rows,
+                                                               float* __restrict__ sin_rows, int half) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int p = max(s - (P - st.pf_len[b]), 0);
+    for (int i = tid; i < H; i += 256) x[(long)b * H + i] = pf[((long)b * pf_ld + p) * H + i];
+    for (int t = tid; t < half; t += 256) {
+        cos_rows[(long)b * half + t] = cos_t[(long)p * half + t];
+        sin_rows[(long)b * half + t] = sin_t[(long)p * half + t];
+    }
+    if (tid == 0) st.ctx_len[b] = p;
+}
+
+// forced pass: src [B][W] (f32 or bf16) -> dst[b][frame_of[b]][slot] rows of a [B][T][slots][W] f32 array
+__global__ __launch_bounds__(256) void tts_copy_out_kernel(const float* __restrict__ srcf, const bf16_t* __restrict__ srcb, int W,
+                                                           const int* __restrict__ frame_of, int T, int slots, int slot,
+                                                           float* __restrict__ dst) {
+    const int b = blockIdx.x;
+    const long o = (((long)b * T + frame_of[b]) * slots + slot) * W;
+    for (int i = threadIdx.x; i < W; i += 256) dst[o + i] = srcf ? srcf[(long)b * W + i] : bf16_to_f32(srcb[(long)b * W + i]);
+}
+
+// ================================================================================================
+// host
+// ================================================================================================
+static const char* const WHO = "talker";
+
+void TtsTalker::check_geometry(const qasr_tts_config& c) {
+    auto bad = [](const std::string& m) { throw std::invalid_argument(std::string(WHO) + ": " + m); };
+    if (c.bits != 4 && c.bits != 8) bad("bits must be 4 or 8 (a float checkpoint is not served)");
+    if (c.group_size != 64) bad("only group size 64 is supported");
+    if (c.head_dim != 128 || c.cp_head_dim != 128) bad("head_dim must be 128 (the attention kernels are built for it)");
+    if (c.heads != 2 * c.kv_heads || c.kv_heads < 1) bad("the Talker needs 2 query heads per kv head");
+    if (c.cp_kv_heads < 1 || c.cp_heads % c.cp_kv_heads != 0) bad("cp_heads must be a multiple of cp_kv_heads");
+    for (int k : {c.hidden, c.inter, c.text_hidden, c.cp_hidden, c.cp_inter, c.cp_embedding_dim})
+        if (k < 64 || k % 64 != 0) bad("every GEMV width (K) must be a multiple of 64");
+    if (c.inter % 16 != 0 || c.cp_inter % 16 != 0) bad("intermediate sizes must be multiples of 16");
+    if (c.cp_embedding_dim != c.hidden) bad("cp_embedding_dim must equal the Talker's hidden size");
+    if (c.layers < 1 || c.cp_layers < 1) bad("layer counts must be positive");
+    if (c.codec_vocab < 1 || c.codec_vocab > TTS_MAX_VOCAB || c.cp_vocab < 1 || c.cp_vocab > TTS_MAX_VOCAB)
+        bad("codec_vocab and cp_vocab in 1..4096");
+    if (c.text_vocab < 1) bad("text_vocab must be positive");
+    for (int id : {c.codec_pad, c.codec_bos, c.codec_eos, c.codec_think, c.codec_nothink, c.codec_think_bos, c.codec_think_eos})
+        if (id < 0 || id >= c.codec_vocab) bad("a codec special id lies outside codec_vocab");
+    for (int id : {c.tts_pad, c.tts_bos, c.tts_eos})
+        if (id < 0 || id >= c.text_vocab) bad("a text-side special id lies outside text_vocab");
+    if (c.suppress_lo < 0 || c.suppress_hi > c.codec_vocab || c.suppress_lo > c.suppress_hi) bad("suppress range outside codec_vocab");
+    if (c.max_batch < 1 || c.max_batch > 64) bad("max_batch in 1..64");
+    if (c.max_frames < 1 || c.max_frames > TTS_MAX_FRAMES) bad("max_frames in 1..500");
+    if (c.max_text < TTS_TEMPLATE || c.max_text > 8192) bad("max_text in 9..8192");
+    if (c.max_instruct < 0 || c.max_instruct > 8192) bad("max_instruct in 0..8192");
+}
+
+void* TtsTalker::dev_upload(const void* src, size_t bytes) {
+    auto buf = std::make_unique<DevBuf>();
+    buf->alloc(bytes);
+    device_bytes_ += buf->bytes;
+    if (src) QASR_HIP(hipMemcpyAsync(buf->p, src, bytes, hipMemcpyHostToDevice, stream_));
+    void* p = buf->p;
+    bufs_.push_back(std::move(buf));
+    if (src) QASR_HIP(hipStreamSynchronize(stream_));     // src may be a temporary
+    return p;
+}
+
+static const SafeEntry& need(const SafeTensorsDir& st, const std::string& key) {
+    auto it = st.entries.find(key);
+    if (it == st.entries.end()) throw WeightLoadError(QASR_ERR_IO, std::string(WHO) + ": missing tensor " + key);
+    return it->second;
+}
+static std::string shape_str(const std::vector<int64_t>& s) {
+    std::string r = "[";
+    for (size_t i = 0; i < s.size(); ++i) r += (i ? ", " : "") + std::to_string(s[i]);
+    return r + "]";
+}
+static bool is_float(const SafeEntry& e) { return e.dtype == "F32" || e.dtype == "F16" || e.dtype == "BF16"; }
+
+const bf16_t* TtsTalker::load_bf16(const SafeTensorsDir& st, const std::string& key, std::vector<int64_t> shape) {
+    const SafeEntry& e = need(st, key);
+    if (e.shape != shape)
+        throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": tensor " + key + " has shape " + shape_str(e.shape) + ", expected " + shape_str(shape));
+    if (!is_float(e)) throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": tensor " + key + " has dtype " + e.dtype + " (F32 / F16 / BF16)");
+    if (dry_) return nullptr;
+    param_bytes_ += e.bytes;
+    if (e.dtype == "BF16") return (const bf16_t*)dev_upload(e.data, e.bytes);
+    std::vector<bf16_t> h(e.numel());
+    for (size_t i = 0; i < h.size(); ++i) h[i] = f32_to_bf16_host(safe_elem_f32(e, i));
+    return (const bf16_t*)dev_upload(h.data(), h.size() * sizeof(bf16_t));
+}
+
+// One quantised Linear, or several fused row-wise: stems concatenated (q | k | v), or two stems interleaved in blocks of `interleave`
+// rows (gate | up, the layout the SWIGLU epilogue of decode_gemv_q_launch reads).
+TtsTalker::QLin TtsTalker::load_qlin(const SafeTensorsDir& st, const std::vector<std::string>& stems, int K, bool bias, int interleave) {
+    const int bits = cfg_.bits, wrow = K * bits / 32, G = K / 64;
+    struct Part { const SafeEntry *w, *s, *b; int N; };
+    std::vector<Part> parts;
+    std::string sdtype;
+    for (const auto& stem : stems) {
+        const SafeEntry& w = need(st, stem + ".weight");
+        if (is_float(w))
+            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": tensor " + stem + ".weight is float (" + w.dtype +
+                                                        "): a float (unquantised) checkpoint is not served, only MLX affine 4 / 8 bit");
+        if (w.dtype != "U32" || w.shape.size() != 2 || w.shape[1] != wrow)
+            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": tensor " + stem + ".weight has dtype " + w.dtype + " shape " +
+                                                        shape_str(w.shape) + ", expected U32 [N, " + std::to_string(wrow) + "] (bits / width mismatch)");
+        const SafeEntry &s = need(st, stem + ".scales"), &b = need(st, stem + ".biases");
+        for (const SafeEntry* t : {&s, &b}) {
+            if (t->shape != std::vector<int64_t>{w.shape[0], (int64_t)G})
+                throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": " + stem + " scales / biases have shape " + shape_str(t->shape) +
+                                                            ", expected " + shape_str({w.shape[0], (int64_t)G}));
+            if (!is_float(*t)) throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": " + stem + " scales / biases have dtype " + t->dtype);
+        }
+        if (s.dtype != b.dtype || (!sdtype.empty() && sdtype != s.dtype))
+            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": " + stem + " scales / biases differ in dtype");
+        sdtype = s.dtype;
+        parts.push_back({&w, &s, &b, (int)w.shape[0]});
+        if (!dry_) param_bytes_ += w.bytes + s.bytes + b.bytes;
+    }
+    // the order of source rows
+    std::vector<std::pair<int, int>> order;            // (part, row)
+    if (interleave) {
+        if (parts.size() != 2 || parts[0].N != parts[1].N || parts[0].N % interleave)
+            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": " + stems[0] + ": gate / up row counts do not interleave");
+        for (int blk = 0; blk < parts[0].N / interleave; ++blk)
+            for (int pi = 0; pi < 2; ++pi)
+                for (int r = 0; r < interleave; ++r) order.push_back({pi, blk * interleave + r});
+    } else {
+        for (size_t pi = 0; pi < parts.size(); ++pi)
+            for (int r = 0; r < parts[pi].N; ++r) order.push_back({(int)pi, r});
+    }
+    const int N = (int)order.size();
+    if (bias) {
+        const SafeEntry& e = need(st, stems[0] + ".bias");
+        if (e.shape != std::vector<int64_t>{N} || !is_float(e))
+            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": tensor " + stems[0] + ".bias has shape " + shape_str(e.shape) +
+                                                        " dtype " + e.dtype + ", expected float [" + std::to_string(N) + "]");
+    }
+    if (dry_) {
+        QLin D;
+        D.N = N; D.K = K;
+        return D;
+    }
+    const bool keep_bf16 = sdtype == "BF16";
+    const size_t sel = keep_bf16 ? 2 : 4;
+    std::vector<uint32_t> hw((size_t)N * wrow);
+    std::vector<uint8_t> hs((size_t)N * G * sel), hb((size_t)N * G * sel);
+    for (int n = 0; n < N; ++n) {
+        const Part& pt = parts[order[n].first];
+        const int r = order[n].second;
+        std::memcpy(&hw[(size_t)n * wrow], pt.w->data + (size_t)r * wrow * 4, (size_t)wrow * 4);
+        if (keep_bf16 || sdtype == "F32") {
+            std::memcpy(&hs[(size_t)n * G * sel], pt.s->data + (size_t)r * G * sel, G * sel);
+            std::memcpy(&hb[(size_t)n * G * sel], pt.b->data + (size_t)r * G * sel, G * sel);
+        } else {
+            for (int g = 0; g < G; ++g) {
+                reinterpret_cast<float*>(hs.data())[(size_t)n * G + g] = safe_elem_f32(*pt.s, (size_t)r * G + g);
+                reinterpret_cast<float*>(hb.data())[(size_t)n * G + g] = safe_elem_f32(*pt.b, (size_t)r * G + g);
+            }
+        }
+    }
+    QLin L;
+    L.N = N; L.K = K;
+    QuantRaw raw;
+    raw.wq = (const uint32_t*)dev_upload(hw.data(), hw.size() * 4);
+    raw.scales = dev_upload(hs.data(), hs.size());
+    raw.biases = dev_upload(hb.data(), hb.size());
+    raw.sb_f32 = keep_bf16 ? 0 : 1; raw.N = N; raw.K = K; raw.bits = bits;
+    L.img.raw = raw; L.img.bits = bits; L.img.sb_f32 = raw.sb_f32;
+    if (bias) {
+        const SafeEntry& e = need(st, stems[0] + ".bias");
+        std::vector<float> h(N);
+        for (int i = 0; i < N; ++i) h[i] = safe_elem_f32(e, i);
+        L.bias = (const float*)dev_upload(h.data(), h.size() * 4);
+        param_bytes_ += e.bytes;
+    }
+    return L;
+}
+
+void TtsTalker::load_net(const SafeTensorsDir& st, const std::string& prefix, Net& n, int layers) {
+    const int nq = n.heads * n.hd, nkv = n.kv * n.hd;
+    for (int l = 0; l < layers; ++l) {
+        const std::string p = prefix + "model.layers." + std::to_string(l) + ".";
+        Layer L;
+        L.qkv = load_qlin(st, {p + "self_attn.q_proj", p + "self_attn.k_proj", p + "self_attn.v_proj"}, n.H, false, 0);
+        if (L.qkv.N != nq + 2 * nkv)
+            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": " + p + "self_attn q/k/v_proj hold " + std::to_string(L.qkv.N) +
+                                                        " rows, expected " + std::to_string(nq + 2 * nkv));
+        L.o = load_qlin(st, {p + "self_attn.o_proj"}, nq, false, 0);
+        L.gu = load_qlin(st, {p + "mlp.gate_proj", p + "mlp.up_proj"}, n.H, false, 16);
+        L.down = load_qlin(st, {p + "mlp.down_proj"}, n.I, false, 0);
+        if (L.o.N != n.H || L.gu.N != 2 * n.I || L.down.N != n.H)
+            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": " + p + " o_proj / mlp row counts do not match the geometry");
+        L.ln1 = load_bf16(st, p + "input_layernorm.weight", {n.H});
+        L.ln2 = load_bf16(st, p + "post_attention_layernorm.weight", {n.H});
+        L.qn = load_bf16(st, p + "self_attn.q_norm.weight", {n.hd});
+        L.kn = load_bf16(st, p + "self_attn.k_norm.weight", {n.hd});
+        // the packed images of the tuned decode GEMVs (dec_quant.h) next to the triplets the generic kernel reads
+        for (QLin* q : {&L.qkv, &L.o, &L.gu, &L.down}) {
+            const QuantRaw& raw = q->img.raw;
+            if (dry_ || raw.N % 16 != 0 || raw.K % 128 != 0) continue;
+            uint32_t* qp = (uint32_t*)dev_upload(nullptr, quant_q_bytes(raw.N, raw.K, raw.bits));
+            void* sb = dev_upload(nullptr, quant_sb_bytes(raw.N, raw.K, raw.sb_f32));
+            quant_pack_launch(raw, qp, sb, stream_);
+            q->img.qp = qp; q->img.sb = sb;
+        }
+        n.layers.push_back(L);
+    }
+    n.norm = load_bf16(st, prefix + "model.norm.weight", {n.H});
+}
+
+static void rope_tables(float theta, int half, int n_pos, std::vector<float>& c, std::vector<float>& sn) {
+    // theta_i = base^(-i/half), f32 like MLXNN.RoPE(traditional: false): the Engine's tables (decoder.hip)
+    c.resize((size_t)n_pos * half); sn.resize((size_t)n_pos * half);
+    const float k = (float)(-std::log((double)theta) / (double)half);
+    for (int i = 0; i < half; ++i) {
+        const float inv = expf((float)i * k);
+        for (int p = 0; p < n_pos; ++p) {
+            const float ang = (float)p * inv;
+            c[(size_t)p * half + i] = cosf(ang);
+            sn[(size_t)p * half + i] = sinf(ang);
+        }
+    }
+}
+
+// every tensor of both networks; with dry_ set: the host checks alone (presence, shape, dtype of every key), no HIP call
+void TtsTalker::load_all(const SafeTensorsDir& st) {
+    const auto& c = cfg_;
+    tk_ = Net{}; cp_ = Net{};
+    tk_.H = c.hidden; tk_.heads = c.heads; tk_.kv = c.kv_heads; tk_.hd = c.head_dim; tk_.I = c.inter; tk_.eps = c.rms_eps;
+    cp_.H = c.cp_hidden; cp_.heads = c.cp_heads; cp_.kv = c.cp_kv_heads; cp_.hd = c.cp_head_dim; cp_.I = c.cp_inter; cp_.eps = c.cp_rms_eps;
+    const std::string T = "talker.", P = "talker.code_predictor.";
+    codec_emb_ = load_bf16(st, T + "model.codec_embedding.weight", {c.codec_vocab, c.hidden});
+    text_emb_ = load_bf16(st, T + "model.text_embedding.weight", {c.text_vocab, c.text_hidden});
+    fc1_ = load_qlin(st, {T + "text_projection.linear_fc1"}, c.text_hidden, true, 0);
+    fc2_ = load_qlin(st, {T + "text_projection.linear_fc2"}, c.text_hidden, true, 0);
+    head_ = load_qlin(st, {T + "codec_head"}, c.hidden, false, 0);
+    if (fc1_.N != c.text_hidden || fc2_.N != c.hidden || head_.N != c.codec_vocab)
+        throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": text_projection / codec_head row counts do not match the geometry");
+    load_net(st, T, tk_, c.layers);
+    load_net(st, P, cp_, c.cp_layers);
+    std::vector<const bf16_t*> tables;
+    for (int g = 0; g < TTS_GROUPS - 1; ++g) {
+        cp_emb_[g] = load_bf16(st, P + "model.codec_embedding." + std::to_string(g) + ".weight", {c.cp_vocab, c.cp_embedding_dim});
+        tables.push_back(cp_emb_[g]);
+        lm_[g] = load_qlin(st, {P + "lm_head." + std::to_string(g)}, c.cp_hidden, false, 0);
+        if (lm_[g].N != c.cp_vocab)
+            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": lm_head." + std::to_string(g) + " does not hold cp_vocab rows");
+    }
+    if (!dry_) d_cp_emb_ = (const bf16_t**)dev_upload(tables.data(), tables.size() * sizeof(void*));
+    if (c.cp_embedding_dim != c.cp_hidden) {
+        proj_ = load_qlin(st, {P + "small_to_mtp_projection"}, c.cp_embedding_dim, true, 0);
+        if (proj_.N != c.cp_hidden)
+            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": small_to_mtp_projection does not hold cp_hidden rows");
+    }
+}
+
+TtsTalker::TtsTalker(const qasr_tts_config& cfg, const SafeTensorsDir& st) : cfg_(cfg) {
+    check_geometry(cfg_);
+    const auto& c = cfg_;
+    dry_ = true;
+    load_all(st);                                                          // throws before any HIP call
+    dry_ = false;
+    QASR_HIP(hipSetDevice(c.device));
+    QASR_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    try {
+        load_all(st);
+        // ---- tables, caches, workspaces -------------------------------------------------------------------------------------
+        const int B = c.max_batch, H = c.hidden, half = c.head_dim / 2;
+        max_prefill_ = c.max_instruct + 11;                                 // instruct + role 3 + codec prefix (<= 8) - 1 + first text
+        max_ctx_ = ((max_prefill_ + c.max_frames + 1 + 31) / 32) * 32;
+        max_tp_ = 3 + B * (c.max_text + c.max_instruct);
+        std::vector<float> rc, rs;
+        rope_tables(c.rope_theta, half, max_ctx_, rc, rs);
+        d_rope_cos_ = (float*)dev_upload(rc.data(), rc.size() * 4);
+        d_rope_sin_ = (float*)dev_upload(rs.data(), rs.size() * 4);
+        rope_tables(c.cp_rope_theta, c.cp_head_dim / 2, TTS_GROUPS, rc, rs);
+        d_cp_cos_ = (float*)dev_upload(rc.data(), rc.size() * 4);
+        d_cp_sin_ = (float*)dev_upload(rs.data(), rs.size() * 4);
+        d_rope_rows_ = (float*)dev_upload(nullptr, (size_t)2 * B * half * 4);
+        const size_t kv_bytes = (size_t)c.layers * B * c.kv_heads * max_ctx_ * c.head_dim * 2;
+        d_k_ = (bf16_t*)dev_upload(nullptr, kv_bytes);
+        d_vf_ = (bf16_t*)dev_upload(nullptr, kv_bytes);
+        QASR_HIP(hipMemsetAsync(d_k_, 0, kv_bytes, stream_));               // the attention sweep reads whole 32-key chunks and masks: finite values
+        QASR_HIP(hipMemsetAsync(d_vf_, 0, kv_bytes, stream_));
+        const size_t cpkv = (size_t)c.cp_layers * B * c.cp_kv_heads * TTS_GROUPS * c.cp_head_dim * 2;
+        d_cpk_ = (bf16_t*)dev_upload(nullptr, cpkv);
+        d_cpv_ = (bf16_t*)dev_upload(nullptr, cpkv);
+        const int nqkv = std::max((c.heads + 2 * c.kv_heads) * c.head_dim, (c.cp_heads + 2 * c.cp_kv_heads) * c.cp_head_dim);
+        const int nattn = std::max(c.heads * c.head_dim, c.cp_heads * c.cp_head_dim);
+        const int wmax = std::max({H, c.cp_hidden, c.inter, c.cp_inter, nattn});
+        d_x_ = (bf16_t*)dev_upload(nullptr, (size_t)B * H * 2);
+        d_hn_ = (bf16_t*)dev_upload(nullptr, (size_t)B * H * 2);
+        d_qkv_ = (bf16_t*)dev_upload(nullptr, (size_t)B * nqkv * 2);
+        d_attn_ = (bf16_t*)dev_upload(nullptr, (size_t)B * nattn * 2);
+        d_act_ = (bf16_t*)dev_upload(nullptr, (size_t)B * std::max(c.inter, c.cp_inter) * 2);
+        d_scratch_ = (bf16_t*)dev_upload(nullptr, (size_t)B * wmax * 2);
+        d_cpa_ = (bf16_t*)dev_upload(nullptr, (size_t)B * H * 2);
+        d_cpb_ = (bf16_t*)dev_upload(nullptr, (size_t)B * H * 2);
+        d_cx_ = (bf16_t*)dev_upload(nullptr, (size_t)B * c.cp_hidden * 2);
+        d_chn_ = (bf16_t*)dev_upload(nullptr, (size_t)B * c.cp_hidden * 2);
+        d_tp_in_ = (bf16_t*)dev_upload(nullptr, (size_t)max_tp_ * c.text_hidden * 2);
+        d_tp_mid_ = (bf16_t*)dev_upload(nullptr, (size_t)max_tp_ * c.text_hidden * 2);
+        d_tp_ = (bf16_t*)dev_upload(nullptr, (size_t)max_tp_ * H * 2);
+        d_pf_ = (bf16_t*)dev_upload(nullptr, (size_t)B * max_prefill_ * H * 2);
+        d_logits_ = (float*)dev_upload(nullptr, (size_t)B * c.codec_vocab * 4);
+        d_cp_logits_ = (float*)dev_upload(nullptr, (size_t)B * c.cp_vocab * 4);
+        d_xvec_ = (float*)dev_upload(nullptr, (size_t)B * H * 4);
+        d_state_ = (int*)dev_upload(nullptr, (size_t)6 * B * 4);
+        d_codes_ = (int*)dev_upload(nullptr, (size_t)B * TTS_GROUPS * c.max_frames * 4);
+        d_tp_ids_ = (int*)dev_upload(nullptr, (size_t)max_tp_ * 4);
+        d_pf_text_ = (int*)dev_upload(nullptr, (size_t)B * max_prefill_ * 4);
+        d_pf_codec_ = (int*)dev_upload(nullptr, (size_t)B * max_prefill_ * 4);
+        d_trail_ = (int*)dev_upload(nullptr, (size_t)B * c.max_text * 4);
+        d_row_index_ = (long long*)dev_upload(nullptr, (size_t)B * 8);
+        d_seen_ = (unsigned char*)dev_upload(nullptr, (size_t)B * c.codec_vocab);
+        d_knobs_ = (Knobs*)dev_upload(nullptr, sizeof(Knobs));
+        QASR_HIP(hipStreamSynchronize(stream_));
+    } catch (...) {
+        bufs_.clear();
+        (void)hipStreamDestroy(stream_);
+        throw;
+    }
+}
+
+void TtsTalker::drop_graphs() {
+    for (auto& kv : graphs_) (void)hipGraphExecDestroy(kv.second);
+    graphs_.clear();
+}
+
+TtsTalker::~TtsTalker() {
+    if (stream_) (void)hipStreamSynchronize(stream_);
+    drop_graphs();
+    bufs_.clear();
+    for (auto& f : forced_buf_) f.reset();
+    if (stream_) (void)hipStreamDestroy(stream_);
+}
+
+static TtsState state_of(int* base, int B) { return TtsState{base, base + B, base + 2 * B, base + 3 * B, base + 4 * B, base + 5 * B}; }
+
+// one token per row through every layer of a network, in place on x.  talker: attention over the row's cache at ctx_len[b];
+// else the code predictor's attention at position cp_pos of the frame.  kv_only_last: the last layer stops behind its attention
+// (its K / V are all a later position needs of it).
+void TtsTalker::layer_steps(const Net& n, bf16_t* x, int B, bool talker, int cp_pos, bool kv_only_last) {
+    const int nq = n.heads * n.hd, nkv = n.kv * n.hd, half = n.hd / 2;
+    const int MB = cfg_.max_batch;
+    TtsState st = state_of(d_state_, MB);
+    for (size_t l = 0; l < n.layers.size(); ++l) {
+        const Layer& L = n.layers[l];
+        DecGemvArgs a{};
+        a.X = x; a.B = B; a.N = nq + 2 * nkv; a.K = n.H; a.out = d_qkv_;
+        decode_gemv_q_launch(DEC_EPI_BF16, a, L.qkv.img, L.ln1, n.eps, d_scratch_, stream_);
+        if (talker) {
+            const size_t per = (size_t)MB * n.kv * max_ctx_ * n.hd;
+            KVLayout kv{d_k_ + l * per, nullptr, max_ctx_, n.kv, n.hd, d_vf_ + l * per};
+            decode_attention_launch(d_qkv_, st.ctx_len, B, n.heads, n.kv, n.hd, L.qn, L.kn, n.eps, d_rope_rows_,
+                                    d_rope_rows_ + (size_t)MB * half, kv, d_attn_, stream_);
+        } else {
+            const size_t per = (size_t)MB * n.kv * TTS_GROUPS * n.hd;
+            hipLaunchKernelGGL(tts_cp_attn_kernel, dim3(n.kv, B), dim3(64), 0, stream_, (const bf16_t*)d_qkv_, cp_pos, n.heads, n.kv, L.qn, L.kn,
+                               n.eps, (const float*)d_cp_cos_, (const float*)d_cp_sin_, d_cpk_ + l * per, d_cpv_ + l * per, d_attn_,
+                               1.0f / sqrtf((float)n.hd));
+        }
+        if (kv_only_last && l + 1 == n.layers.size()) break;
+        a.X = d_attn_; a.N = n.H; a.K = nq; a.out = x;
+        decode_gemv_q_launch(DEC_EPI_RESID, a, L.o.img, nullptr, n.eps, d_scratch_, stream_);
+        a.X = x; a.N = 2 * n.I; a.K = n.H; a.out = d_act_;
+        decode_gemv_q_launch(DEC_EPI_SWIGLU, a, L.gu.img, L.ln2, n.eps, d_scratch_, stream_);
+        a.X = d_act_; a.N = n.H; a.K = n.I; a.out = x;
+        decode_gemv_q_launch(DEC_EPI_RESID, a, L.down.img, nullptr, n.eps, d_scratch_, stream_);
+    }
+}
+
+// One frame of every row (tts_talker.h): Talker step, code 0, the code predictor's 16 positions, next input.
+void TtsTalker::issue_frame(int B, bool forced_mode) {
+    const auto& c = cfg_;
+    const int MB = c.max_batch, H = c.hidden, Hc = c.cp_hidden;
+    TtsState st = state_of(d_state_, MB);
+    const bool proj = c.cp_embedding_dim != c.cp_hidden;
+    layer_steps(tk_, d_x_, B, true, 0, false);
+    rmsnorm_rows_launch(d_x_, tk_.norm, d_hn_, B, H, c.rms_eps, stream_);
+    gemv_rows(head_.img.raw, d_hn_, B, nullptr, d_logits_, nullptr, c.codec_vocab, false, stream_);
+    if (forced_mode) {
+        if (d_f_tlog_) hipLaunchKernelGGL(tts_copy_out_kernel, dim3(B), dim3(256), 0, stream_, (const float*)d_logits_, (const bf16_t*)nullptr, c.codec_vocab, (const int*)st.frame_of, forced_T_host_, 1, 0, d_f_tlog_);
+        if (d_f_hid_) hipLaunchKernelGGL(tts_copy_out_kernel, dim3(B), dim3(256), 0, stream_, (const float*)nullptr, (const bf16_t*)d_hn_, H, (const int*)st.frame_of, forced_T_host_, 1, 0, d_f_hid_);
+    }
+    TtsSampleArgs sa{};
+    sa.knobs = d_knobs_; sa.st = st; sa.seen = d_seen_; sa.row_index = d_row_index_;
+    sa.codes = d_codes_; sa.stride = c.max_frames;
+    sa.forced = forced_mode ? d_f_codes_ : nullptr; sa.forced_T = forced_T_host_;
+    sa.logits = d_logits_; sa.V = c.codec_vocab; sa.group = 0;
+    sa.emb = codec_emb_; sa.E = H; sa.emb_out = d_cpb_; sa.hn = d_hn_; sa.hn_out = d_cpa_;
+    hipLaunchKernelGGL(tts_sample_kernel, dim3(B), dim3(1024), 0, stream_, sa);
+    // the code predictor: positions 0 (hidden state) and 1 (code 0) give code 1; position g + 1 holds code g and gives code g + 1
+    for (int pos = 0; pos < TTS_GROUPS; ++pos) {
+        bf16_t* in = pos == 0 ? d_cpa_ : d_cpb_;
+        bf16_t* x = in;
+        if (proj) {
+            gemv_rows(proj_.img.raw, in, B, proj_.bias, nullptr, d_cx_, Hc, false, stream_);
+            x = d_cx_;
+        }
+        layer_steps(cp_, x, B, false, pos, pos == 0);
+        if (pos == 0) continue;
+        const int g = pos - 1;                                             // lm_head.g -> code g + 1
+        rmsnorm_rows_launch(x, cp_.norm, d_chn_, B, Hc, c.cp_rms_eps, stream_);
+        gemv_rows(lm_[g].img.raw, d_chn_, B, nullptr, d_cp_logits_, nullptr, c.cp_vocab, false, stream_);
+        if (forced_mode && d_f_cplog_)
+            hipLaunchKernelGGL(tts_copy_out_kernel, dim3(B), dim3(256), 0, stream_, (const float*)d_cp_logits_, (const bf16_t*)nullptr, c.cp_vocab, (const int*)st.frame_of, forced_T_host_, TTS_GROUPS - 1, g, d_f_cplog_);
+        sa.logits = d_cp_logits_; sa.V = c.cp_vocab; sa.group = g + 1;
+        sa.emb = cp_emb_[g]; sa.E = c.cp_embedding_dim; sa.emb_out = d_cpb_; sa.hn = nullptr; sa.hn_out = nullptr;
+        hipLaunchKernelGGL(tts_sample_kernel, dim3(B), dim3(1024), 0, stream_, sa);
+    }
+    TtsNextArgs na{};
+    na.st = st; na.codes = d_codes_; na.stride = c.max_frames; na.forced = sa.forced; na.forced_T = forced_T_host_;
+    na.tp = d_tp_; na.trail = d_trail_; na.max_trail = c.max_text;
+    na.codec_emb = codec_emb_; na.cp_emb = d_cp_emb_; na.H = H; na.codec_vocab = c.codec_vocab; na.cp_vocab = c.cp_vocab;
+    na.x = d_x_; na.cos_t = d_rope_cos_; na.sin_t = d_rope_sin_;
+    na.cos_rows = d_rope_rows_; na.sin_rows = d_rope_rows_ + (size_t)MB * (c.head_dim / 2); na.half = c.head_dim / 2;
+    hipLaunchKernelGGL(tts_next_input_kernel, dim3(B), dim3(256), 0, stream_, na);
+    QASR_HIP(hipGetLastError());
+}
+
+void TtsTalker::run_frame(int B) {
+    if (graph_epoch_ != tuning().epoch) { drop_graphs(); graph_epoch_ = tuning().epoch; }
+    if (warmed_.insert(B).second) { issue_frame(B, false); return; }
+    auto it = graphs_.find(B);
+    if (it == graphs_.end()) {
+        hipGraph_t g = nullptr;
+        hipGraphExec_t ge = nullptr;
+        QASR_HIP(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
+        try { issue_frame(B, false); }
+        catch (...) { (void)hipStreamEndCapture(stream_, &g); if (g) (void)hipGraphDestroy(g); throw; }
+        QASR_HIP(hipStreamEndCapture(stream_, &g));
+        hipError_t e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(g);
+        QASR_HIP(e);
+        it = graphs_.emplace(B, ge).first;
+    }
+    QASR_HIP(hipGraphLaunch(it->second, stream_));
+}
+
+// buildPrefillEmbeddings (Qwen3TTS.swift:1313-1390) for every row, then the prompt positions but the last through the Talker's layers.
+void TtsTalker::prefill(const std::vector<TtsRow>& rows) {
+    const auto& c = cfg_;
+    const int B = (int)rows.size(), MB = c.max_batch, H = c.hidden, P = max_prefill_, half = c.head_dim / 2;
+    std::vector<int> tp_ids = {c.tts_pad, c.tts_bos, c.tts_eos};          // rows 0 1 2 of the projected text table
+    std::vector<int> pf_text((size_t)B * P, -1), pf_codec((size_t)B * P, -1), trail((size_t)B * c.max_text, 0), state((size_t)6 * MB, 0);
+    std::vector<float> xv((size_t)B * H, 0.0f);
+    std::vector<long long> ridx(MB, 0);
+    int Pmax = 0;
+    for (int b = 0; b < B; ++b) {
+        const TtsRow& r = rows[b];
+        ridx[b] = r.index;
+        int* pt = &pf_text[(size_t)b * P];
+        int* pc = &pf_codec[(size_t)b * P];
+        int n = 0;
+        auto text_row = [&](int id) { tp_ids.push_back(id); return (int)tp_ids.size() - 1; };
+        for (int i = 0; i < r.n_instruct; ++i) pt[n++] = text_row(r.instruct[i]);                  // instruct in front
+        for (int i = 0; i < 3; ++i) pt[n++] = text_row(r.text[i]);                                 // role
+        std::vector<int> codec = {c.codec_think, c.codec_think_bos, r.language, c.codec_think_eos};
+        if (r.xvector) { codec.push_back(-2); std::memcpy(&xv[(size_t)b * H], r.xvector, (size_t)H * 4); }
+        if (r.speaker >= 0) codec.push_back(r.speaker);
+        codec.push_back(c.codec_pad);
+        codec.push_back(c.codec_bos);
+        const int L = (int)codec.size();
+        for (int i = 0; i < L - 1; ++i) { pt[n] = i < L - 2 ? 0 : 1; pc[n++] = codec[i]; }        // tts_pad ... tts_bos over the prefix
+        pt[n] = text_row(r.text[3]); pc[n++] = codec[L - 1];                                       // first text + codec_bos
+        int nt = 0;
+        int* tr = &trail[(size_t)b * c.max_text];
+        for (int i = 4; i < r.n_text - 5; ++i) tr[nt++] = text_row(r.text[i]);
+        tr[nt++] = 2;                                                                              // tts_eos
+        int* s = state.data();
+        s[4 * MB + b] = nt;
+        s[5 * MB + b] = n;
+        Pmax = std::max(Pmax, n);
+    }
+    for (int b = B; b < MB; ++b) state[(size_t)1 * MB + b] = 1;
+    const int ntp = (int)tp_ids.size();
+    QASR_HIP(hipMemcpyAsync(d_tp_ids_, tp_ids.data(), (size_t)ntp * 4, hipMemcpyHostToDevice, stream_));
+    QASR_HIP(hipMemcpyAsync(d_pf_text_, pf_text.data(), pf_text.size() * 4, hipMemcpyHostToDevice, stream_));
+    QASR_HIP(hipMemcpyAsync(d_pf_codec_, pf_codec.data(), pf_codec.size() * 4, hipMemcpyHostToDevice, stream_));
+    QASR_HIP(hipMemcpyAsync(d_trail_, trail.data(), trail.size() * 4, hipMemcpyHostToDevice, stream_));
+    QASR_HIP(hipMemcpyAsync(d_state_, state.data(), state.size() * 4, hipMemcpyHostToDevice, stream_));
+    QASR_HIP(hipMemcpyAsync(d_xvec_, xv.data(), xv.size() * 4, hipMemcpyHostToDevice, stream_));
+    QASR_HIP(hipMemcpyAsync(d_row_index_, ridx.data(), ridx.size() * 8, hipMemcpyHostToDevice, stream_));
+    QASR_HIP(hipMemsetAsync(d_seen_, 0, (size_t)MB * c.codec_vocab, stream_));
+    QASR_HIP(hipMemsetAsync(d_codes_, 0xff, (size_t)MB * TTS_GROUPS * c.max_frames * 4, stream_));
+    // text_projection(text_embedding(id)) of every text-side id of the call
+    hipLaunchKernelGGL(tts_gather_rows_kernel, dim3(ntp), dim3(256), 0, stream_, text_emb_, (const int*)d_tp_ids_, c.text_hidden, d_tp_in_);
+    gemv_rows(fc1_.img.raw, d_tp_in_, ntp, fc1_.bias, nullptr, d_tp_mid_, c.text_hidden, true, stream_);
+    gemv_rows(fc2_.img.raw, d_tp_mid_, ntp, fc2_.bias, nullptr, d_tp_, H, false, stream_);
+    hipLaunchKernelGGL(tts_prefill_build_kernel, dim3(P, B), dim3(256), 0, stream_, (const int*)d_pf_text_, (const int*)d_pf_codec_, P,
+                       (const bf16_t*)d_tp_, codec_emb_, (const float*)d_xvec_, H, d_pf_);
+    TtsState st = state_of(d_state_, MB);
+    for (int s = 0; s < Pmax; ++s) {
+        hipLaunchKernelGGL(tts_prefill_feed_kernel, dim3(B), dim3(256), 0, stream_, st, s, Pmax, (const bf16_t*)d_pf_, P, H, d_x_,
+                           (const float*)d_rope_cos_, (const float*)d_rope_sin_, d_rope_rows_, d_rope_rows_ + (size_t)MB * half, half);
+        if (s + 1 < Pmax) layer_steps(tk_, d_x_, B, true, 0, false);      // the last position is the Talker step of frame 0
+    }
+    QASR_HIP(hipGetLastError());
+    QASR_HIP(hipStreamSynchronize(stream_));                              // the host vectors above go out of scope
+}
+
+void TtsTalker::set_knobs(const qasr_tts_sampling& s, unsigned long long seed) {
+    Knobs k{};
+    k.talker = TtsSampleParams{s.temperature, s.repetition_penalty, s.eos_logit_bias, s.top_k, cfg_.suppress_lo, cfg_.suppress_hi,
+                               cfg_.codec_eos, seed};
+    k.cp = TtsSampleParams{s.temperature, 1.0f, 0.0f, s.top_k, 0, 0, -1, seed};
+    QASR_HIP(hipMemcpyAsync(d_knobs_, &k, sizeof(k), hipMemcpyHostToDevice, stream_));
+    QASR_HIP(hipStreamSynchronize(stream_));
+}
+
+void TtsTalker::generate(const std::vector<TtsRow>& rows, const qasr_tts_sampling& s, unsigned long long seed, int max_frames,
+                         int32_t* codes, int32_t* n_frames) {
+    const int B = (int)rows.size(), MB = cfg_.max_batch, F = cfg_.max_frames;
+    if (B == 0) return;
+    QASR_HIP(hipSetDevice(cfg_.device));
+    max_frames = std::min(std::max(max_frames, 1), F);
+    set_knobs(s, seed);
+    prefill(rows);
+    std::vector<int> fin(MB);
+    TtsState st = state_of(d_state_, MB);
+    for (int f = 0; f < max_frames; ++f) {
+        run_frame(B);
+        if ((f + 1) % TTS_POLL == 0 && f + 1 < max_frames) {              // the finished flags, every TTS_POLL frames
+            QASR_HIP(hipMemcpyAsync(fin.data(), st.finished, (size_t)B * 4, hipMemcpyDeviceToHost, stream_));
+            QASR_HIP(hipStreamSynchronize(stream_));
+            if (std::all_of(fin.begin(), fin.begin() + B, [](int v) { return v != 0; })) break;
+        }
+    }
+    // frames computed behind a row's EOS (up to the next poll) were never stored: a finished row writes no code
+    std::vector<int> h((size_t)B * TTS_GROUPS * F);
+    QASR_HIP(hipMemcpyAsync(h.data(), d_codes_, h.size() * 4, hipMemcpyDeviceToHost, stream_));
+    QASR_HIP(hipMemcpyAsync(n_frames, st.n_frames, (size_t)B * 4, hipMemcpyDeviceToHost, stream_));
+    QASR_HIP(hipStreamSynchronize(stream_));
+    for (int b = 0; b < B; ++b) {
+        n_frames[b] = std::min(n_frames[b], max_frames);
+        for (int g = 0; g < TTS_GROUPS; ++g)
+            for (int t = 0; t < F; ++t) {
+                const size_t i = ((size_t)b * TTS_GROUPS + g) * F + t;
+                codes[i] = t < n_frames[b] ? h[i] : -1;
+            }
+    }
+}
+
+void TtsTalker::forced(const std::vector<TtsRow>& rows, const TtsForcedOut& f) {
+    const int B = (int)rows.size(), T = f.T;
+    const auto& c = cfg_;
+    if (B == 0 || T == 0) return;
+    QASR_HIP(hipSetDevice(c.device));
+    qasr_tts_sampling s{0.0f, 1, 1.0f, 1.0f, T, 0.0f};
+    set_knobs(s, 0);
+    const size_t n_codes = (size_t)B * TTS_GROUPS * T, n_tl = (size_t)B * T * c.codec_vocab,
+                 n_cl = (size_t)B * T * (TTS_GROUPS - 1) * c.cp_vocab, n_h = (size_t)B * T * c.hidden;
+    for (auto& fb : forced_buf_) fb = std::make_unique<DevBuf>();
+    forced_buf_[0]->alloc(n_codes * 4);
+    d_f_codes_ = forced_buf_[0]->as<int>();
+    d_f_tlog_ = d_f_cplog_ = d_f_hid_ = nullptr;
+    if (f.talker_logits) { forced_buf_[1]->alloc(n_tl * 4); d_f_tlog_ = forced_buf_[1]->as<float>(); }
+    if (f.cp_logits) { forced_buf_[2]->alloc(n_cl * 4); d_f_cplog_ = forced_buf_[2]->as<float>(); }
+    if (f.hidden) { forced_buf_[3]->alloc(n_h * 4); d_f_hid_ = forced_buf_[3]->as<float>(); }
+    forced_T_host_ = T;
+    QASR_HIP(hipMemcpyAsync(d_f_codes_, f.codes, n_codes * 4, hipMemcpyHostToDevice, stream_));
+    prefill(rows);
+    for (int t = 0; t < T; ++t) issue_frame(B, true);
+    if (f.talker_logits) QASR_HIP(hipMemcpyAsync(f.talker_logits, d_f_tlog_, n_tl * 4, hipMemcpyDeviceToHost, stream_));
+    if (f.cp_logits) QASR_HIP(hipMemcpyAsync(f.cp_logits, d_f_cplog_, n_cl * 4, hipMemcpyDeviceToHost, stream_));
+    if (f.hidden) QASR_HIP(hipMemcpyAsync(f.hidden, d_f_hid_, n_h * 4, hipMemcpyDeviceToHost, stream_));
+    QASR_HIP(hipStreamSynchronize(stream_));
+    for (auto& fb : forced_buf_) fb.reset();
+    d_f_codes_ = nullptr; d_f_tlog_ = d_f_cplog_ = d_f_hid_ = nullptr;
+}
+
+}  // namespace qasr

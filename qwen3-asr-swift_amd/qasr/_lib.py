@@ -67,6 +67,28 @@ class QasrTransducerCallbacks(C.Structure):
     _fields_ = [("ctx", C.c_void_p), ("decoder_step", TD_DECODER_FN), ("joint", TD_JOINT_FN)]
 
 
+class QasrTtsConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("hidden", "layers", "heads", "kv_heads", "head_dim", "inter", "text_vocab", "text_hidden",
+                                         "codec_vocab", "cp_hidden", "cp_embedding_dim", "cp_layers", "cp_heads", "cp_kv_heads",
+                                         "cp_head_dim", "cp_inter", "cp_vocab")] + \
+               [(n, C.c_float) for n in ("rms_eps", "rope_theta", "cp_rms_eps", "cp_rope_theta")] + \
+               [(n, C.c_int32) for n in ("bits", "group_size", "codec_pad", "codec_bos", "codec_eos", "codec_think", "codec_nothink",
+                                         "codec_think_bos", "codec_think_eos", "suppress_lo", "suppress_hi", "tts_pad", "tts_bos",
+                                         "tts_eos", "max_batch", "max_frames", "max_text", "max_instruct", "device")]
+
+
+class QasrTtsSampling(C.Structure):
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("repetition_penalty", C.c_float),
+                ("max_tokens", C.c_int32), ("eos_logit_bias", C.c_float)]
+
+
+class QasrTtsRequest(C.Structure):
+    _fields_ = [("B", C.c_size_t), ("text", C.POINTER(C.POINTER(C.c_int32))), ("text_len", C.POINTER(C.c_int32)),
+                ("language", C.POINTER(C.c_int32)), ("speaker", C.POINTER(C.c_int32)),
+                ("xvector", C.POINTER(C.POINTER(C.c_float))), ("instruct", C.POINTER(C.POINTER(C.c_int32))),
+                ("instruct_len", C.POINTER(C.c_int32)), ("row_index", C.POINTER(C.c_int64))]
+
+
 SC_TRANSCRIBE_FN = C.CFUNCTYPE(ScTranscriptionResult, C.c_void_p, C.POINTER(C.c_float), C.c_size_t, C.c_int)
 SC_RATE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p)
 
@@ -323,6 +345,19 @@ SIGNATURES = {
     "qasr_xvec_mel": (C.c_int, [_E, _P(_F), _P(C.c_size_t), C.c_size_t, _P(_F)]),
     "qasr_xvec_embed_mel": (C.c_int, [_E, _F, C.c_size_t, _F]),
     "qasr_xvec_timing": (C.c_int, [_E, _F]),
+    "qasr_tts_default_config": (C.c_int, [C.c_char_p, C.c_int, _P(QasrTtsConfig)]),
+    "qasr_tts_default_sampling": (None, [C.c_int, _P(QasrTtsSampling)]),
+    "qasr_tts_poll_interval": (C.c_int, []),
+    "qasr_tts_create": (C.c_int, [C.c_char_p, _P(QasrTtsConfig), _P(_E)]),
+    "qasr_tts_free": (None, [_E]),
+    "qasr_tts_last_error": (C.c_char_p, [_E]),
+    "qasr_tts_memory_footprint": (C.c_size_t, [_E]),
+    "qasr_tts_device_bytes": (C.c_size_t, [_E]),
+    "qasr_tts_generate": (C.c_int, [_E, _P(QasrTtsRequest), _P(QasrTtsSampling), C.c_uint64, _I, _I]),
+    "qasr_tts_forced": (C.c_int, [_E, _P(QasrTtsRequest), _I, C.c_size_t, _F, _F, _F]),
+    "qasr_tts_sample_host": (C.c_int, [_P(QasrTtsConfig), _F, C.c_int32, C.c_int, _P(QasrTtsSampling), _I, C.c_int32, C.c_uint64,
+                                       C.c_int64, C.c_int32, C.c_int32]),
+    "qasr_tts_synthesize": (C.c_int, [_E, _E, _P(QasrTtsRequest), _P(QasrTtsSampling), C.c_uint64, _P(_F), _P(C.c_size_t), _I, _I]),
     "qasr_transducer_default_config": (C.c_int, [C.c_char_p, _P(QasrTransducerConfig)]),
     "qasr_tdt_greedy_decode": (C.c_int, [_P(QasrTransducerConfig), _P(QasrTransducerCallbacks), C.c_int32, _I, _F, C.c_int32, _F]),
     "qasr_rnnt_greedy_decode": (C.c_int, [_P(QasrTransducerConfig), _P(QasrTransducerCallbacks), C.c_int32, C.c_int32, _I, _F, C.c_int32, _I]),

@@ -758,3 +758,129 @@ def write_tts_speaker_encoder_safetensors(sd: dict, model_dir: str, dtype: str =
         d[k] = np.asarray(v, dtype=np.float32)
     _write_safetensors(d, model_dir, dtype, drop, reshape)
     return model_dir
+
+
+# ---- Qwen3-TTS Talker + code predictor (qasr_tts_*) ----------------------------------------------------------------------------
+TTS_TALKER_REAL = dict(hidden=1024, layers=28, heads=16, kv_heads=8, head_dim=128, inter=3072, text_vocab=151936, text_hidden=2048,
+                       codec_vocab=3072, cp_hidden=1024, cp_embedding_dim=1024, cp_layers=5, cp_heads=16, cp_kv_heads=8, cp_head_dim=128,
+                       cp_inter=3072, cp_vocab=2048, bits=4, tts_pad=151671, tts_bos=151672, tts_eos=151673)
+# reduced test geometries: a text vocabulary of 512 with the three text-side special ids remapped to its end
+TTS_TALKER_SMALL = dict(TTS_TALKER_REAL, hidden=256, layers=2, heads=4, kv_heads=2, inter=512, text_vocab=512, text_hidden=128,
+                        cp_hidden=256, cp_embedding_dim=256, cp_layers=2, cp_heads=4, cp_kv_heads=2, cp_inter=512,
+                        tts_pad=509, tts_bos=510, tts_eos=511)
+TTS_TALKER_LARGE_FORM = dict(TTS_TALKER_SMALL, hidden=512, inter=1024, cp_embedding_dim=512)   # embedding_dim != cp_hidden: the projection
+
+
+def tts_talker_tensor_shapes(geometry=None) -> dict:
+    """key -> (shape, quantised?) of every tensor of the Talker and the code predictor in the reference's key names
+    (TTSWeightLoading.swift:24-158), with the `talker.` / `talker.code_predictor.` prefixes.  A quantised [out, in] Linear is stored as
+    the triplet weight | scales | biases; `.bias` keys are float."""
+    g = dict(TTS_TALKER_REAL, **(geometry or {}))
+    s = {}
+
+    def net(p, H, heads, kv, hd, inter, layers):
+        for l in range(layers):
+            q = f"{p}model.layers.{l}."
+            s[q + "self_attn.q_proj.weight"] = ((heads * hd, H), True)
+            s[q + "self_attn.k_proj.weight"] = ((kv * hd, H), True)
+            s[q + "self_attn.v_proj.weight"] = ((kv * hd, H), True)
+            s[q + "self_attn.o_proj.weight"] = ((H, heads * hd), True)
+            s[q + "self_attn.q_norm.weight"] = ((hd,), False)
+            s[q + "self_attn.k_norm.weight"] = ((hd,), False)
+            s[q + "input_layernorm.weight"] = ((H,), False)
+            s[q + "post_attention_layernorm.weight"] = ((H,), False)
+            s[q + "mlp.gate_proj.weight"] = ((inter, H), True)
+            s[q + "mlp.up_proj.weight"] = ((inter, H), True)
+            s[q + "mlp.down_proj.weight"] = ((H, inter), True)
+        s[p + "model.norm.weight"] = ((H,), False)
+
+    t, c = "talker.", "talker.code_predictor."
+    s[t + "model.codec_embedding.weight"] = ((g["codec_vocab"], g["hidden"]), False)
+    s[t + "model.text_embedding.weight"] = ((g["text_vocab"], g["text_hidden"]), False)
+    s[t + "text_projection.linear_fc1.weight"] = ((g["text_hidden"], g["text_hidden"]), True)
+    s[t + "text_projection.linear_fc1.bias"] = ((g["text_hidden"],), False)
+    s[t + "text_projection.linear_fc2.weight"] = ((g["hidden"], g["text_hidden"]), True)
+    s[t + "text_projection.linear_fc2.bias"] = ((g["hidden"],), False)
+    s[t + "codec_head.weight"] = ((g["codec_vocab"], g["hidden"]), True)
+    net(t, g["hidden"], g["heads"], g["kv_heads"], g["head_dim"], g["inter"], g["layers"])
+    net(c, g["cp_hidden"], g["cp_heads"], g["cp_kv_heads"], g["cp_head_dim"], g["cp_inter"], g["cp_layers"])
+    for i in range(15):
+        s[c + f"model.codec_embedding.{i}.weight"] = ((g["cp_vocab"], g["cp_embedding_dim"]), False)
+        s[c + f"lm_head.{i}.weight"] = ((g["cp_vocab"], g["cp_hidden"]), True)
+    if g["cp_embedding_dim"] != g["cp_hidden"]:
+        s[c + "small_to_mtp_projection.weight"] = ((g["cp_hidden"], g["cp_embedding_dim"]), True)
+        s[c + "small_to_mtp_projection.bias"] = ((g["cp_hidden"],), False)
+    return s
+
+
+def synth_tts_talker_state_dict(geometry=None, seed: int = 0, quantized: bool = True) -> dict:
+    """Seeded Talker + code-predictor weights in the checkpoint's form: float tensors bf16, every Linear quantised with
+    quantize_linear at geometry["bits"] (quantized=False keeps them bf16: the float checkpoint the loader refuses).  Matrices are
+    N(0, 1 / fan_in); the heads' rows carry a log-normal gain, which gives the logits a heavy tail (a clear first maximum, as a
+    trained model has, so a greedy run does not hang on bf16-sized ties); norms 1 + 0.1 N, embeddings 0.5 N, biases 0.05 N."""
+    g = dict(TTS_TALKER_REAL, **(geometry or {}))
+    rng = torch.Generator().manual_seed(424242 + seed)
+    sd = {}
+    for key, (shape, quant) in tts_talker_tensor_shapes(g).items():
+        if key.endswith(".bias"):
+            w = 0.05 * torch.randn(shape, generator=rng)
+        elif "norm" in key:
+            w = 1.0 + 0.1 * torch.randn(shape, generator=rng)
+        elif "embedding" in key and not quant:
+            w = 0.5 * torch.randn(shape, generator=rng)
+        else:
+            w = torch.randn(shape, generator=rng) / math.sqrt(shape[1])
+            if "head" in key:
+                w = 2.0 * w * torch.exp(torch.randn((shape[0], 1), generator=rng))
+        w = w.to(torch.bfloat16)
+        if quant and quantized:
+            stem = key[:-len(".weight")]
+            sd[key], sd[stem + ".scales"], sd[stem + ".biases"] = quantize_linear(w, g["bits"])
+        else:
+            sd[key] = w
+    return sd
+
+
+def write_tts_talker_safetensors(sd: dict, model_dir: str, drop=(), extra=(), scales_dtype: str = "BF16") -> str:
+    """Writes `sd` (synth_tts_talker_state_dict) as model_dir/model.safetensors: int32 tensors as U32, bf16 as BF16 (scales / biases as
+    `scales_dtype`: BF16 | F32 | F16), float32 as F32.  `drop`: keys left out; `extra`: (key, float array) pairs added as F32 (the main
+    checkpoint's other tensors).  Returns model_dir."""
+    import json
+    import os
+    os.makedirs(model_dir, exist_ok=True)
+    header, blobs, off = {}, [], 0
+
+    def add(key, dtype, shape, raw):
+        nonlocal off
+        header[key] = {"dtype": dtype, "shape": list(shape), "data_offsets": [off, off + len(raw)]}
+        blobs.append(raw)
+        off += len(raw)
+
+    for key in sorted(sd):
+        if key in drop:
+            continue
+        v = sd[key]
+        if v.dtype == torch.int32:
+            add(key, "U32", v.shape, v.contiguous().numpy().astype("<i4").tobytes())
+            continue
+        dt = scales_dtype if key.endswith((".scales", ".biases")) else ("BF16" if v.dtype == torch.bfloat16 else "F32")
+        f = v.to(torch.float32).contiguous().numpy()
+        if dt == "BF16":
+            raw = (f.view("<u4") >> 16).astype("<u2").tobytes() if v.dtype == torch.bfloat16 else \
+                ((f.view("<u4") + 0x7FFF + ((f.view("<u4") >> 16) & 1)) >> 16).astype("<u2").tobytes()
+        elif dt == "F16":
+            raw = f.astype("<f2").tobytes()
+        else:
+            raw = f.astype("<f4").tobytes()
+        add(key, dt, v.shape, raw)
+    for k, v in (extra.items() if isinstance(extra, dict) else extra):
+        a = np.asarray(v, dtype=np.float32)
+        add(k, "F32", a.shape, a.astype("<f4").tobytes())
+    h = json.dumps(header).encode()
+    h += b" " * ((8 - len(h) % 8) % 8)
+    with open(os.path.join(model_dir, "model.safetensors"), "wb") as fh:
+        fh.write(len(h).to_bytes(8, "little"))
+        fh.write(h)
+        for raw in blobs:
+            fh.write(raw)
+    return model_dir

@@ -1,0 +1,238 @@
+"""The Qwen3-TTS Talker + code predictor on the GPU over the C ABI (include/qasr.h, qasr_tts_*).
+
+Reference: Sources/Qwen3TTS/Qwen3TTS.swift (Qwen3TTSModel.synthesize, synthesizeBatch, synthesizeWithVoiceClone in x-vector mode),
+Talker.swift, CodePredictor.swift, Sampling.swift, Configuration.swift.  Text -> ids stays with the caller: the wrapper builds the chat
+template of prepareTextTokens / prepareInstructTokens around ids it is given.  Codes are int32 [16, n_frames] per row at 12.5 Hz; with a
+SpeechTokenizerDecoder (qasr.codec) they become 24 kHz float32 audio.  No CPU fallback.
+"""
+import ctypes as C
+from dataclasses import dataclass
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+from . import _lib
+from .model import QasrError
+
+_F = C.POINTER(C.c_float)
+_I = C.POINTER(C.c_int32)
+NUM_CODE_GROUPS = 16
+IM_START, IM_END, NEWLINE, ASSISTANT, USER = 151644, 151645, 198, 77091, 872
+
+
+class CodecTokens:
+    """Configuration.swift:152-193."""
+    codec_pad, codec_bos, codec_eos = 2148, 2149, 2150
+    codec_think, codec_nothink, codec_think_bos, codec_think_eos = 2154, 2155, 2156, 2157
+    tts_pad, tts_bos, tts_eos = 151671, 151672, 151673
+    languages = {"english": 2050, "german": 2052, "chinese": 2055, "japanese": 2058, "spanish": 2054, "french": 2061, "korean": 2064,
+                 "russian": 2069, "italian": 2070, "portuguese": 2071, "beijing_dialect": 2074, "sichuan_dialect": 2062}
+    short = {"en": "english", "de": "german", "zh": "chinese", "ja": "japanese", "es": "spanish", "fr": "french", "ko": "korean",
+             "ru": "russian", "it": "italian", "pt": "portuguese"}
+
+    @classmethod
+    def language_id(cls, language: str) -> Optional[int]:
+        """languageId(for:): the codec id of a language name or two-letter code, None when unknown."""
+        key = str(language).lower()
+        return cls.languages.get(cls.short.get(key, key))
+
+
+@dataclass
+class SamplingConfig:
+    """Sampling.swift:5-30 (minP is declared and never read there: no field)."""
+    temperature: float = 0.9
+    top_k: int = 50
+    top_p: float = 1.0
+    repetition_penalty: float = 1.05
+    max_tokens: int = 4096
+    eos_logit_bias: float = 0.0
+
+    @classmethod
+    def greedy(cls) -> "SamplingConfig":
+        return cls(temperature=0.0, top_k=1)
+
+    def c_struct(self) -> _lib.QasrTtsSampling:
+        return _lib.QasrTtsSampling(float(self.temperature), int(self.top_k), float(self.top_p), float(self.repetition_penalty),
+                                    int(self.max_tokens), float(self.eos_logit_bias))
+
+
+def prepare_text_tokens(text_ids: Sequence[int]) -> List[int]:
+    """prepareTextTokens: <|im_start|>assistant\\n{text}<|im_end|>\\n<|im_start|>assistant\\n around the caller's ids."""
+    return [IM_START, ASSISTANT, NEWLINE, *[int(t) for t in text_ids], IM_END, NEWLINE, IM_START, ASSISTANT, NEWLINE]
+
+
+def prepare_instruct_tokens(instruct_ids: Sequence[int]) -> List[int]:
+    """prepareInstructTokens: <|im_start|>user\\n{instruct}<|im_end|>\\n."""
+    return [IM_START, USER, NEWLINE, *[int(t) for t in instruct_ids], IM_END, NEWLINE]
+
+
+def default_config(model: str = "0.6B", bits: int = 4, **over) -> _lib.QasrTtsConfig:
+    """Qwen3TTSConfig.config(for:bits:) with the CodecTokens ids; keyword arguments replace fields."""
+    cfg = _lib.QasrTtsConfig()
+    rc = _lib.load(strict=True).qasr_tts_default_config(model.encode(), int(bits), C.byref(cfg))
+    if rc != 0:
+        raise QasrError(f"qasr error {rc}: default_config({model!r}, {bits})")
+    for k, v in over.items():
+        if not hasattr(cfg, k):
+            raise QasrError(f"qasr error 1: qasr_tts_config has no field {k}")
+        setattr(cfg, k, v)
+    return cfg
+
+
+def sample_host(logits, sampling: SamplingConfig, talker=True, history=(), seed=0, row_index=0, frame=0, group=0, cfg=None) -> int:
+    """The host twin of the device sampler on one row of logits (qasr_tts_sample_host; pure CPU)."""
+    a = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1)
+    h = np.ascontiguousarray(history, dtype=np.int32).reshape(-1)
+    s = sampling.c_struct()
+    rc = _lib.load(strict=True).qasr_tts_sample_host(C.byref(cfg) if cfg is not None else None, a.ctypes.data_as(_F), a.size, int(bool(talker)),
+                                                     C.byref(s), h.ctypes.data_as(_I), h.size, int(seed), int(row_index), int(frame), int(group))
+    if rc < 0:
+        raise QasrError(f"qasr error {-rc}: sample_host")
+    return int(rc)
+
+
+class _Request:
+    """The C request of a batch; keeps the arrays it points to alive."""
+
+    def __init__(self, texts, languages, speakers=None, xvectors=None, instructs=None, row_index=None):
+        B = len(texts)
+        self.keep = []
+
+        def rows(items):
+            arrs = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1) for t in items]
+            self.keep.append(arrs)
+            return (_I * B)(*[a.ctypes.data_as(_I) for a in arrs]), (C.c_int32 * B)(*[a.size for a in arrs])
+
+        if isinstance(languages, (int, np.integer)):
+            languages = [languages] * B
+        if len(languages) != B:
+            raise QasrError("qasr error 1: one language id per row")
+        rq = _lib.QasrTtsRequest()
+        rq.B = B
+        self.text, self.text_len = rows(texts)
+        rq.text, rq.text_len = self.text, self.text_len
+        self.lang = (C.c_int32 * B)(*[int(v) for v in languages])
+        rq.language = self.lang
+        if speakers is not None:
+            self.spk = (C.c_int32 * B)(*[-1 if v is None else int(v) for v in speakers])
+            rq.speaker = self.spk
+        if xvectors is not None:
+            arrs = [None if v is None else np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for v in xvectors]
+            self.keep.append(arrs)
+            self.xv = (_F * B)(*[None if a is None else a.ctypes.data_as(_F) for a in arrs])
+            self.xv_sizes = [None if a is None else a.size for a in arrs]
+            rq.xvector = self.xv
+        if instructs is not None:
+            self.ins, self.ins_len = rows([[] if v is None else v for v in instructs])
+            rq.instruct, rq.instruct_len = self.ins, self.ins_len
+        if row_index is not None:
+            self.ridx = (C.c_int64 * B)(*[int(v) for v in row_index])
+            rq.row_index = self.ridx
+        self.rq = rq
+
+
+class Qwen3TTSModel:
+    """Qwen3TTSModel on the device: ids in, codes (and with a codec, audio) out."""
+
+    def __init__(self, handle, cfg):
+        self.lib, self.h, self.cfg = _lib.load(strict=True), handle, cfg
+
+    @classmethod
+    def from_pretrained(cls, model_dir, cfg=None, **over):
+        """model_dir: the main model directory (talker.* keys in any *.safetensors file).  cfg: a qasr_tts_config (default_config());
+        keyword arguments replace fields of it (max_batch, max_frames, max_text, max_instruct, device, ...)."""
+        lib = _lib.load(strict=True)
+        cfg = cfg if cfg is not None else default_config()
+        for k, v in over.items():
+            setattr(cfg, k, v)
+        h = C.c_void_p()
+        rc = lib.qasr_tts_create(str(model_dir).encode(), C.byref(cfg), C.byref(h))
+        if rc != 0:
+            raise QasrError(f"qasr error {rc}: {lib.qasr_tts_last_error(None).decode()}")
+        return cls(h, cfg)
+
+    def close(self):
+        if self.h:
+            self.lib.qasr_tts_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def _check(self, rc):
+        if rc != 0:
+            raise QasrError(f"qasr error {rc}: {self.lib.qasr_tts_last_error(self.h).decode()}")
+
+    @property
+    def memory_footprint(self) -> int:
+        return int(self.lib.qasr_tts_memory_footprint(self.h))
+
+    @property
+    def device_bytes(self) -> int:
+        return int(self.lib.qasr_tts_device_bytes(self.h))
+
+    def _request(self, texts, languages, speakers, xvectors, instructs, row_index):
+        rq = _Request(texts, languages, speakers, xvectors, instructs, row_index)
+        for n in getattr(rq, "xv_sizes", []):
+            if n is not None and n != self.cfg.hidden:
+                raise QasrError(f"qasr error 1: an x-vector holds {n} floats, the Talker's hidden size is {self.cfg.hidden}")
+        return rq
+
+    # ---- codes ----
+    def generate_codes(self, texts, languages, sampling: Optional[SamplingConfig] = None, seed: int = 0, speakers=None, xvectors=None,
+                       instructs=None, row_index=None) -> List[np.ndarray]:
+        """texts: templated id lists (prepare_text_tokens), one per row -> int32 [16, n_frames] per row."""
+        rq = self._request(texts, languages, speakers, xvectors, instructs, row_index)
+        s = (sampling or SamplingConfig()).c_struct()
+        B, F = len(texts), self.cfg.max_frames
+        codes = np.zeros((B, NUM_CODE_GROUPS, F), dtype=np.int32)
+        n = np.zeros(B, dtype=np.int32)
+        self._check(self.lib.qasr_tts_generate(self.h, C.byref(rq.rq), C.byref(s), int(seed), codes.ctypes.data_as(_I), n.ctypes.data_as(_I)))
+        return [codes[b, :, :int(n[b])].copy() for b in range(B)]
+
+    def forced(self, texts, languages, codes, speakers=None, xvectors=None, instructs=None, want=("talker", "cp", "hidden")):
+        """Teacher-forced pass on codes [B, 16, T] -> dict of talker logits [B, T, codec_vocab], cp logits [B, T, 15, cp_vocab] and
+        post-norm hidden states [B, T, hidden]."""
+        rq = self._request(texts, languages, speakers, xvectors, instructs, None)
+        c = np.ascontiguousarray(codes, dtype=np.int32)
+        B, G, T = c.shape
+        if B != len(texts) or G != NUM_CODE_GROUPS:
+            raise QasrError("qasr error 1: forced codes are [B, 16, T]")
+        out = {}
+        if "talker" in want:
+            out["talker"] = np.zeros((B, T, self.cfg.codec_vocab), dtype=np.float32)
+        if "cp" in want:
+            out["cp"] = np.zeros((B, T, NUM_CODE_GROUPS - 1, self.cfg.cp_vocab), dtype=np.float32)
+        if "hidden" in want:
+            out["hidden"] = np.zeros((B, T, self.cfg.hidden), dtype=np.float32)
+        ptr = lambda k: out[k].ctypes.data_as(_F) if k in out else None
+        self._check(self.lib.qasr_tts_forced(self.h, C.byref(rq.rq), c.ctypes.data_as(_I), T, ptr("talker"), ptr("cp"), ptr("hidden")))
+        return out
+
+    # ---- audio ----
+    def synthesize_batch(self, codec, texts, languages, sampling: Optional[SamplingConfig] = None, seed: int = 0, speakers=None,
+                         xvectors=None, instructs=None, row_index=None, return_codes=False):
+        """synthesizeBatch: codes, then `codec` (a qasr.codec.SpeechTokenizerDecoder) -> float32 [1920 * n_frames] per row."""
+        rq = self._request(texts, languages, speakers, xvectors, instructs, row_index)
+        s = (sampling or SamplingConfig()).c_struct()
+        B, F = len(texts), self.cfg.max_frames
+        pcm = [np.zeros(1920 * F, dtype=np.float32) for _ in range(B)]
+        pp = (_F * B)(*[a.ctypes.data_as(_F) for a in pcm])
+        ns = (C.c_size_t * B)()
+        codes = np.zeros((B, NUM_CODE_GROUPS, F), dtype=np.int32)
+        n = np.zeros(B, dtype=np.int32)
+        self._check(self.lib.qasr_tts_synthesize(self.h, getattr(codec, "h", codec), C.byref(rq.rq), C.byref(s), int(seed), pp, ns,
+                                                 codes.ctypes.data_as(_I), n.ctypes.data_as(_I)))
+        audio = [pcm[b][:int(ns[b])].copy() for b in range(B)]
+        if return_codes:
+            return audio, [codes[b, :, :int(n[b])].copy() for b in range(B)]
+        return audio
+
+    def synthesize(self, codec, text, language, sampling: Optional[SamplingConfig] = None, seed: int = 0, speaker=None, instruct=None):
+        """synthesize: one templated id list -> float32 audio at 24 kHz."""
+        return self.synthesize_batch(codec, [text], [language], sampling, seed, None if speaker is None else [speaker], None,
+                                     None if instruct is None else [instruct])[0]
+
+    def synthesize_with_voice_clone(self, codec, text, language, xvector, sampling: Optional[SamplingConfig] = None, seed: int = 0):
+        """synthesizeWithVoiceClone in x-vector mode: xvector [hidden] from qasr.tts_speaker.SpeakerEncoder.embed."""
+        return self.synthesize_batch(codec, [text], [language], sampling, seed, None, [xvector])[0]
