@@ -221,6 +221,51 @@ int qasr_decode_structure(qasr_engine* e, int* fused_qa, int* chain, int* launch
  * each other bit for bit and with a float64 product on ragged shapes.  *avg_ms (may be NULL): mean of `reps` launches. */
 int qasr_gemm_probe(qasr_engine* e, const uint16_t* A, const uint16_t* W, const float* bias, int M, int N, int K, int form,
                     int reps, float* out, float* avg_ms);
+/* Diagnostic: ONE operand gather + fused epilogue pair of that GEMM as the product launches it (same functor types, same launch entry),
+ * on host data: upload, one launch, download.  Needs no weights; no reference counterpart.  tests/test_gpu_gemm_cases.py holds every pair
+ * against a float64 restatement (tests/gemm_cases.py) and the gathers bit for bit against qasr_gemm_probe on the materialised operand.
+ *   which                    operand A (bf16 bit patterns)         epilogue -> out                                     launch
+ *   CONV                     NHWC image [n_img][H][W][C], 3x3 /    bf16 gelu(acc + bias_f32[n]), +0 where ow >=         gemm_nt
+ *                            stride 2 / pad 1, K index (kh*3+kw)   aux_i[img] (the image's valid output width; the
+ *                            *C+ci; wide = 1: the per-K-tile tap   engine's level 2 / 3 width field carries it)
+ *                            decomposition (C >= 64)
+ *   CONV_PLAIN               the same gathers                      f32 acc + bias_f32[n]                               gemm_nt
+ *   ROWTABLE                 a_len elements, row m = A + aux_l[m]  f32 acc + bias_f32[n]                               gemm_nt
+ *   GROUPCONV                frames [M][groups*cpg]; aux_i = per   f32 gelu(acc + bias_f32[col]) + aux_f[m][col],      gemm_nt_groups
+ *                            frame (t, L) of its clip; kernel KP,  col = g * cpg + n
+ *                            padding KP / 2, K index tap*cpg+ci;
+ *                            W [groups][cpg][KP*cpg]
+ *   GROUPCONV_PLAIN          the same gather                       f32 acc + bias_f32[col]                             gemm_nt_groups
+ *   BIAS_BF16 / _GELU        dense [M][K]                          bf16 act(acc + bias_bf16[n]), bias may be NULL      gemm_nt
+ *   BIASF_BF16 / _GELU       dense                                 bf16 act(acc + bias_f32[n])                         gemm_nt
+ *   STORE_BF16               dense                                 bf16 acc                                            gemm_nt
+ *   RESID_F32 / RESID_F32F   dense                                 f32 out += acc + bias (bf16 / f32)                  gemm_nt
+ *   RESID_BF16               dense                                 bf16 out = bf16(out + bf16(acc))                    gemm_nt
+ *   POS_F32                  dense                                 f32 acc + aux_f[aux_i[m]][n]  (aux_f: [n_t][ld])    gemm_nt
+ *   SWIGLU                   dense; W rows in blocks of 16 gate +  bf16(bf16(silu(bf16 g)) * bf16 u), [M][N / 2]       gemm_nt_swiglu
+ *                            16 up rows
+ * out is [out_rows][ld] (f32 or bf16 by the table; ld = 0: tight, out_rows = 0: M); it is uploaded before the launch, so the residual
+ * forms read it and rows >= M come back as they went in.  form as for qasr_gemm_probe; the grouped launch has the single-buffer form only
+ * (-1 or 1).  Refused with QASR_ERR_INVALID before anything is launched: C % 8 != 0, wide with C < 64, N % 4 != 0, a SWIGLU N that is not
+ * a multiple of 32, form 2 for the grouped launch, M / N / K that contradict the geometry, ld % 4 != 0 or smaller than the written width,
+ * a row offset / frame record / position index that would read outside the given arrays. */
+enum {
+    QASR_GEMM_CASE_CONV = 0, QASR_GEMM_CASE_CONV_PLAIN = 1, QASR_GEMM_CASE_ROWTABLE = 2, QASR_GEMM_CASE_GROUPCONV = 3,
+    QASR_GEMM_CASE_GROUPCONV_PLAIN = 4, QASR_GEMM_CASE_BIAS_BF16 = 5, QASR_GEMM_CASE_BIAS_BF16_GELU = 6, QASR_GEMM_CASE_BIASF_BF16 = 7,
+    QASR_GEMM_CASE_BIASF_BF16_GELU = 8, QASR_GEMM_CASE_STORE_BF16 = 9, QASR_GEMM_CASE_RESID_F32 = 10, QASR_GEMM_CASE_RESID_F32F = 11,
+    QASR_GEMM_CASE_RESID_BF16 = 12, QASR_GEMM_CASE_POS_F32 = 13, QASR_GEMM_CASE_SWIGLU = 14
+};
+typedef struct qasr_gemm_case {
+    int32_t M, N, K;                  /* output rows, weight rows, reduction length (conv: n_img*OH*OW, any, 9*C; groupconv: frames, cpg, KP*cpg) */
+    int32_t ld, out_rows;             /* out's row stride in elements and its row count; 0 = tight / M */
+    int32_t n_img, H, W, C;           /* conv */
+    int32_t wide, hw_major, level;    /* conv: AConv3x3s2W | pixel order m = (img*OH+oh)*OW+ow (1) or (img*OW+ow)*OH+oh (0) | 2 or 3 */
+    int32_t a_len;                    /* rowtable: elements of A */
+    int32_t KP, cpg, groups;          /* groupconv */
+    int32_t n_t;                      /* pos: rows of aux_f */
+} qasr_gemm_case;
+int qasr_gemm_case_probe(qasr_engine* e, int which, int form, const qasr_gemm_case* g, const uint16_t* A, const uint16_t* W,
+                         const void* bias, const int32_t* aux_i, const int64_t* aux_l, const float* aux_f, void* out);
 
 /* ---- utterance-batch data parallelism inside one process ----------------------------------------------------------------------
  * Replaces the sequential file loop of `speech transcribe-batch` (Sources/AudioCLILib/TranscribeBatchCommand.swift:82-93) for a caller

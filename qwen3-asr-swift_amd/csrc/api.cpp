@@ -21,6 +21,57 @@ template <class F> static int on_device(qasr_engine* e, F&& f) {
 
 static bool contains(const std::string& s, const char* sub) { return s.find(sub) != std::string::npos; }
 
+// qasr_gemm_case_probe: why the arguments are refused, or null.  Everything a launch would index with is checked here, on the host.
+static const char* gemm_case_refusal(int which, int form, const qasr_gemm_case& g, const void* bias, const int32_t* aux_i,
+                                     const int64_t* aux_l, const float* aux_f) {
+    if (which < QASR_GEMM_CASE_CONV || which > QASR_GEMM_CASE_SWIGLU) return "gemm case: unknown case id";
+    if (form < -1 || form > 2) return "gemm case: form must be -1, 0, 1 or 2";
+    if (g.M <= 0 || g.N <= 0 || g.K <= 0) return "gemm case: M, N, K must be positive";
+    if (g.K % 8) return "gemm case: K must be a multiple of 8";
+    if (g.N % 4) return "gemm case: N must be a multiple of 4";
+    const bool grouped = which == QASR_GEMM_CASE_GROUPCONV || which == QASR_GEMM_CASE_GROUPCONV_PLAIN;
+    int width = g.N;                                   // columns written per row
+    if (which == QASR_GEMM_CASE_SWIGLU) {
+        if (g.N % 32) return "gemm case: the swiglu width must be a multiple of 32";
+        width = g.N / 2;
+    }
+    if (grouped) {
+        if (form == 2 || form == 0) return "gemm case: the grouped launch has the single-buffer 128 x 128 form only (AGroupConv1d: no_p8)";
+        if (g.KP <= 0 || g.cpg <= 0 || g.groups <= 0 || g.cpg % 8) return "gemm case: groupconv needs KP, groups > 0 and cpg a positive multiple of 8";
+        if (g.N != g.cpg || (long)g.K != (long)g.KP * g.cpg) return "gemm case: groupconv needs N = cpg and K = KP * cpg";
+        width = g.groups * g.cpg;
+        if (!aux_i || !bias || (which == QASR_GEMM_CASE_GROUPCONV && !aux_f)) return "gemm case: groupconv needs frame records, a bias and (EpiPosConv) the residual";
+        for (int m = 0; m < g.M; ++m) {                // frame m is frame t of a clip of L frames that lies inside [0, M)
+            const long t = aux_i[2 * m], L = aux_i[2 * m + 1];
+            if (t < 0 || t >= L || m - t < 0 || m - t + L > g.M) return "gemm case: a frame record points outside the packed frames";
+        }
+    }
+    if (which == QASR_GEMM_CASE_CONV || which == QASR_GEMM_CASE_CONV_PLAIN) {
+        if (g.n_img <= 0 || g.H <= 0 || g.W <= 0 || g.C <= 0 || g.C % 8) return "gemm case: conv needs n_img, H, W > 0 and C a positive multiple of 8";
+        if (g.wide && g.C < 64) return "gemm case: the per-K-tile conv gather needs C >= 64";
+        const long OH = (g.H - 1) / 2 + 1, OW = (g.W - 1) / 2 + 1;
+        if ((long)g.M != g.n_img * OH * OW || (long)g.K != 9L * g.C) return "gemm case: conv needs M = n_img * OH * OW and K = 9 * C";
+        if (!bias) return "gemm case: conv needs a bias";
+        if (which == QASR_GEMM_CASE_CONV && (!aux_i || (g.level != 2 && g.level != 3))) return "gemm case: conv needs valid widths and level 2 or 3";
+    }
+    if (which == QASR_GEMM_CASE_ROWTABLE) {
+        if (!aux_l || !bias || g.a_len <= 0) return "gemm case: rowtable needs offsets, a bias and a_len";
+        for (int m = 0; m < g.M; ++m)
+            if (aux_l[m] < 0 || aux_l[m] % 8 || aux_l[m] + g.K > g.a_len) return "gemm case: a row offset is misaligned or outside A";
+    }
+    if (which == QASR_GEMM_CASE_POS_F32) {
+        if (!aux_i || !aux_f || g.n_t <= 0) return "gemm case: pos needs tok_t, the table and n_t";
+        for (int m = 0; m < g.M; ++m)
+            if (aux_i[m] < 0 || aux_i[m] >= g.n_t) return "gemm case: a position index is outside the table";
+    }
+    if ((which == QASR_GEMM_CASE_BIASF_BF16 || which == QASR_GEMM_CASE_BIASF_BF16_GELU || which == QASR_GEMM_CASE_RESID_F32 ||
+         which == QASR_GEMM_CASE_RESID_F32F) && !bias) return "gemm case: this epilogue needs a bias";
+    if (g.ld < 0 || g.out_rows < 0 || (g.ld && (g.ld % 4 || g.ld < width)) || (g.out_rows && g.out_rows < g.M))
+        return "gemm case: ld must be 0 or a multiple of 4 that holds the written width, out_rows 0 or >= M";
+    if (grouped && g.ld && g.ld != width) return "gemm case: groupconv output is tight ([M][groups * cpg])";
+    return nullptr;
+}
+
 extern "C" {
 
 int qasr_default_config(const char* preset, qasr_config* c) {
@@ -175,6 +226,13 @@ int qasr_gemm_probe(qasr_engine* e, const uint16_t* A, const uint16_t* W, const 
     if (!e || !A || !W || !out || M <= 0 || N <= 0 || K <= 0 || K % 8 || N % 4 || form < -1 || form > 2 || reps <= 0)
         return QASR_ERR_INVALID;
     return on_device(e, [&] { e->impl->gemm_probe(A, W, bias, M, N, K, form, reps, out, avg_ms); });
+}
+
+int qasr_gemm_case_probe(qasr_engine* e, int which, int form, const qasr_gemm_case* g, const uint16_t* A, const uint16_t* W,
+                         const void* bias, const int32_t* aux_i, const int64_t* aux_l, const float* aux_f, void* out) {
+    if (!e || !g || !A || !W || !out) return QASR_ERR_INVALID;
+    if (const char* why = gemm_case_refusal(which, form, *g, bias, aux_i, aux_l, aux_f)) return fail(e, QASR_ERR_INVALID, why);
+    return on_device(e, [&] { e->impl->gemm_case_probe(which, form, *g, A, W, bias, aux_i, aux_l, aux_f, out); });
 }
 
 int qasr_transcribe_batch(qasr_engine* e, const float* const* pcm, const size_t* n, size_t B, int sample_rate,

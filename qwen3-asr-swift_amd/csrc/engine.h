@@ -109,6 +109,9 @@ public:
     void batch_timings(float ms[5], int32_t* n_steps);
     void gemm_probe(const uint16_t* A, const uint16_t* W, const float* bias, int M, int N, int K, int form, int reps, float* out,
                     float* avg_ms);
+    // qasr_gemm_case_probe (csrc/gemm_cases.hip): one operand gather + epilogue pair of the product, launched once on host data
+    void gemm_case_probe(int which, int form, const qasr_gemm_case& g, const uint16_t* A, const uint16_t* W, const void* bias,
+                         const int32_t* aux_i, const int64_t* aux_l, const float* aux_f, void* out);
     void kernel_probe(int which, int reps, float* avg_ms, double* bytes_per_launch);
     int batch_size() const { return batch_; }
     void decode_structure(int* fused_qa, int* chain, int* launches_per_layer);

@@ -448,16 +448,17 @@ inline void gemm_nt_groups(const ALoad& a, const bf16_t* Wt, long ldw, long w_gr
 }
 
 template <class ALoad, class Epi>
-inline void gemm_nt_swiglu(const ALoad& a, const bf16_t* Wt, long ldw, int M, int N, int K, const Epi& epi, hipStream_t s) {
+// form: as for gemm_nt (-1 = the engine's pick)
+inline void gemm_nt_swiglu(const ALoad& a, const bf16_t* Wt, long ldw, int M, int N, int K, const Epi& epi, hipStream_t s, int form = -1) {
     if (M <= 0 || N <= 0) return;
     if (N % 32 != 0) throw std::invalid_argument("swiglu gemm: fused width must be a multiple of 32");
-    if (gemm_use_p8(M, N)) {
+    if (form == 2 || (form < 0 && gemm_use_p8(M, N))) {
         hipLaunchKernelGGL((gemm_nt_p8_kernel<ALoad, Epi, 1>), dim3(gemm_p8_grid(M, N)), dim3(512), 0, s, a, Wt, ldw, M, N, K, epi,
                            gemm_zero_block());
         return;
     }
     int grid = cdiv(M, GEMM_BM) * cdiv(N, GEMM_BN);
-    if (gemm_nbuf(grid) == 1)
+    if (form == 1 || (form != 0 && gemm_nbuf(grid) == 1))
         hipLaunchKernelGGL((gemm_nt_glds1_kernel<ALoad, Epi, 1>), dim3(grid), dim3(GEMM_THREADS), 0, s, a, Wt, ldw, M, N, K, epi,
                            gemm_zero_block(), gemm_tile_rows(M, N));
     else

@@ -129,6 +129,11 @@ class ScVadVtable(C.Structure):
                 ("input_sample_rate", SC_RATE_FN), ("chunk_size", VAD_CHUNK_FN)]
 
 
+class QasrGemmCase(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("M", "N", "K", "ld", "out_rows", "n_img", "H", "W", "C", "wide", "hw_major", "level", "a_len",
+                                         "KP", "cpg", "groups", "n_t")]
+
+
 _P = C.POINTER
 _F = _P(C.c_float)
 _I = _P(C.c_int32)
@@ -166,6 +171,8 @@ SIGNATURES = {
     "qasr_batch_timings": (C.c_int, [_E, _F, _I]),
     "qasr_kernel_probe": (C.c_int, [_E, C.c_int, C.c_int, _F, _P(C.c_double)]),
     "qasr_gemm_probe": (C.c_int, [_E, _P(C.c_uint16), _P(C.c_uint16), _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F, _F]),
+    "qasr_gemm_case_probe": (C.c_int, [_E, C.c_int, C.c_int, _P(QasrGemmCase), _P(C.c_uint16), _P(C.c_uint16), C.c_void_p, _I, _P(C.c_int64),
+                                       _F, C.c_void_p]),
     "qasr_set_shared_device": (C.c_int, [_E, C.c_int]),
     "qasr_decode_structure": (C.c_int, [_E, _P(C.c_int), _P(C.c_int), _P(C.c_int)]),
     "qasr_set_tuning": (C.c_int, [C.c_char_p, C.c_int]),
