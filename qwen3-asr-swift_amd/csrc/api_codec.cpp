@@ -99,20 +99,9 @@ int qasr_codec_create(int device, const char* model_dir, int max_windows, qasr_e
     std::vector<bool> embed_stored;
     try {                                              // geometry, every key, shape and dtype before any HIP call
         g = codec_read_geometry(model_dir, WHO);
-        try { codec_check_geometry(g); }
+        try { codec_check_geometry(g, WHO); }
         catch (const std::exception& ex) { throw WeightLoadError(QASR_ERR_INVALID, ex.what()); }
-        {   // which form each codebook is stored in (TTSWeightLoading.swift:286-300)
-            std::unique_ptr<SafeTensorsDir> st;
-            try { st = std::make_unique<SafeTensorsDir>(model_dir, "model.safetensors"); }
-            catch (const std::exception& ex) { throw WeightLoadError(QASR_ERR_IO, std::string(WHO) + ": " + ex.what()); }
-            for (int q = 0; q < g.quantizers; ++q) {
-                const std::string p = codec_codebook_prefix(q);
-                const bool e = st->entries.count(p + ".embed") > 0;
-                if (!e && !st->entries.count(p + ".embedding_sum") && !st->entries.count(p + ".cluster_usage"))
-                    throw WeightLoadError(QASR_ERR_IO, std::string(WHO) + ": missing tensor " + p + ".embed");
-                embed_stored.push_back(e);
-            }
-        }
+        embed_stored = codec_codebooks_stored(model_dir, WHO, "decoder", g.quantizers);
         w = load_checked_f32(model_dir, WHO, codec_tensor_shapes(g, embed_stored), false);
     } catch (const WeightLoadError& ex) { return fail<qasr_codec>(nullptr, ex.code, ex.what()); }
     catch (const std::exception& ex) { return fail<qasr_codec>(nullptr, QASR_ERR_IO, ex.what()); }

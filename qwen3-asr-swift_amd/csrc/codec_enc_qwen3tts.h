@@ -17,11 +17,8 @@ namespace qasr {
 constexpr int CENC_LEVELS = 7, CENC_STAGES = 8, CENC_MAX_CLIPS = 1024;
 constexpr long CENC_DEFAULT_SAMPLES = 720000, CENC_MAX_SAMPLES = 1L << 24;
 
-// codec_check_geometry with the encoder's name in the message
-void codec_enc_check_geometry(const CodecGeom& g);
 // key -> shape of every tensor the encoder reads (encoder.*); embed_stored as for codec_tensor_shapes
-std::vector<std::pair<std::string, std::vector<int64_t>>> codec_enc_tensor_shapes(const CodecGeom& g, const std::vector<bool>& embed_stored);
-std::string codec_enc_codebook_prefix(int q);
+CodecShapes codec_enc_tensor_shapes(const CodecGeom& g, const std::vector<bool>& embed_stored);
 // the six strides in the order they are applied: upsample_rates reversed, then upsampling_ratios reversed
 void codec_enc_strides(const CodecGeom& g, int s[6]);
 // rows of a clip of n samples at every rate: len[0] = n, len[l + 1] = ceil(len[l] / stride[l]); len[6] = frames
@@ -47,12 +44,10 @@ class CodecEncQwen3TTS {
     hipStream_t stream() const { return work_; }
 
   private:
-    struct Gemm { size_t wt = 0, bias = 0; int K = 0, N = 0, Cin = 0, taps = 1; bool has_bias = false; };
-    struct Snake { size_t a = 0, b = 0; };
-    struct Layer { size_t n1, n2, ls1, ls2; Gemm qkv, o, gu, down; };
+    using Gemm = CodecGemm;
+    using Snake = CodecSnake;
     struct Down { Gemm pw1, pw2, sconv; size_t dw, dwb, lnw, lnb, gamma; };
-    struct Unit { Snake s1, s2; Gemm c1, c2; };
-    struct Block { Unit u[3]; Snake s; Gemm sconv; };
+    struct Block { CodecUnit u[3]; Snake s; Gemm sconv; };
     void check_loaded() const;
     void pass(const CodecEncClip* c, int n, Mode mode);
     void plan(const CodecEncClip* c, int n);
@@ -81,7 +76,7 @@ class CodecEncQwen3TTS {
     Gemm enc5_, post_conv_, in_proj_, rvq_;
     Block blocks_[4];
     Down down_[2];
-    std::vector<Layer> layers_;
+    std::vector<CodecLayer> layers_;
     // the pass
     int n_clips_ = 0, n_tiles_ = 0;
     long M_[CENC_LEVELS] = {};

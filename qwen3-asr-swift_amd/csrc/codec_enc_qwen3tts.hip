@@ -6,21 +6,22 @@
 // rows (start[l][clips] = the level's row count) and a kernel finds a row's clip by bisection.  Row and element indices are 64-bit.
 // Launches of a pass:
 //   cenc_in_kernel      the 1 -> C k = 7 conv as a 7-term dot, one thread per output element, 96-wide rows stored coalesced
-//   cenc_gemm_kernel    codec_gemm_kernel's 64 x 64 f32 tile and k order (taps outer, channels inner, one fmaf chain per output) with a
-//                       stride: the A element of (output row t of a clip, tap j, channel c) is x[t s - (taps - 1 - j) dilation][c] of
-//                       the same clip one level up, exact zero before the clip's first row, SnakeBeta optionally applied as it is
-//                       loaded; the same epilogues.  Runs every conv but the first, every Linear and the RVQ projections.
-//   cenc_rms_kernel, cenc_dwln_kernel   RMSNorm; depthwise k = 7 causal conv + LayerNorm; one workgroup per row
+//   codec_gemm_kernel   the decoder's GEMM (codec_shared.h: 64 x 64 f32 tile, k = taps outer, channels inner, one fmaf chain per output,
+//                       the same epilogues) with the row locator ClipRows, which adds a stride: the A element of (output row t of a
+//                       clip, tap j, channel c) is x[t s - (taps - 1 - j) dilation][c] of the same clip one level up, exact zero before
+//                       the clip's first row, SnakeBeta optionally applied as it is loaded.  Runs every conv but the first, every
+//                       Linear and the RVQ projections.
+//   codec_rms_kernel, codec_dwln_kernel   (codec_shared.h) RMSNorm; depthwise k = 7 causal conv + LayerNorm; one workgroup per row
 //   cenc_attn_kernel    unmasked attention over a whole clip, flash-style: a workgroup owns 32 queries of one clip and one head, streams
 //                       the clip's K / V in tiles of 32 through LDS (RoPE on the way in, rotate-halves, positions from 0) with a running
 //                       max and sum
 //   cenc_vq_kernel      ResidualVectorQuantizer.encode: a workgroup owns 64 frames of one quantizer and walks its codebooks in order;
 //                       per codebook the [64][size] score GEMM in the same tile, the distance in the reference's expanded form, a
 //                       (value, index) argmin, then the residual update in place
-// Summation order: every GEMM output is one thread's fmaf chain over k = 0..K-1; the norms as in the decoder; an
-// attention output row is accumulated over the clip's keys in order, tile after tile from the clip's first frame.  No reduction crosses a
-// clip and nothing depends on a clip's place, so a clip's latent and codes are the same bits alone, in any batch and under any split
-// into passes.
+// Summation order: every GEMM output is one thread's fmaf chain over k = 0..K-1; the norms are the decoder's
+// kernels; an attention output row is accumulated over the clip's keys in order, tile after tile from the clip's first frame.  No
+// reduction crosses a clip and nothing depends on a clip's place, so a clip's latent and codes are the same bits alone, in any batch and
+// under any split into passes.
 #include "codec_enc_qwen3tts.h"
 #include <algorithm>
 #include <cmath>
@@ -29,21 +30,6 @@
 namespace qasr {
 
 // ---- geometry, keys, lengths (host) -------------------------------------------------------------------------------------------------
-void codec_enc_check_geometry(const CodecGeom& g) {
-    try { codec_check_geometry(g); }
-    catch (const std::invalid_argument& ex) {
-        std::string m = ex.what();
-        const std::string from = "speech tokenizer decoder";
-        if (m.compare(0, from.size(), from) == 0) m = "speech tokenizer encoder" + m.substr(from.size());
-        throw std::invalid_argument(m);
-    }
-}
-
-std::string codec_enc_codebook_prefix(int q) {
-    return q == 0 ? std::string("encoder.quantizer.rvq_first.vq.layers.0._codebook")
-                  : "encoder.quantizer.rvq_rest.vq.layers." + std::to_string(q - 1) + "._codebook";
-}
-
 void codec_enc_strides(const CodecGeom& g, int s[6]) {
     for (int i = 0; i < 4; ++i) s[i] = g.rates[3 - i];
     s[4] = g.ratios[1]; s[5] = g.ratios[0];
@@ -56,15 +42,15 @@ void codec_enc_lengths(const CodecGeom& g, long n, long len[CENC_LEVELS]) {
     for (int l = 0; l < 6; ++l) len[l + 1] = (len[l] + s[l] - 1) / s[l];
 }
 
-std::vector<std::pair<std::string, std::vector<int64_t>>> codec_enc_tensor_shapes(const CodecGeom& g, const std::vector<bool>& embed_stored) {
-    std::vector<std::pair<std::string, std::vector<int64_t>>> s;
+CodecShapes codec_enc_tensor_shapes(const CodecGeom& g, const std::vector<bool>& embed_stored) {
+    CodecShapes s;
     auto add = [&](const std::string& k, std::vector<int64_t> sh) { s.emplace_back(k, std::move(sh)); };
-    const int64_t L = g.latent, H = g.hidden, Dd = g.decoder_dim, D = g.codebook_dim, A = (int64_t)g.heads * g.head_dim;
+    const int64_t L = g.latent, H = g.hidden, Dd = g.decoder_dim, D = g.codebook_dim;
     int st[6];
     codec_enc_strides(g, st);
     for (int q = 0; q < g.quantizers; ++q) {
         const int64_t n = q == 0 ? g.semantic_size : g.acoustic_size;
-        const std::string p = codec_enc_codebook_prefix(q);
+        const std::string p = codec_codebook_prefix("encoder", q);
         if (embed_stored[q]) add(p + ".embed", {n, D});
         else { add(p + ".embedding_sum", {n, D}); add(p + ".cluster_usage", {n}); }
     }
@@ -96,53 +82,13 @@ std::vector<std::pair<std::string, std::vector<int64_t>>> codec_enc_tensor_shape
         add(p + "1.conv.weight", {L, L, 2 * st[4 + i]}); add(p + "1.conv.bias", {L});
     }
     add("encoder.post_conv.conv.weight", {L, L, 3}); add("encoder.post_conv.conv.bias", {L});
-    const std::string P = "encoder.pre_transformer.";
-    add(P + "input_proj.weight", {H, L}); add(P + "input_proj.bias", {H});
-    add(P + "output_proj.weight", {L, H}); add(P + "output_proj.bias", {L});      // read by the reference's loader, never applied (:100)
-    add(P + "norm.weight", {H});
-    for (int l = 0; l < g.layers; ++l) {
-        const std::string p = P + "layers." + std::to_string(l) + ".";
-        for (const char* k : {"q_proj", "k_proj", "v_proj"}) add(p + "self_attn." + k + ".weight", {A, H});
-        add(p + "self_attn.o_proj.weight", {H, A});
-        add(p + "input_layernorm.weight", {H}); add(p + "post_attention_layernorm.weight", {H});
-        add(p + "mlp.gate_proj.weight", {2 * H, H}); add(p + "mlp.up_proj.weight", {2 * H, H}); add(p + "mlp.down_proj.weight", {H, 2 * H});
-        add(p + "self_attn_layer_scale.scale", {H}); add(p + "mlp_layer_scale.scale", {H});
-    }
+    // output_proj is read by the reference's loader, never applied (:100)
+    codec_pre_transformer_shapes(s, "encoder.pre_transformer.", g);
     return s;
 }
 
 // ---- kernels ------------------------------------------------------------------------------------------------------------------------
-constexpr int CG_THREADS = 256, CG_T = 64, CG_K = 16, ROW_THREADS = 256, AT_Q = 32, AT_K = 32;
-enum { E_LIN = 0, E_GELU = 1, E_RES = 2, E_LSRES = 3, E_SWIGLU = 4 };
-
-// x + (1 / exp(beta)) sin^2(exp(alpha) x) with a = exp(alpha), b = 1 / exp(beta) formed at load (SpeechTokenizerDecoder.swift:105-110)
-__device__ __forceinline__ float cenc_snake(float x, float a, float b) {
-    const float s = sinf(a * x);
-    return x + b * (s * s);
-}
-
-// the clip that owns row m: start[0] = 0 < start[1] < .. < start[n] = rows, every clip holds at least one row
-__device__ __forceinline__ int cenc_clip_of(const int* __restrict__ start, int n, long m) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((long)start[mid] <= m) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// sum over the workgroup's 256 values in a fixed tree; every thread gets it.  Ends with a barrier that also frees `red`.
-__device__ __forceinline__ float cenc_block_sum(float v, float* red, int tid) {
-    red[tid] = v;
-    __syncthreads();
-    for (int s = ROW_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = red[tid] + red[tid + s];
-        __syncthreads();
-    }
-    const float r = red[0];
-    __syncthreads();
-    return r;
-}
+constexpr int AT_Q = 32, AT_K = 32;
 
 // y[m][c] = b[c] + sum_j w[j][c] x[m - (6 - j)] inside the clip (:224); x [M], w [7][C], y [M][C]; one thread per (m, c)
 __global__ __launch_bounds__(ROW_THREADS) void cenc_in_kernel(const float* __restrict__ x, long M, int C, const int* __restrict__ start,
@@ -152,7 +98,7 @@ __global__ __launch_bounds__(ROW_THREADS) void cenc_in_kernel(const float* __res
     if (e >= M * C) return;
     const long m = e / C;
     const int c = (int)(e - m * C);
-    const long first = start[cenc_clip_of(start, nclips, m)];
+    const long first = start[clip_of(start, nclips, m)];
     float acc = 0.0f;
 #pragma unroll
     for (int j = 0; j < 7; ++j) {
@@ -160,137 +106,6 @@ __global__ __launch_bounds__(ROW_THREADS) void cenc_in_kernel(const float* __res
         acc = fmaf(src >= first ? x[src] : 0.0f, w[j * C + c], acc);
     }
     y[e] = acc + b[c];
-}
-
-// C = epilogue(sum_k A(m, k) Wt[k][n]), k = j C_in + c <-> x[first_in + (m - first_out) stride - (taps - 1 - j) dil][c], zero before
-// first_in.  A [rows of the input level][C_in], Wt [K][N]; ostart / istart: the first rows of the clips at the output / input level
-// (nullptr: rows are independent, taps = 1).  E_SWIGLU: columns 2 i, 2 i + 1 are gate i, up i; C [M][N / 2].
-template <bool SNAKE, int EPI>
-__global__ __launch_bounds__(CG_THREADS) void cenc_gemm_kernel(const float* __restrict__ A, long M, int Cin, int taps, int dil, int stride,
-                                                               const int* __restrict__ ostart, const int* __restrict__ istart, int nclips,
-                                                               const float* __restrict__ Wt, int K, int N, const float* __restrict__ bias,
-                                                               const float* __restrict__ sa, const float* __restrict__ sb,
-                                                               const float* __restrict__ ls, const float* R, float* C, int ldc) {
-    __shared__ __attribute__((aligned(16))) float As[CG_K][CG_T + 4];
-    __shared__ __attribute__((aligned(16))) float Bs[CG_K][CG_T];
-    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    const long m0 = (long)blockIdx.x * CG_T;
-    const int n0 = blockIdx.y * CG_T;
-    long base[4], first[4];                            // input row of the last tap, and the clip's first input row, per A row loaded
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const long m = m0 + ((tid + r * CG_THREADS) >> 4);
-        base[r] = m; first[r] = 0;
-        if (ostart && m < M) {
-            const int clip = cenc_clip_of(ostart, nclips, m);
-            first[r] = istart[clip];
-            base[r] = first[r] + (m - ostart[clip]) * stride;
-        }
-    }
-    float acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[i][q] = 0.0f;
-    for (int k0 = 0; k0 < K; k0 += CG_K) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int idx = tid + r * CG_THREADS, row = idx >> 4, kk = idx & 15, k = k0 + kk;
-            float v = 0.0f;                            // rows past M, inputs past K and rows before the clip add exact zeros
-            if (m0 + row < M && k < K) {
-                const int j = k / Cin, c = k - j * Cin;
-                const long src = base[r] - (long)(taps - 1 - j) * dil;
-                if (src >= first[r]) {
-                    v = A[src * Cin + c];
-                    if (SNAKE) v = cenc_snake(v, sa[c], sb[c]);
-                }
-            }
-            As[kk][row] = v;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int idx = tid + r * CG_THREADS, kk = idx >> 6, col = idx & 63, k = k0 + kk, n = n0 + col;
-            Bs[kk][col] = (k < K && n < N) ? Wt[(size_t)k * N + n] : 0.0f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < CG_K; ++kk) {
-            const float4 a = lds_read_f4(&As[kk][ty * 4]);
-            const float4 bq = lds_read_f4(&Bs[kk][tx * 4]);
-            const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {bq.x, bq.y, bq.z, bq.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[i][q] = fmaf(av[i], bv[q], acc[i][q]);
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const long m = m0 + ty * 4 + i;
-        if (m >= M) continue;
-        if (EPI == E_SWIGLU) {                         // silu(gate) * up (SpeechTokenizerDecoder.swift:340)
-#pragma unroll
-            for (int q = 0; q < 4; q += 2) {
-                const int n = n0 + tx * 4 + q;
-                if (n + 1 >= N) continue;
-                const float g = acc[i][q];
-                C[m * ldc + (n >> 1)] = (g / (1.0f + expf(-g))) * acc[i][q + 1];
-            }
-            continue;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int n = n0 + tx * 4 + q;
-            if (n >= N) continue;
-            float v = acc[i][q];
-            if (bias) v = v + bias[n];
-            if (EPI == E_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
-            if (EPI == E_RES) v = v + R[m * ldc + n];
-            if (EPI == E_LSRES) v = v * ls[n] + R[m * ldc + n];
-            C[m * ldc + n] = v;
-        }
-    }
-}
-
-// y = x / sqrt(mean(x^2) + eps) * w, one workgroup per row
-__global__ __launch_bounds__(ROW_THREADS) void cenc_rms_kernel(const float* __restrict__ x, int C, const float* __restrict__ w, float eps,
-                                                               float* __restrict__ y) {
-    __shared__ float red[ROW_THREADS];
-    const long m = blockIdx.x;
-    const int tid = threadIdx.x;
-    float p = 0.0f;
-    for (int c = tid; c < C; c += ROW_THREADS) { const float v = x[m * C + c]; p = p + v * v; }
-    const float inv = 1.0f / sqrtf(cenc_block_sum(p, red, tid) / (float)C + eps);
-    for (int c = tid; c < C; c += ROW_THREADS) y[m * C + c] = (x[m * C + c] * inv) * w[c];
-}
-
-// depthwise causal conv k = 7 (w [7][C], + bias) then LayerNorm eps 1e-5, one workgroup per row; C <= 4096 (:156-160 of the decoder)
-__global__ __launch_bounds__(ROW_THREADS) void cenc_dwln_kernel(const float* __restrict__ x, int C, const int* __restrict__ start, int nclips,
-                                                                const float* __restrict__ w, const float* __restrict__ b,
-                                                                const float* __restrict__ lnw, const float* __restrict__ lnb,
-                                                                float* __restrict__ y) {
-    __shared__ float red[ROW_THREADS];
-    __shared__ float val[4096];
-    const long m = blockIdx.x, first = start[cenc_clip_of(start, nclips, m)];
-    const int tid = threadIdx.x;
-    float p = 0.0f;
-    for (int c = tid; c < C; c += ROW_THREADS) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 7; ++j) {
-            const long src = m - (6 - j);
-            if (src >= first) acc = acc + x[src * C + c] * w[j * C + c];
-        }
-        acc = acc + b[c];
-        val[c] = acc;
-        p = p + acc;
-    }
-    const float mu = cenc_block_sum(p, red, tid) / (float)C;
-    float q = 0.0f;
-    for (int c = tid; c < C; c += ROW_THREADS) { const float d = val[c] - mu; q = q + d * d; }
-    const float inv = 1.0f / sqrtf(cenc_block_sum(q, red, tid) / (float)C + 1e-5f);
-    for (int c = tid; c < C; c += ROW_THREADS) y[m * C + c] = ((val[c] - mu) * inv) * lnw[c] + lnb[c];
 }
 
 // qkv [M][3 A] (A = heads x 64); tiles[b] = (the clip's first row, its frames, the tile's first query); rope [positions][32] (cos, sin);
@@ -459,45 +274,17 @@ __global__ __launch_bounds__(CG_THREADS) void cenc_vq_kernel(float* r, long M, i
 }
 
 // ---- weights ------------------------------------------------------------------------------------------------------------------------
-namespace {
-struct Builder {
-    std::vector<float> h;
-    const CheckedWeights& w;
-    explicit Builder(const CheckedWeights& cw) : w(cw) {}
-    const std::vector<float>& t(const std::string& k) const { return w.t.at(k); }
-    size_t take(size_t n) { const size_t at = h.size(); h.resize(at + ((n + 3) & ~(size_t)3), 0.0f); return at; }
-    size_t vec(const std::string& k) { const auto& v = t(k); const size_t at = take(v.size()); std::copy(v.begin(), v.end(), h.begin() + at); return at; }
-};
-}  // namespace
-
 CodecEncQwen3TTS::CodecEncQwen3TTS(int device, const CheckedWeights& cw, const CodecGeom& g, const std::vector<bool>& embed_stored,
                                    long max_samples, hipStream_t work)
     : device_(device), g_(g), max_samples_(max_samples) {
-    codec_enc_check_geometry(g);
+    codec_check_geometry(g, "speech tokenizer encoder");
     if (max_samples < 1 || max_samples > CENC_MAX_SAMPLES) throw std::invalid_argument("speech tokenizer encoder: max_samples in 1..2^24");
     param_bytes_ = cw.disk_bytes;
     Builder b(cw);
     const int L = g.latent, H = g.hidden, Dd = g.decoder_dim, D = g.codebook_dim, A = g.heads * g.head_dim, I = 2 * H, Q = g.quantizers;
     codec_enc_strides(g, stride_);
-    // Wt[j C_in + c][n] = W[n][c][j] of a conv [out][in][k] (k = 1: a Linear [out][in])
-    auto conv = [&](const std::string& key, int Cout, int Cin, int k, bool bias) {
-        Gemm gm; gm.K = k * Cin; gm.N = Cout; gm.Cin = Cin; gm.taps = k;
-        const auto& W = b.t(key + ".weight");
-        gm.wt = b.take((size_t)gm.K * gm.N);
-        for (int n = 0; n < Cout; ++n)
-            for (int c = 0; c < Cin; ++c)
-                for (int j = 0; j < k; ++j) b.h[gm.wt + ((size_t)j * Cin + c) * Cout + n] = W[((size_t)n * Cin + c) * k + j];
-        gm.has_bias = bias;
-        if (bias) gm.bias = b.vec(key + ".bias");
-        return gm;
-    };
-    auto snake = [&](const std::string& key) {          // exp(alpha) | 1 / exp(beta), in f32 as the reference forms them
-        Snake s;
-        const auto &al = b.t(key + ".alpha"), &be = b.t(key + ".beta");
-        s.a = b.take(al.size()); s.b = b.take(be.size());
-        for (size_t i = 0; i < al.size(); ++i) { b.h[s.a + i] = expf(al[i]); b.h[s.b + i] = 1.0f / expf(be[i]); }
-        return s;
-    };
+    auto conv = [&](const std::string& key, int Cout, int Cin, int k, bool bias) { return codec_pack_conv(b, key, Cout, Cin, k, bias); };
+    auto snake = [&](const std::string& key) { return codec_pack_snake(b, key); };
     // codebooks (TTSWeightLoading+Encoder.swift:121-139) as [S][D], transposed [D][S] for the score GEMM, and |c|^2 in f32
     for (int chain = 0; chain < 2; ++chain) {
         const int n = chain ? g.acoustic_size : g.semantic_size, stages = chain ? Q - 1 : 1;
@@ -506,14 +293,8 @@ CodecEncQwen3TTS::CodecEncQwen3TTS(int device, const CheckedWeights& cw, const C
         csq_[chain] = b.take((size_t)stages * n);
         for (int st = 0; st < stages; ++st) {
             const int q = chain + st;
-            const std::string p = codec_enc_codebook_prefix(q);
-            float* e = b.h.data() + cb_[chain] + (size_t)st * n * D;
-            if (embed_stored[q]) std::copy(b.t(p + ".embed").begin(), b.t(p + ".embed").end(), e);
-            else {
-                const auto &sum = b.t(p + ".embedding_sum"), &use = b.t(p + ".cluster_usage");
-                for (int i = 0; i < n; ++i)
-                    for (int d = 0; d < D; ++d) e[(size_t)i * D + d] = sum[(size_t)i * D + d] / std::max(use[i], 1e-7f);
-            }
+            codec_pack_codebook(b, cb_[chain] + (size_t)st * n * D, codec_codebook_prefix("encoder", q), embed_stored[q], n, D);
+            const float* e = b.h.data() + cb_[chain] + (size_t)st * n * D;
             float* et = b.h.data() + cbt_[chain] + (size_t)st * n * D;
             float* sq = b.h.data() + csq_[chain] + (size_t)st * n;
             for (int i = 0; i < n; ++i) {
@@ -534,13 +315,8 @@ CodecEncQwen3TTS::CodecEncQwen3TTS(int device, const CheckedWeights& cw, const C
             }
     }
     int c = Dd / 16;
-    {   // [C][1][7] -> [7][C]
-        const auto& W = b.t("encoder.encoder.0.conv.weight");
-        in_w_ = b.take((size_t)7 * c);
-        for (int ch = 0; ch < c; ++ch)
-            for (int j = 0; j < 7; ++j) b.h[in_w_ + (size_t)j * c + ch] = W[(size_t)ch * 7 + j];
-        in_b_ = b.vec("encoder.encoder.0.conv.bias");
-    }
+    in_w_ = codec_pack_taps7(b, "encoder.encoder.0.conv.weight", c);
+    in_b_ = b.vec("encoder.encoder.0.conv.bias");
     width_[0] = c;
     for (int k = 0; k < 4; ++k) {
         const std::string p = "encoder.encoder." + std::to_string(k + 1) + ".block.";
@@ -561,10 +337,7 @@ CodecEncQwen3TTS::CodecEncQwen3TTS(int device, const CheckedWeights& cw, const C
     for (int i = 0; i < 2; ++i) {
         const std::string p = "encoder.downsample." + std::to_string(i) + ".";
         Down& u = down_[i];
-        const auto& dw = b.t(p + "0.dwconv.conv.weight");                // [L][1][7] -> [7][L]
-        u.dw = b.take((size_t)7 * L);
-        for (int ch = 0; ch < L; ++ch)
-            for (int j = 0; j < 7; ++j) b.h[u.dw + (size_t)j * L + ch] = dw[(size_t)ch * 7 + j];
+        u.dw = codec_pack_taps7(b, p + "0.dwconv.conv.weight", L);
         u.dwb = b.vec(p + "0.dwconv.conv.bias");
         u.lnw = b.vec(p + "0.norm.weight"); u.lnb = b.vec(p + "0.norm.bias");
         u.pw1 = conv(p + "0.pwconv1", 4 * L, L, 1, true);
@@ -576,32 +349,8 @@ CodecEncQwen3TTS::CodecEncQwen3TTS(int device, const CheckedWeights& cw, const C
     const std::string P = "encoder.pre_transformer.";
     in_proj_ = conv(P + "input_proj", H, L, 1, true);
     norm_ = b.vec(P + "norm.weight");
-    for (int l = 0; l < g.layers; ++l) {
-        const std::string p = P + "layers." + std::to_string(l) + ".";
-        Layer ly;
-        ly.n1 = b.vec(p + "input_layernorm.weight"); ly.n2 = b.vec(p + "post_attention_layernorm.weight");
-        ly.ls1 = b.vec(p + "self_attn_layer_scale.scale"); ly.ls2 = b.vec(p + "mlp_layer_scale.scale");
-        ly.qkv.K = H; ly.qkv.N = 3 * A; ly.qkv.Cin = H;
-        ly.qkv.wt = b.take((size_t)H * 3 * A);
-        int part = 0;
-        for (const char* k : {"q_proj", "k_proj", "v_proj"}) {
-            const auto& W = b.t(p + "self_attn." + k + ".weight");
-            for (int n = 0; n < A; ++n)
-                for (int ch = 0; ch < H; ++ch) b.h[ly.qkv.wt + (size_t)ch * 3 * A + part * A + n] = W[(size_t)n * H + ch];
-            ++part;
-        }
-        ly.o = conv(p + "self_attn.o_proj", H, A, 1, false);
-        ly.gu.K = H; ly.gu.N = 2 * I; ly.gu.Cin = H;
-        ly.gu.wt = b.take((size_t)H * 2 * I);
-        const auto &Wg = b.t(p + "mlp.gate_proj.weight"), &Wu = b.t(p + "mlp.up_proj.weight");
-        for (int n = 0; n < I; ++n)
-            for (int ch = 0; ch < H; ++ch) {
-                b.h[ly.gu.wt + (size_t)ch * 2 * I + 2 * n] = Wg[(size_t)n * H + ch];
-                b.h[ly.gu.wt + (size_t)ch * 2 * I + 2 * n + 1] = Wu[(size_t)n * H + ch];
-            }
-        ly.down = conv(p + "mlp.down_proj", H, I, 1, false);
-        layers_.push_back(ly);
-    }
+    for (int l = 0; l < g.layers; ++l)
+        layers_.push_back(codec_pack_layer(b, P + "layers." + std::to_string(l) + ".", H, A));
     // rows a pass can hold at every level: a clip of n samples has ceil(n / rate) rows, so max_samples / rate + one per clip
     long rate = 1;
     size_t big = 0;
@@ -612,13 +361,7 @@ CodecEncQwen3TTS::CodecEncQwen3TTS(int device, const CheckedWeights& cw, const C
         if (l < 6) rate *= stride_[l];
     }
     const long max_frames = (max_samples + rate - 1) / rate;
-    rope_ = b.take((size_t)max_frames * 32 * 2);       // MLXNN.RoPE base 10000 over all 64 dimensions, positions 0 .. a clip's last frame
-    for (long t = 0; t < max_frames; ++t)
-        for (int d = 0; d < 32; ++d) {
-            const float inv = (float)pow(10000.0, -(double)d / 32.0), ang = (float)t * inv;
-            b.h[rope_ + ((size_t)t * 32 + d) * 2] = (float)cos((double)ang);
-            b.h[rope_ + ((size_t)t * 32 + d) * 2 + 1] = (float)sin((double)ang);
-        }
+    rope_ = codec_pack_rope(b, max_frames);            // positions 0 .. a clip's last frame
     QASR_HIP(hipSetDevice(device_));
     QASR_HIP(hipStreamCreateWithFlags(&own_, hipStreamNonBlocking));
     work_ = work ? work : own_;
@@ -691,9 +434,9 @@ template <bool SNAKE, int EPI>
 void CodecEncQwen3TTS::gemm(const Gemm& gm, const float* A, long M, int dil, int stride, int level, int in_level, const Snake* sn,
                             const float* ls, const float* R, float* C, int ldc) {
     const dim3 grid((unsigned)cdiv(M, CG_T), (unsigned)cdiv(gm.N, CG_T));
-    hipLaunchKernelGGL((cenc_gemm_kernel<SNAKE, EPI>), grid, dim3(CG_THREADS), 0, work_, A, M, gm.Cin, gm.taps, dil, stride,
-                       level < 0 ? (const int*)nullptr : starts(level), level < 0 ? (const int*)nullptr : starts(in_level), n_clips_,
-                       W(gm.wt), gm.K, gm.N, gm.has_bias ? W(gm.bias) : (const float*)nullptr, sn ? W(sn->a) : (const float*)nullptr,
+    const ClipRows rows{level < 0 ? nullptr : starts(level), level < 0 ? nullptr : starts(in_level), n_clips_, stride};
+    hipLaunchKernelGGL((codec_gemm_kernel<ClipRows, SNAKE, EPI>), grid, dim3(CG_THREADS), 0, work_, A, M, gm.Cin, gm.taps, dil, rows,
+                       W(gm.wt), gm.K, gm.N, gm.has_bias ? W(gm.bias) : (const float*)nullptr, gm.N, sn ? W(sn->a) : (const float*)nullptr,
                        sn ? W(sn->b) : (const float*)nullptr, ls, R, C, ldc);
 }
 
@@ -722,8 +465,8 @@ void CodecEncQwen3TTS::dev_convs() {
     for (int i = 0; i < 2; ++i) {                      // ConvNeXt, strided conv (:233-236)
         const Down& u = down_[i];
         const int lv = 4 + i;
-        hipLaunchKernelGGL(cenc_dwln_kernel, dim3((unsigned)M_[lv]), dim3(ROW_THREADS), 0, work_, a, L, starts(lv), n_clips_, W(u.dw), W(u.dwb),
-                           W(u.lnw), W(u.lnb), t);
+        hipLaunchKernelGGL(codec_dwln_kernel<ClipRows>, dim3((unsigned)M_[lv]), dim3(ROW_THREADS), 0, work_, a, L,
+                           ClipRows{starts(lv), starts(lv), n_clips_, 1}, W(u.dw), W(u.dwb), W(u.lnw), W(u.lnb), t);
         gemm<false, E_GELU>(u.pw1, t, M_[lv], 1, 1, -1, -1, nullptr, nullptr, nullptr, o, 4 * L);
         gemm<false, E_LSRES>(u.pw2, o, M_[lv], 1, 1, -1, -1, nullptr, W(u.gamma), a, a, L);
         gemm<false, E_LIN>(u.sconv, a, M_[lv + 1], 1, stride_[lv], lv + 1, lv, nullptr, nullptr, nullptr, t, L);
@@ -741,17 +484,17 @@ void CodecEncQwen3TTS::dev_transformer() {
     const long M = M_[6];
     float *x = d_x_.as<float>(), *h = d_h_.as<float>(), *qkv = d_qkv_.as<float>(), *att = d_att_.as<float>(), *gg = d_g_.as<float>();
     gemm<false, E_LIN>(in_proj_, conv_out_, M, 1, 1, -1, -1, nullptr, nullptr, nullptr, x, H);
-    for (const Layer& ly : layers_) {
-        hipLaunchKernelGGL(cenc_rms_kernel, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(ly.n1), g_.eps, h);
+    for (const CodecLayer& ly : layers_) {
+        hipLaunchKernelGGL(codec_rms_kernel<>, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(ly.n1), g_.eps, h);
         gemm<false, E_LIN>(ly.qkv, h, M, 1, 1, -1, -1, nullptr, nullptr, nullptr, qkv, 3 * A);
         hipLaunchKernelGGL(cenc_attn_kernel, dim3((unsigned)n_tiles_, (unsigned)g_.heads), dim3(ROW_THREADS), 0, work_, qkv,
                            d_tiles_.as<int4>(), reinterpret_cast<const float2*>(W(rope_)), g_.heads, att);
         gemm<false, E_LSRES>(ly.o, att, M, 1, 1, -1, -1, nullptr, W(ly.ls1), x, x, H);
-        hipLaunchKernelGGL(cenc_rms_kernel, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(ly.n2), g_.eps, h);
+        hipLaunchKernelGGL(codec_rms_kernel<>, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(ly.n2), g_.eps, h);
         gemm<false, E_SWIGLU>(ly.gu, h, M, 1, 1, -1, -1, nullptr, nullptr, nullptr, gg, 2 * H);
         gemm<false, E_LSRES>(ly.down, gg, M, 1, 1, -1, -1, nullptr, W(ly.ls2), x, x, H);
     }
-    hipLaunchKernelGGL(cenc_rms_kernel, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(norm_), g_.eps, h);
+    hipLaunchKernelGGL(codec_rms_kernel<>, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(norm_), g_.eps, h);
     QASR_HIP(hipEventRecord(ev_[7], work_));
     QASR_HIP(hipGetLastError());
 }

@@ -10,30 +10,17 @@
 // x8 x5 x4 x3, 3 residual units of dilation 1 3 9) -> SnakeBeta, conv k7 to one channel, clip.  Every conv is causal inside its window.
 // f32 throughout.
 #pragma once
-#include "engine.h"
-#include "safetensors.h"
-#include <string>
-#include <vector>
+#include "codec_shared.h"
 
 namespace qasr {
 
-constexpr int CODEC_RATE = 24000, CODEC_MAX_T = 35, CODEC_CHUNK = 25, CODEC_CONTEXT = 10, CODEC_STAGES = 8, CODEC_SAMPLES_PER_FRAME = 1920;
+constexpr int CODEC_RATE = 24000, CODEC_MAX_T = 35, CODEC_CHUNK = 25, CODEC_CONTEXT = 10, CODEC_STAGES = 8;
 
-struct CodecGeom {                     // SpeechTokenizerDecoderConfig's defaults
-    int latent = 1024, decoder_dim = 1536, hidden = 512, heads = 16, head_dim = 64, layers = 8;
-    int rates[4] = {8, 5, 4, 3}, ratios[2] = {2, 2};
-    int quantizers = 16, semantic_size = 2048, acoustic_size = 2048, codebook_dim = 256;
-    float eps = 1e-8f;
-    int samples_per_frame() const { return ratios[0] * ratios[1] * rates[0] * rates[1] * rates[2] * rates[3]; }
-};
-// throws std::invalid_argument with the offending field
-void codec_check_geometry(const CodecGeom& g);
 // model_dir/config.json's "decoder_config" over the defaults (api_codec.cpp); throws WeightLoadError with messages starting "<who>: "
 CodecGeom codec_read_geometry(const std::string& dir, const char* who);
 // key -> shape of every tensor the decoder reads; embed_stored[q]: codebook q (0 = rvq_first) is stored under `embed`, else under
 // embedding_sum + cluster_usage
-std::vector<std::pair<std::string, std::vector<int64_t>>> codec_tensor_shapes(const CodecGeom& g, const std::vector<bool>& embed_stored);
-std::string codec_codebook_prefix(int q);
+CodecShapes codec_tensor_shapes(const CodecGeom& g, const std::vector<bool>& embed_stored);
 // chunkedDecode's windows (:696-733): frames starts[i] .. ends[i] are decoded, the first context[i] of them dropped
 struct CodecSpan { int start, context, end; };
 std::vector<CodecSpan> codec_window_positions(long T);
@@ -56,12 +43,10 @@ class CodecQwen3TTS {
     hipStream_t stream() const { return work_; }
 
   private:
-    struct Gemm { size_t wt = 0, bias = 0; int K = 0, N = 0, Cin = 0, taps = 1; bool has_bias = false; };
-    struct Snake { size_t a = 0, b = 0; };
-    struct Layer { size_t n1, n2, ls1, ls2; Gemm qkv, o, gu, down; };
+    using Gemm = CodecGemm;
+    using Snake = CodecSnake;
     struct Up { Gemm tconv, pw1, pw2; size_t dw, dwb, lnw, lnb, gamma; };
-    struct Unit { Snake s1, s2; Gemm c1, c2; };
-    struct Block { Snake s; Gemm tconv; Unit u[3]; };
+    struct Block { Snake s; Gemm tconv; CodecUnit u[3]; };
     enum Mode { FULL, RVQ, PT };
     void check_loaded() const;
     void ensure(long M1, Mode mode);
@@ -84,7 +69,7 @@ class CodecQwen3TTS {
     // weights (offsets in floats into d_w_)
     size_t cb_first_ = 0, rope_ = 0, final_w_ = 0, final_b_ = 0, norm_ = 0;
     Gemm rvq_, pre_conv_, in_proj_, out_proj_, dec0_;
-    std::vector<Layer> layers_;
+    std::vector<CodecLayer> layers_;
     Up up_[2];
     Block blocks_[4];
     Snake final_snake_;

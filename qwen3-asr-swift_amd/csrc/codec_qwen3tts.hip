@@ -6,18 +6,19 @@
 // 1920), so one table fstart[frame row] = off serves every rate; row indices are 64-bit.
 // Launches of a pass:
 //   codec_gather_kernel    per frame: codebook 0's vector | the 15 acoustic vectors summed in codebook order -> [M][2 D]
-//   codec_gemm_kernel      the 64 x 64 tiled f32 GEMM of sep_gemm_kernel as an implicit-GEMM causal conv: K = taps x C_in, the A element of
-//                          (row t, tap j, channel c) is x[t - (taps - 1 - j) dilation][c], zero before the window's first row, SnakeBeta
+//   codec_gemm_kernel      (codec_shared.h, with the row locator WindowRows) the 64 x 64 tiled f32 GEMM of sep_gemm_kernel as an
+//                          implicit-GEMM causal conv: K = taps x C_in, the A element of (row t, tap j, channel c) is
+//                          x[t - (taps - 1 - j) dilation][c], zero before the window's first row, SnakeBeta
 //                          optionally applied as it is loaded; the epilogue is bias | bias + GELU | bias + residual | layer scale +
 //                          residual | SiLU(gate) x up over interleaved columns.  It runs the two RVQ projections (one GEMM, K = 2 D),
 //                          pre_conv, every Linear, decoder.decoder.0, the k = 7 and k = 1 convs of the residual units, and every
 //                          transposed conv: with k = 2 s, output row t s + j is x[t] W[:, :, j] + x[t - 1] W[:, :, j + s], a two-tap GEMM
 //                          with N = s C_out whose output row [s][C_out] IS rows t s .. t s + s - 1 of the upsampled tensor; the trim
 //                          falls out.  Edge tiles are guarded, not padded.
-//   codec_rms_kernel       RMSNorm, one workgroup per row
+//   codec_rms_kernel       (codec_shared.h) RMSNorm, one workgroup per row
 //   codec_attn_kernel      one workgroup per (window, head): q, k (RoPE on the way in, rotate-halves, positions from 0) and v in LDS,
 //                          causal scores, softmax, P V
-//   codec_dwln_kernel      depthwise k = 7 causal conv + LayerNorm, one workgroup per row
+//   codec_dwln_kernel      (codec_shared.h, WindowRows) depthwise k = 7 causal conv + LayerNorm, one workgroup per row
 //   codec_out_kernel       final SnakeBeta, the C -> 1 k = 7 conv as one dot of 7 C terms per sample, clip
 // Summation order: every GEMM output is one thread's fmaf chain over k = 0..K-1 (taps outer, channels inner;
 // rows before the window add exact zeros); the row reductions of the norms are a thread's sequential partial over c = tid, tid + 256, ..
@@ -31,55 +32,20 @@
 namespace qasr {
 
 // ---- geometry, keys, windows (host) -------------------------------------------------------------------------------------------------
-void codec_check_geometry(const CodecGeom& g) {
-    auto bad = [](const std::string& m) { throw std::invalid_argument("speech tokenizer decoder: " + m); };
-    if (g.head_dim != 64) bad("head_dim must be 64");
-    if (g.heads < 1 || g.heads > 64) bad("num_heads in 1..64");
-    if (g.layers < 1 || g.layers > 64) bad("num_layers in 1..64");
-    if (g.hidden < 1 || g.hidden > 4096 || g.latent < 1 || g.latent > 4096) bad("hidden_size and latent_dim in 1..4096");
-    if (g.decoder_dim < 16 || g.decoder_dim > 8192 || g.decoder_dim % 16) bad("decoder_dim a multiple of 16 in 16..8192");
-    for (int r : g.rates) if (r < 1 || r > 16) bad("four upsample_rates in 1..16");
-    for (int r : g.ratios) if (r < 1 || r > 16) bad("two upsampling_ratios in 1..16");
-    if (g.quantizers < 2 || g.quantizers > 64) bad("num_quantizers in 2..64");
-    if (g.semantic_size < 1 || g.acoustic_size < 1 || g.semantic_size > (1 << 20) || g.acoustic_size > (1 << 20)) bad("codebook sizes in 1..2^20");
-    if (g.codebook_dim < 1 || g.codebook_dim > 4096) bad("codebook_dim in 1..4096");
-    if (((long)g.semantic_size * g.codebook_dim) % 4 || ((long)g.acoustic_size * g.codebook_dim) % 4) bad("codebook size x codebook_dim a multiple of 4");
-    if (!(g.eps > 0.0f)) bad("rms_norm_eps > 0");
-    // every output buffer of the C ABI is [1920 T] (qasr_codec_samples_per_frame, SpeechTokenizerDecoder.swift:698 fixes it too)
-    if (g.samples_per_frame() != CODEC_SAMPLES_PER_FRAME)
-        bad("upsampling_ratios x upsample_rates multiply to " + std::to_string(g.samples_per_frame()) + " samples per frame, must be 1920");
-}
-
-std::string codec_codebook_prefix(int q) {
-    return q == 0 ? std::string("decoder.quantizer.rvq_first.vq.layers.0._codebook")
-                  : "decoder.quantizer.rvq_rest.vq.layers." + std::to_string(q - 1) + "._codebook";
-}
-
-std::vector<std::pair<std::string, std::vector<int64_t>>> codec_tensor_shapes(const CodecGeom& g, const std::vector<bool>& embed_stored) {
-    std::vector<std::pair<std::string, std::vector<int64_t>>> s;
+CodecShapes codec_tensor_shapes(const CodecGeom& g, const std::vector<bool>& embed_stored) {
+    CodecShapes s;
     auto add = [&](const std::string& k, std::vector<int64_t> sh) { s.emplace_back(k, std::move(sh)); };
-    const int64_t L = g.latent, H = g.hidden, Dd = g.decoder_dim, D = g.codebook_dim, A = (int64_t)g.heads * g.head_dim;
+    const int64_t L = g.latent, H = g.hidden, Dd = g.decoder_dim, D = g.codebook_dim;
     for (int q = 0; q < g.quantizers; ++q) {
         const int64_t n = q == 0 ? g.semantic_size : g.acoustic_size;
-        const std::string p = codec_codebook_prefix(q);
+        const std::string p = codec_codebook_prefix("decoder", q);
         if (embed_stored[q]) add(p + ".embed", {n, D});
         else { add(p + ".embedding_sum", {n, D}); add(p + ".cluster_usage", {n}); }
     }
     add("decoder.quantizer.rvq_first.output_proj.weight", {H, D, 1});
     add("decoder.quantizer.rvq_rest.output_proj.weight", {H, D, 1});
     add("decoder.pre_conv.conv.weight", {L, H, 3}); add("decoder.pre_conv.conv.bias", {L});
-    const std::string P = "decoder.pre_transformer.";
-    add(P + "input_proj.weight", {H, L}); add(P + "input_proj.bias", {H});
-    add(P + "output_proj.weight", {L, H}); add(P + "output_proj.bias", {L});
-    add(P + "norm.weight", {H});
-    for (int l = 0; l < g.layers; ++l) {
-        const std::string p = P + "layers." + std::to_string(l) + ".";
-        for (const char* k : {"q_proj", "k_proj", "v_proj"}) add(p + "self_attn." + k + ".weight", {A, H});
-        add(p + "self_attn.o_proj.weight", {H, A});
-        add(p + "input_layernorm.weight", {H}); add(p + "post_attention_layernorm.weight", {H});
-        add(p + "mlp.gate_proj.weight", {2 * H, H}); add(p + "mlp.up_proj.weight", {2 * H, H}); add(p + "mlp.down_proj.weight", {H, 2 * H});
-        add(p + "self_attn_layer_scale.scale", {H}); add(p + "mlp_layer_scale.scale", {H});
-    }
+    codec_pre_transformer_shapes(s, "decoder.pre_transformer.", g);
     for (int i = 0; i < 2; ++i) {
         const std::string p = "decoder.upsample." + std::to_string(i) + ".";
         add(p + "0.conv.weight", {L, L, 2 * g.ratios[i]}); add(p + "0.conv.bias", {L});
@@ -121,28 +87,6 @@ std::vector<CodecSpan> codec_window_positions(long T) {
 }
 
 // ---- kernels ------------------------------------------------------------------------------------------------------------------------
-constexpr int CG_THREADS = 256, CG_T = 64, CG_K = 16, ROW_THREADS = 256;
-enum { E_LIN = 0, E_GELU = 1, E_RES = 2, E_LSRES = 3, E_SWIGLU = 4 };
-
-// x + (1 / exp(beta)) sin^2(exp(alpha) x) with a = exp(alpha), b = 1 / exp(beta) formed at load (SpeechTokenizerDecoder.swift:105-110)
-__device__ __forceinline__ float codec_snake(float x, float a, float b) {
-    const float s = sinf(a * x);
-    return x + b * (s * s);
-}
-
-// sum over the workgroup's 256 values in a fixed tree; every thread gets it.  Ends with a barrier that also frees `red`.
-__device__ __forceinline__ float codec_block_sum(float v, float* red, int tid) {
-    red[tid] = v;
-    __syncthreads();
-    for (int s = ROW_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = red[tid] + red[tid + s];
-        __syncthreads();
-    }
-    const float r = red[0];
-    __syncthreads();
-    return r;
-}
-
 // codes [M][Q]; cb: codebook 0 [S0][D], then Q - 1 codebooks [S1][D]; out [M][2 D] = first | rest summed in codebook order (:449-462)
 __global__ __launch_bounds__(ROW_THREADS) void codec_gather_kernel(const int* __restrict__ codes, int Q, int D, long S0, long S1,
                                                                    const float* __restrict__ cb, float* __restrict__ out) {
@@ -157,132 +101,6 @@ __global__ __launch_bounds__(ROW_THREADS) void codec_gather_kernel(const int* __
         }
         out[m * 2 * D + D + d] = acc;
     }
-}
-
-// C = epilogue(sum_k A(m, k) Wt[k][n]), k = j C_in + c <-> x[m - (taps - 1 - j) dil][c].  A [M][C_in], Wt [K][N], fstart[m / rate] * rate is
-// the first row of m's window.  bias[n % bmod] (nullptr: none).  E_SWIGLU: columns 2 i, 2 i + 1 are gate i, up i; C [M][N / 2].
-template <bool SNAKE, int EPI>
-__global__ __launch_bounds__(CG_THREADS) void codec_gemm_kernel(const float* __restrict__ A, long M, int Cin, int taps, int dil, int rate,
-                                                                const int* __restrict__ fstart, const float* __restrict__ Wt, int K, int N,
-                                                                const float* __restrict__ bias, int bmod, const float* __restrict__ sa,
-                                                                const float* __restrict__ sb, const float* __restrict__ ls,
-                                                                const float* R, float* C, int ldc) {
-    __shared__ __attribute__((aligned(16))) float As[CG_K][CG_T + 4];
-    __shared__ __attribute__((aligned(16))) float Bs[CG_K][CG_T];
-    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    const long m0 = (long)blockIdx.x * CG_T;
-    const int n0 = blockIdx.y * CG_T;
-    long wstart[4];                                    // first row of the window of each A row this thread loads
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const long m = m0 + ((tid + r * CG_THREADS) >> 4);
-        wstart[r] = m < M ? (long)fstart[m / rate] * rate : 0;
-    }
-    float acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[i][q] = 0.0f;
-    for (int k0 = 0; k0 < K; k0 += CG_K) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int idx = tid + r * CG_THREADS, row = idx >> 4, kk = idx & 15, k = k0 + kk;
-            const long m = m0 + row;
-            float v = 0.0f;                            // rows past M, inputs past K and rows before the window add exact zeros
-            if (m < M && k < K) {
-                const int j = k / Cin, c = k - j * Cin;
-                const long src = m - (long)(taps - 1 - j) * dil;
-                if (src >= wstart[r]) {
-                    v = A[src * Cin + c];
-                    if (SNAKE) v = codec_snake(v, sa[c], sb[c]);
-                }
-            }
-            As[kk][row] = v;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int idx = tid + r * CG_THREADS, kk = idx >> 6, col = idx & 63, k = k0 + kk, n = n0 + col;
-            Bs[kk][col] = (k < K && n < N) ? Wt[(size_t)k * N + n] : 0.0f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < CG_K; ++kk) {
-            const float4 a = lds_read_f4(&As[kk][ty * 4]);
-            const float4 bq = lds_read_f4(&Bs[kk][tx * 4]);
-            const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {bq.x, bq.y, bq.z, bq.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[i][q] = fmaf(av[i], bv[q], acc[i][q]);
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const long m = m0 + ty * 4 + i;
-        if (m >= M) continue;
-        if (EPI == E_SWIGLU) {                         // silu(gate) * up (:340)
-#pragma unroll
-            for (int q = 0; q < 4; q += 2) {
-                const int n = n0 + tx * 4 + q;
-                if (n + 1 >= N) continue;
-                const float g = acc[i][q];
-                C[m * ldc + (n >> 1)] = (g / (1.0f + expf(-g))) * acc[i][q + 1];
-            }
-            continue;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int n = n0 + tx * 4 + q;
-            if (n >= N) continue;
-            float v = acc[i][q];
-            if (bias) v = v + bias[n % bmod];
-            if (EPI == E_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
-            if (EPI == E_RES) v = v + R[m * ldc + n];
-            if (EPI == E_LSRES) v = v * ls[n] + R[m * ldc + n];
-            C[m * ldc + n] = v;
-        }
-    }
-}
-
-// y = x / sqrt(mean(x^2) + eps) * w, one workgroup per row
-__global__ __launch_bounds__(ROW_THREADS) void codec_rms_kernel(const float* __restrict__ x, int C, const float* __restrict__ w, float eps,
-                                                                float* __restrict__ y) {
-    __shared__ float red[ROW_THREADS];
-    const long m = blockIdx.x;
-    const int tid = threadIdx.x;
-    float p = 0.0f;
-    for (int c = tid; c < C; c += ROW_THREADS) { const float v = x[m * C + c]; p = p + v * v; }
-    const float inv = 1.0f / sqrtf(codec_block_sum(p, red, tid) / (float)C + eps);
-    for (int c = tid; c < C; c += ROW_THREADS) y[m * C + c] = (x[m * C + c] * inv) * w[c];
-}
-
-// depthwise causal conv k = 7 (w [7][C], + bias) then LayerNorm eps 1e-5, one workgroup per row; C <= 4096 (:156-160)
-__global__ __launch_bounds__(ROW_THREADS) void codec_dwln_kernel(const float* __restrict__ x, int C, int rate, const int* __restrict__ fstart,
-                                                                 const float* __restrict__ w, const float* __restrict__ b,
-                                                                 const float* __restrict__ lnw, const float* __restrict__ lnb,
-                                                                 float* __restrict__ y) {
-    __shared__ float red[ROW_THREADS];
-    __shared__ float val[4096];
-    const long m = blockIdx.x, start = (long)fstart[m / rate] * rate;
-    const int tid = threadIdx.x;
-    float p = 0.0f;
-    for (int c = tid; c < C; c += ROW_THREADS) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 7; ++j) {
-            const long src = m - (6 - j);
-            if (src >= start) acc = acc + x[src * C + c] * w[j * C + c];
-        }
-        acc = acc + b[c];
-        val[c] = acc;
-        p = p + acc;
-    }
-    const float mu = codec_block_sum(p, red, tid) / (float)C;
-    float q = 0.0f;
-    for (int c = tid; c < C; c += ROW_THREADS) { const float d = val[c] - mu; q = q + d * d; }
-    const float inv = 1.0f / sqrtf(codec_block_sum(q, red, tid) / (float)C + 1e-5f);
-    for (int c = tid; c < C; c += ROW_THREADS) y[m * C + c] = ((val[c] - mu) * inv) * lnw[c] + lnb[c];
 }
 
 // qkv [M][3 A] (A = heads x 64), win[w] = (frames, first row), rope [35][32] (cos, sin); out [M][A].  grid (windows, heads).
@@ -348,37 +166,16 @@ __global__ __launch_bounds__(ROW_THREADS) void codec_out_kernel(const float* __r
 }
 
 // ---- weights ------------------------------------------------------------------------------------------------------------------------
-namespace {
-struct Builder {
-    std::vector<float> h;
-    const CheckedWeights& w;
-    explicit Builder(const CheckedWeights& cw) : w(cw) {}
-    const std::vector<float>& t(const std::string& k) const { return w.t.at(k); }
-    size_t take(size_t n) { const size_t at = h.size(); h.resize(at + ((n + 3) & ~(size_t)3), 0.0f); return at; }
-    size_t vec(const std::string& k) { const auto& v = t(k); const size_t at = take(v.size()); std::copy(v.begin(), v.end(), h.begin() + at); return at; }
-};
-}  // namespace
-
 CodecQwen3TTS::CodecQwen3TTS(int device, const CheckedWeights& cw, const CodecGeom& g, const std::vector<bool>& embed_stored,
                              int max_windows, hipStream_t work)
     : device_(device), g_(g), max_windows_(max_windows), spf_(g.samples_per_frame()) {
-    codec_check_geometry(g);
+    codec_check_geometry(g, "speech tokenizer decoder");
     if (max_windows < 1 || max_windows > 512) throw std::invalid_argument("speech tokenizer decoder: max_windows in 1..512");
     param_bytes_ = cw.disk_bytes;
     Builder b(cw);
-    const int L = g.latent, H = g.hidden, Dd = g.decoder_dim, D = g.codebook_dim, A = g.heads * g.head_dim, I = 2 * H;
-    // Wt[j C_in + c][n] = W[n][c][j] of a conv [out][in][k] (k = 1: a Linear [out][in])
-    auto conv = [&](const std::string& key, int Cout, int Cin, int k, bool bias) {
-        Gemm gm; gm.K = k * Cin; gm.N = Cout; gm.Cin = Cin; gm.taps = k;
-        const auto& W = b.t(key + ".weight");
-        gm.wt = b.take((size_t)gm.K * gm.N);
-        for (int n = 0; n < Cout; ++n)
-            for (int c = 0; c < Cin; ++c)
-                for (int j = 0; j < k; ++j) b.h[gm.wt + ((size_t)j * Cin + c) * Cout + n] = W[((size_t)n * Cin + c) * k + j];
-        gm.has_bias = bias;
-        if (bias) gm.bias = b.vec(key + ".bias");
-        return gm;
-    };
+    const int L = g.latent, H = g.hidden, Dd = g.decoder_dim, D = g.codebook_dim, A = g.heads * g.head_dim;
+    auto conv = [&](const std::string& key, int Cout, int Cin, int k, bool bias) { return codec_pack_conv(b, key, Cout, Cin, k, bias); };
+    auto snake = [&](const std::string& key) { return codec_pack_snake(b, key); };
     // transposed conv [in][out][2 s] as two taps: tap 0 (x[t - 1]) holds W[:, :, ph + s], tap 1 (x[t]) holds W[:, :, ph]; n = ph C_out + co
     auto tconv = [&](const std::string& key, int Cin, int Cout, int s) {
         Gemm gm; gm.K = 2 * Cin; gm.N = s * Cout; gm.Cin = Cin; gm.taps = 2;
@@ -395,27 +192,14 @@ CodecQwen3TTS::CodecQwen3TTS(int device, const CheckedWeights& cw, const CodecGe
         gm.bias = b.vec(key + ".bias");
         return gm;
     };
-    auto snake = [&](const std::string& key) {          // exp(alpha) | 1 / exp(beta), in f32 as the reference forms them
-        Snake s;
-        const auto &al = b.t(key + ".alpha"), &be = b.t(key + ".beta");
-        s.a = b.take(al.size()); s.b = b.take(be.size());
-        for (size_t i = 0; i < al.size(); ++i) { b.h[s.a + i] = expf(al[i]); b.h[s.b + i] = 1.0f / expf(be[i]); }
-        return s;
-    };
     // codebooks (TTSWeightLoading.swift:280-301)
     for (int q = 0; q < g.quantizers; ++q) {
         const int n = q == 0 ? g.semantic_size : g.acoustic_size;
-        const std::string p = codec_codebook_prefix(q);
         // codec_gather_kernel indexes all codebooks from cb_first_ as one array: take() pads to 4 floats, and codec_check_geometry
         // requires size x dim to be a multiple of 4, so consecutive takes are contiguous
         const size_t at = b.take((size_t)n * D);
         if (q == 0) cb_first_ = at;
-        if (embed_stored[q]) std::copy(b.t(p + ".embed").begin(), b.t(p + ".embed").end(), b.h.begin() + at);
-        else {
-            const auto &sum = b.t(p + ".embedding_sum"), &use = b.t(p + ".cluster_usage");
-            for (int i = 0; i < n; ++i)
-                for (int d = 0; d < D; ++d) b.h[at + (size_t)i * D + d] = sum[(size_t)i * D + d] / std::max(use[i], 1e-7f);
-        }
+        codec_pack_codebook(b, at, codec_codebook_prefix("decoder", q), embed_stored[q], n, D);
     }
     {   // both output projections as one GEMM over [first | rest]
         rvq_.K = 2 * D; rvq_.N = H; rvq_.Cin = 2 * D; rvq_.taps = 1;
@@ -432,40 +216,13 @@ CodecQwen3TTS::CodecQwen3TTS(int device, const CheckedWeights& cw, const CodecGe
     in_proj_ = conv(P + "input_proj", H, L, 1, true);
     out_proj_ = conv(P + "output_proj", L, H, 1, true);
     norm_ = b.vec(P + "norm.weight");
-    for (int l = 0; l < g.layers; ++l) {
-        const std::string p = P + "layers." + std::to_string(l) + ".";
-        Layer ly;
-        ly.n1 = b.vec(p + "input_layernorm.weight"); ly.n2 = b.vec(p + "post_attention_layernorm.weight");
-        ly.ls1 = b.vec(p + "self_attn_layer_scale.scale"); ly.ls2 = b.vec(p + "mlp_layer_scale.scale");
-        ly.qkv.K = H; ly.qkv.N = 3 * A; ly.qkv.Cin = H;
-        ly.qkv.wt = b.take((size_t)H * 3 * A);
-        int part = 0;
-        for (const char* k : {"q_proj", "k_proj", "v_proj"}) {
-            const auto& W = b.t(p + "self_attn." + k + ".weight");
-            for (int n = 0; n < A; ++n)
-                for (int c = 0; c < H; ++c) b.h[ly.qkv.wt + (size_t)c * 3 * A + part * A + n] = W[(size_t)n * H + c];
-            ++part;
-        }
-        ly.o = conv(p + "self_attn.o_proj", H, A, 1, false);
-        ly.gu.K = H; ly.gu.N = 2 * I; ly.gu.Cin = H;
-        ly.gu.wt = b.take((size_t)H * 2 * I);
-        const auto &Wg = b.t(p + "mlp.gate_proj.weight"), &Wu = b.t(p + "mlp.up_proj.weight");
-        for (int n = 0; n < I; ++n)
-            for (int c = 0; c < H; ++c) {
-                b.h[ly.gu.wt + (size_t)c * 2 * I + 2 * n] = Wg[(size_t)n * H + c];
-                b.h[ly.gu.wt + (size_t)c * 2 * I + 2 * n + 1] = Wu[(size_t)n * H + c];
-            }
-        ly.down = conv(p + "mlp.down_proj", H, I, 1, false);
-        layers_.push_back(ly);
-    }
+    for (int l = 0; l < g.layers; ++l)
+        layers_.push_back(codec_pack_layer(b, P + "layers." + std::to_string(l) + ".", H, A));
     for (int i = 0; i < 2; ++i) {
         const std::string p = "decoder.upsample." + std::to_string(i) + ".";
         Up& u = up_[i];
         u.tconv = tconv(p + "0.conv", L, L, g.ratios[i]);
-        const auto& dw = b.t(p + "1.dwconv.conv.weight");                // [L][1][7] -> [7][L]
-        u.dw = b.take((size_t)7 * L);
-        for (int c = 0; c < L; ++c)
-            for (int j = 0; j < 7; ++j) b.h[u.dw + (size_t)j * L + c] = dw[(size_t)c * 7 + j];
+        u.dw = codec_pack_taps7(b, p + "1.dwconv.conv.weight", L);
         u.dwb = b.vec(p + "1.dwconv.conv.bias");
         u.lnw = b.vec(p + "1.norm.weight"); u.lnb = b.vec(p + "1.norm.bias");
         u.pw1 = conv(p + "1.pwconv1", 4 * L, L, 1, true);
@@ -492,20 +249,9 @@ CodecQwen3TTS::CodecQwen3TTS(int device, const CheckedWeights& cw, const CodecGe
     }
     big_per_frame_ = big;
     final_snake_ = snake("decoder.decoder.5");
-    {   // [1][C][7] -> [7][C]
-        const auto& W = b.t("decoder.decoder.6.conv.weight");
-        final_w_ = b.take((size_t)7 * c);
-        for (int ch = 0; ch < c; ++ch)
-            for (int j = 0; j < 7; ++j) b.h[final_w_ + (size_t)j * c + ch] = W[(size_t)ch * 7 + j];
-        final_b_ = b.vec("decoder.decoder.6.conv.bias");
-    }
-    rope_ = b.take((size_t)CODEC_MAX_T * 32 * 2);      // MLXNN.RoPE base 10000 over all 64 dimensions, positions 0..34
-    for (int t = 0; t < CODEC_MAX_T; ++t)
-        for (int d = 0; d < 32; ++d) {
-            const float inv = (float)pow(10000.0, -(double)d / 32.0), ang = (float)t * inv;
-            b.h[rope_ + ((size_t)t * 32 + d) * 2] = (float)cos((double)ang);
-            b.h[rope_ + ((size_t)t * 32 + d) * 2 + 1] = (float)sin((double)ang);
-        }
+    final_w_ = codec_pack_taps7(b, "decoder.decoder.6.conv.weight", c);
+    final_b_ = b.vec("decoder.decoder.6.conv.bias");
+    rope_ = codec_pack_rope(b, CODEC_MAX_T);           // positions 0..34
     QASR_HIP(hipSetDevice(device_));
     QASR_HIP(hipStreamCreateWithFlags(&own_, hipStreamNonBlocking));
     work_ = work ? work : own_;
@@ -589,8 +335,8 @@ template <bool SNAKE, int EPI>
 void CodecQwen3TTS::gemm(const Gemm& gm, const float* A, long M, int dil, int rate, const Snake* sn, const float* ls, const float* R, float* C,
                          int ldc, int bmod) {
     const dim3 grid((unsigned)cdiv(M, CG_T), (unsigned)cdiv(gm.N, CG_T));
-    hipLaunchKernelGGL((codec_gemm_kernel<SNAKE, EPI>), grid, dim3(CG_THREADS), 0, work_, A, M, gm.Cin, gm.taps, dil, rate,
-                       d_fstart_.as<int>(), W(gm.wt), gm.K, gm.N, gm.has_bias ? W(gm.bias) : (const float*)nullptr, bmod,
+    hipLaunchKernelGGL((codec_gemm_kernel<WindowRows, SNAKE, EPI>), grid, dim3(CG_THREADS), 0, work_, A, M, gm.Cin, gm.taps, dil,
+                       WindowRows{d_fstart_.as<int>(), rate}, W(gm.wt), gm.K, gm.N, gm.has_bias ? W(gm.bias) : (const float*)nullptr, bmod,
                        sn ? W(sn->a) : (const float*)nullptr, sn ? W(sn->b) : (const float*)nullptr, ls, R, C, ldc);
 }
 
@@ -607,17 +353,17 @@ void CodecQwen3TTS::dev_pre_transformer() {
     const long M = M1_;
     float *x = d_x_.as<float>(), *h = d_h_.as<float>(), *qkv = d_qkv_.as<float>(), *att = d_att_.as<float>(), *gg = d_g_.as<float>();
     gemm<false, E_LIN>(in_proj_, d_lat_[0].as<float>(), M, 1, 1, nullptr, nullptr, nullptr, x, H, H);
-    for (const Layer& ly : layers_) {
-        hipLaunchKernelGGL(codec_rms_kernel, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(ly.n1), g_.eps, h);
+    for (const CodecLayer& ly : layers_) {
+        hipLaunchKernelGGL(codec_rms_kernel<>, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(ly.n1), g_.eps, h);
         gemm<false, E_LIN>(ly.qkv, h, M, 1, 1, nullptr, nullptr, nullptr, qkv, 3 * A, 3 * A);
         hipLaunchKernelGGL(codec_attn_kernel, dim3((unsigned)n_win_, (unsigned)g_.heads), dim3(ROW_THREADS), 0, work_, qkv,
                            d_win_.as<int2>(), reinterpret_cast<const float2*>(W(rope_)), g_.heads, att);
         gemm<false, E_LSRES>(ly.o, att, M, 1, 1, nullptr, W(ly.ls1), x, x, H, H);
-        hipLaunchKernelGGL(codec_rms_kernel, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(ly.n2), g_.eps, h);
+        hipLaunchKernelGGL(codec_rms_kernel<>, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(ly.n2), g_.eps, h);
         gemm<false, E_SWIGLU>(ly.gu, h, M, 1, 1, nullptr, nullptr, nullptr, gg, 2 * H, 2 * H);
         gemm<false, E_LSRES>(ly.down, gg, M, 1, 1, nullptr, W(ly.ls2), x, x, H, H);
     }
-    hipLaunchKernelGGL(codec_rms_kernel, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(norm_), g_.eps, h);
+    hipLaunchKernelGGL(codec_rms_kernel<>, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(norm_), g_.eps, h);
     gemm<false, E_LIN>(out_proj_, h, M, 1, 1, nullptr, nullptr, nullptr, d_lat_[1].as<float>(), L, L);
     QASR_HIP(hipGetLastError());
 }
@@ -634,8 +380,8 @@ void CodecQwen3TTS::dev_vocoder(bool clip) {
         gemm<false, E_LIN>(u.tconv, x, M1_ * rate, 1, rate, nullptr, nullptr, nullptr, y, u.tconv.N, L);
         rate *= g_.ratios[i];
         const long M = M1_ * rate;
-        hipLaunchKernelGGL(codec_dwln_kernel, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, y, L, rate, d_fstart_.as<int>(), W(u.dw),
-                           W(u.dwb), W(u.lnw), W(u.lnb), h);
+        hipLaunchKernelGGL(codec_dwln_kernel<WindowRows>, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, y, L,
+                           WindowRows{d_fstart_.as<int>(), rate}, W(u.dw), W(u.dwb), W(u.lnw), W(u.lnb), h);
         gemm<false, E_GELU>(u.pw1, h, M, 1, rate, nullptr, nullptr, nullptr, mid, 4 * L, 4 * L);
         gemm<false, E_LSRES>(u.pw2, mid, M, 1, rate, nullptr, W(u.gamma), y, y, L, L);
         x = y;

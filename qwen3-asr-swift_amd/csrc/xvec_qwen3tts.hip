@@ -20,6 +20,7 @@
 // Summation order: every GEMM / conv output is one thread's fmaf chain over k; every per-clip reduction is first summed over the rows of
 // a tile in row order, then over the clip's tiles in tile order.  Nothing depends on a clip's place in the pass.
 #include "xvec_qwen3tts.h"
+#include "codec_shared.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -73,16 +74,6 @@ constexpr int RS_HALO = 28, RS_ROWS = XV_RES_TILE + 2 * RS_HALO, RS_RP = RS_ROWS
 enum { A_LIN = 0, A_RELU = 1, A_TANH_CTX = 2 };
 enum { S_NONE = 0, S_SUM = 1, S_MAX = 2 };
 
-// the clip that owns row m: start[0] = 0 < start[1] < .. < start[n] = rows, every clip holds at least one row
-__device__ __forceinline__ int xv_clip_of(const int* __restrict__ start, int n, long m) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((long)start[mid] <= m) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // column c of the partials of tiles tb .. te - 1, in tile order
 __device__ __forceinline__ float xv_tiles_sum(const float* __restrict__ part, int ld, int tb, int te, int c) {
     float s = 0.0f;
@@ -109,7 +100,7 @@ __global__ __launch_bounds__(256) void xv_mel_kernel(const float* __restrict__ p
     __shared__ float mag[XV_NBINS + 3];
     const int tid = threadIdx.x;
     const long m = blockIdx.x;
-    const int clip = xv_clip_of(start, nclips, m);
+    const int clip = clip_of(start, nclips, m);
     const long frame = m - start[clip], n = nsamp[clip];
     const float* x = pcm + off[clip];
 #pragma unroll
@@ -455,23 +446,12 @@ __global__ __launch_bounds__(XG_THREADS) void xv_fc_kernel(const int* __restrict
 }
 
 // ---- weights ------------------------------------------------------------------------------------------------------------------------
-namespace {
-struct Builder {
-    std::vector<float> h;
-    const CheckedWeights& w;
-    explicit Builder(const CheckedWeights& cw) : w(cw) {}
-    const std::vector<float>& t(const std::string& k) const { return w.t.at("speaker_encoder." + k); }
-    size_t take(size_t n) { const size_t at = h.size(); h.resize(at + ((n + 3) & ~(size_t)3), 0.0f); return at; }
-    size_t vec(const std::string& k) { const auto& v = t(k); const size_t at = take(v.size()); std::copy(v.begin(), v.end(), h.begin() + at); return at; }
-};
-}  // namespace
-
 XvecQwen3TTS::XvecQwen3TTS(int device, const CheckedWeights& cw, int E, long max_samples, hipStream_t work)
     : device_(device), E_(E), max_samples_(max_samples) {
     if (max_samples < 1 || max_samples > XV_MAX_SAMPLES) throw std::invalid_argument("speaker encoder: max_samples in 1..2^28");
     if (E < 1 || E > 65536) throw std::invalid_argument("speaker encoder: fc.weight has " + std::to_string(E) + " rows, 1..65536 supported");
     param_bytes_ = cw.disk_bytes;
-    Builder b(cw);
+    Builder b(cw, "speaker_encoder.");
     // Wt[j C_in + c][n] = W[n][j][c] of a conv stored [out][k][in] (:436-437)
     auto conv = [&](const std::string& key, int Cout, int k, int Cin, int c0, int c1) {
         Gemm gm; gm.K = k * (c1 - c0); gm.N = Cout; gm.Cin = c1 - c0; gm.taps = k;
