@@ -267,6 +267,35 @@ typedef struct qasr_gemm_case {
 int qasr_gemm_case_probe(qasr_engine* e, int which, int form, const qasr_gemm_case* g, const uint16_t* A, const uint16_t* W,
                          const void* bias, const int32_t* aux_i, const int64_t* aux_l, const float* aux_f, void* out);
 
+/* Diagnostic: the text decoder's attention and the kernels that write its K / V cache, by themselves, on host data and a scratch cache of ONE
+ * layer whose geometry is the struct's (free of the engine's preset; needs no weights).  Nothing is restated: the product's launch entries
+ * run (csrc/dec_kernels.h), with rope tables from the product's table builder at rope_theta.  All tensors are bf16 bit patterns.
+ *   QASR_ATTN_PROMPT  qkv [n_pos][(heads + 2 kv_heads) * hd] (q | k | v), clip c = packed rows [cu[c], cu[c + 1]) in slot slot_of_clip[c];
+ *                     pos[p] / slot[p] = position and slot of packed row p.  qk_norm_rope_launch, then prefill_attention_launch.
+ *                     route 1: qkv = x[n_pos][hidden] . W[(heads + 2 kv_heads) * hd][hidden]^T first (gemm_nt, EpiStoreBf16);
+ *                     route 2: that product as the head-tile GEMM with EpiQkHeads, then qk_norm_rope_launch(v_only) (hd 128 and
+ *                     (heads + kv_heads) % 8 == 0; only the v third of qkv is meaningful then).  qkv comes back in every route.
+ *                     -> qr [n_pos][heads * hd], out [n_pos][heads * hd]
+ *   QASR_ATTN_DECODE  qkv [n_pos][...], one new token per row; row b lives in slot b at position pos[b] (its context length); cu,
+ *                     slot_of_clip, slot, qr unused (may be NULL).  refresh of the rope rows, then decode_attention_launch.
+ *                     -> out [n_pos][heads * hd]
+ * kcache [n_slots][kv_heads][max_ctx][hd] and vfrag (same size, fragment-major per (slot, kv head): csrc/dec_attention.hip vfrag_index) are
+ * uploaded before and downloaded after the launches, vt [n_slots][kv_heads][hd][max_ctx] (the prompt pass's V^T scratch, PROMPT only) is
+ * uploaded.  Knobs: qasr_set_tuning.  Refused with QASR_ERR_INVALID before anything is launched: hd other than 32 / 128, max_ctx % 32 != 0
+ * (PROMPT: % 64), DECODE with heads != 2 * kv_heads or n_pos > n_slots or a pos outside [0, max_ctx - 1], PROMPT with a head count the
+ * writers do not take, a cu that does not start at 0 / increase / end at n_pos, a clip longer than max_ctx, a slot outside n_slots or used
+ * by two clips, pos / slot that contradict cu, route 2 where it does not apply.  tests/test_gpu_attn_cases.py. */
+enum { QASR_ATTN_PROMPT = 0, QASR_ATTN_DECODE = 1 };
+typedef struct qasr_attn_case {
+    int32_t n_slots, heads, kv_heads, hd, max_ctx;
+    int32_t n_pos, n_clips;           /* packed rows (DECODE: batch rows); PROMPT: clips */
+    int32_t route, hidden;            /* PROMPT: 0 = qkv given | 1 | 2 (see above), width of x */
+    float eps, rope_theta;
+} qasr_attn_case;
+int qasr_attn_case_probe(qasr_engine* e, int op, const qasr_attn_case* g, uint16_t* qkv, const uint16_t* x, const uint16_t* W,
+                         const int32_t* cu, const int32_t* slot_of_clip, const int32_t* pos, const int32_t* slot, const uint16_t* qn_w,
+                         const uint16_t* kn_w, uint16_t* kcache, uint16_t* vfrag, const uint16_t* vt, uint16_t* qr, uint16_t* out);
+
 /* ---- utterance-batch data parallelism inside one process ----------------------------------------------------------------------
  * Replaces the sequential file loop of `speech transcribe-batch` (Sources/AudioCLILib/TranscribeBatchCommand.swift:82-93) for a caller
  * that owns several GPUs: one engine (= one HIP device + one stream, weights replicated) and one host thread per listed device; clips

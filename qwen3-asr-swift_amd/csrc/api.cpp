@@ -72,6 +72,52 @@ static const char* gemm_case_refusal(int which, int form, const qasr_gemm_case& 
     return nullptr;
 }
 
+// qasr_attn_case_probe: why the arguments are refused, or null.  Everything a launch would index with is checked here, on the host.
+static const char* attn_case_refusal(int op, const qasr_attn_case& g, const uint16_t* x, const uint16_t* W, const int32_t* cu,
+                                     const int32_t* slot_of_clip, const int32_t* pos, const int32_t* slot, const uint16_t* vt,
+                                     const uint16_t* qr) {
+    if (op != QASR_ATTN_PROMPT && op != QASR_ATTN_DECODE) return "attn case: unknown operation";
+    if (g.hd != 32 && g.hd != 128) return "attn case: head_dim must be 32 or 128";
+    if (g.n_slots <= 0 || g.heads <= 0 || g.kv_heads <= 0 || g.n_pos <= 0) return "attn case: n_slots, heads, kv_heads, n_pos must be positive";
+    if (g.max_ctx <= 0 || g.max_ctx % 32) return "attn case: max_ctx must be a positive multiple of 32";
+    if (g.heads > 64 || g.kv_heads > 64 || g.n_pos > 65536 || (double)g.n_slots * g.kv_heads * g.max_ctx * g.hd > 64.0 * 1024 * 1024)
+        return "attn case: geometry above the probe's limits (64 heads, 65536 rows, 64 Mi cache elements)";
+    if (!(g.eps > 0.0f) || !(g.eps < 1.0f) || !(g.rope_theta >= 1.0f) || !(g.rope_theta <= 1e9f)) return "attn case: eps in (0, 1) and rope_theta in [1, 1e9]";
+    if (!pos) return "attn case: positions are missing";
+    if (op == QASR_ATTN_DECODE) {
+        if (g.heads != 2 * g.kv_heads) return "attn case: decode attention is built for 2 query heads per kv head";
+        if (g.n_pos > g.n_slots) return "attn case: more batch rows than slots";
+        if (g.route != 0) return "attn case: decode has no route";
+        for (int b = 0; b < g.n_pos; ++b)
+            if (pos[b] < 0 || pos[b] >= g.max_ctx) return "attn case: a context length is outside [0, max_ctx - 1]";
+        return nullptr;
+    }
+    if (!cu || !slot_of_clip || !slot || !vt || !qr) return "attn case: prompt needs cu, slot_of_clip, slot, vt and qr";
+    if (g.max_ctx % 64) return "attn case: the prompt pass moves 64-key tiles, max_ctx must be a multiple of 64";
+    if (g.heads % g.kv_heads) return "attn case: heads must be a multiple of kv_heads";
+    const int nh = g.heads + 2 * g.kv_heads;
+    if (g.hd == 128 ? nh % 2 != 0 : nh % 8 != 0) return "attn case: head count the q/k norm + rope kernels do not take";
+    if (g.route < 0 || g.route > 2) return "attn case: route must be 0, 1 or 2";
+    if (g.route) {
+        if (!x || !W || g.hidden <= 0 || g.hidden % 8 || g.hidden > 8192) return "attn case: routes 1 and 2 need x, W and hidden a multiple of 8 up to 8192";
+        if (g.route == 2 && (g.hd != 128 || (g.heads + g.kv_heads) % 8)) return "attn case: the head-tile route needs head_dim 128 and (heads + kv_heads) % 8 == 0";
+    }
+    if (g.n_clips <= 0 || g.n_clips > g.n_slots) return "attn case: n_clips must be in [1, n_slots]";
+    if (cu[0] != 0) return "attn case: cu must start at 0";
+    for (int c = 0; c < g.n_clips; ++c) {
+        if (cu[c + 1] <= cu[c]) return "attn case: cu must increase";
+        if (cu[c + 1] > g.n_pos) return "attn case: cu runs past n_pos";
+        if (cu[c + 1] - cu[c] > g.max_ctx) return "attn case: a clip is longer than max_ctx";
+        if (slot_of_clip[c] < 0 || slot_of_clip[c] >= g.n_slots) return "attn case: a clip's slot is outside n_slots";
+        for (int d = 0; d < c; ++d)
+            if (slot_of_clip[d] == slot_of_clip[c]) return "attn case: two clips share a slot";
+        for (int p = cu[c]; p < cu[c + 1]; ++p)
+            if (slot[p] != slot_of_clip[c] || pos[p] != p - cu[c]) return "attn case: pos / slot contradict cu";
+    }
+    if (cu[g.n_clips] != g.n_pos) return "attn case: cu must end at n_pos";
+    return nullptr;
+}
+
 extern "C" {
 
 int qasr_default_config(const char* preset, qasr_config* c) {
@@ -233,6 +279,14 @@ int qasr_gemm_case_probe(qasr_engine* e, int which, int form, const qasr_gemm_ca
     if (!e || !g || !A || !W || !out) return QASR_ERR_INVALID;
     if (const char* why = gemm_case_refusal(which, form, *g, bias, aux_i, aux_l, aux_f)) return fail(e, QASR_ERR_INVALID, why);
     return on_device(e, [&] { e->impl->gemm_case_probe(which, form, *g, A, W, bias, aux_i, aux_l, aux_f, out); });
+}
+
+int qasr_attn_case_probe(qasr_engine* e, int op, const qasr_attn_case* g, uint16_t* qkv, const uint16_t* x, const uint16_t* W,
+                         const int32_t* cu, const int32_t* slot_of_clip, const int32_t* pos, const int32_t* slot, const uint16_t* qn_w,
+                         const uint16_t* kn_w, uint16_t* kcache, uint16_t* vfrag, const uint16_t* vt, uint16_t* qr, uint16_t* out) {
+    if (!e || !g || !qkv || !qn_w || !kn_w || !kcache || !vfrag || !out) return QASR_ERR_INVALID;
+    if (const char* why = attn_case_refusal(op, *g, x, W, cu, slot_of_clip, pos, slot, vt, qr)) return fail(e, QASR_ERR_INVALID, why);
+    return on_device(e, [&] { e->impl->attn_case_probe(op, *g, qkv, x, W, cu, slot_of_clip, pos, slot, qn_w, kn_w, kcache, vfrag, vt, qr, out); });
 }
 
 int qasr_transcribe_batch(qasr_engine* e, const float* const* pcm, const size_t* n, size_t B, int sample_rate,

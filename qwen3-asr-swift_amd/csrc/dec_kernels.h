@@ -7,6 +7,7 @@
 #include "common.h"
 #include "gemm.h"
 #include "dec_rope.h"
+#include <vector>
 
 namespace qasr {
 
@@ -136,6 +137,11 @@ struct RopeRows {
 void greedy_finalize_launch(const float* part_val, const int* part_idx, int n_parts, GreedyState st, int B,
                             int advance_ctx, const bf16_t* embed, bf16_t* x, int H, RopeRows rr, hipStream_t s,
                             const QuantRaw* qembed = nullptr);
+
+// teacher-forced path and qasr_attn_case_probe (no greedy_finalize): rr.cos_rows / sin_rows[b] = the table row of position ctx_len[b]
+void refresh_rope_rows_launch(const int* ctx_len, RopeRows rr, int B, hipStream_t s);
+// the position-indexed tables on the host, [n_pos][half] f32 each (decoder.hip)
+void rope_tables_host(float theta, int half, int n_pos, std::vector<float>& c, std::vector<float>& sn);
 
 // Epilogue of the prompt pass's q|k|v projection as a head-tile GEMM (gemm.h MODE 2, head_dim 128): per packed position and head, q/k RMSNorm
 // over the head, RoPE at pos[m], q -> qr[m][head][128], k -> cache.k[slot[m]][kvh][pos[m]] -- the arithmetic of qk_norm_rope_wide_kernel

@@ -105,9 +105,26 @@ __global__ __launch_bounds__(256) void qk_norm_rope_kernel(const bf16_t* __restr
     if (h >= heads + kv_heads) return;                  // V needs no arithmetic: v_transpose_kernel reads it from qkv
     const float x1a = bf16_to_f32((bf16_t)(a & 0xffff)), x1b = bf16_to_f32((bf16_t)(a >> 16));
     const float x2a = bf16_to_f32((bf16_t)(bb & 0xffff)), x2b = bf16_to_f32((bf16_t)(bb >> 16));
-    float ss = (x1a * x1a + x1b * x1b) + (x2a * x2a + x2b * x2b);
+    float ss;
+    if constexpr (HD == 128) {
+        // the sum of squares in the wide form's order, so that inv -- and with it every bit written -- is that of qk_norm_rope_wide_kernel and
+        // EpiQkHeads: the 8 consecutive rotation pairs of a wide lane (4 lanes here) left to right, then the butterfly over those groups.
+        // (A plain butterfly over the 32 lanes gave an inv one f32 ulp away now and then, and with it a q or k element one bf16 ulp away.)
+        const float ta = x1a * x1a + x2a * x2a, tb = x1b * x1b + x2b * x2b;
+        const int base = lane & ~3;
+        ss = 0.0f;
 #pragma unroll
-    for (int ofs = 1; ofs < LPH; ofs <<= 1) ss += __shfl_xor(ss, ofs, 64);
+        for (int q = 0; q < 4; ++q) {
+            ss += __shfl(ta, base + q, 64);
+            ss += __shfl(tb, base + q, 64);
+        }
+#pragma unroll
+        for (int ofs = 4; ofs < LPH; ofs <<= 1) ss += __shfl_xor(ss, ofs, 64);
+    } else {
+        ss = (x1a * x1a + x1b * x1b) + (x2a * x2a + x2b * x2b);
+#pragma unroll
+        for (int ofs = 1; ofs < LPH; ofs <<= 1) ss += __shfl_xor(ss, ofs, 64);
+    }
     const float inv = rsqrtf(ss / (float)HD + eps);
     const bf16_t* nw = h < heads ? qn_w : kn_w;
     const unsigned w1 = *reinterpret_cast<const unsigned*>(nw + 2 * j), w2 = *reinterpret_cast<const unsigned*>(nw + HALF + 2 * j);

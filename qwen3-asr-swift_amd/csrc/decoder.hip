@@ -63,6 +63,27 @@ __global__ void refresh_rope_rows_kernel(const int* __restrict__ ctx_len, RopeRo
     }
 }
 
+void refresh_rope_rows_launch(const int* ctx_len, RopeRows rr, int B, hipStream_t s) {
+    if (B <= 0) return;
+    if (rr.half > 64) throw std::invalid_argument("rope rows: head_dim above 128");
+    hipLaunchKernelGGL(refresh_rope_rows_kernel, dim3(B), dim3(64), 0, s, ctx_len, rr);
+}
+
+// RoPE tables [n_pos][half]: theta_i = base^(-i/half), f32 like MLXNN.RoPE(traditional: false)
+void rope_tables_host(float theta, int half, int n_pos, std::vector<float>& c, std::vector<float>& sn) {
+    c.resize((size_t)n_pos * half);
+    sn.resize((size_t)n_pos * half);
+    const float k = (float)(-std::log((double)theta) / (double)half);
+    for (int i = 0; i < half; ++i) {
+        const float inv = expf((float)i * k);
+        for (int p = 0; p < n_pos; ++p) {
+            const float ang = (float)p * inv;
+            c[(size_t)p * half + i] = cosf(ang);
+            sn[(size_t)p * half + i] = sinf(ang);
+        }
+    }
+}
+
 // decode-step weights are streamed as MFMA A fragments: keep a fragment-major copy (1.19 GB extra for 0.6B)
 const bf16_t* Engine::packed_copy(const bf16_t* w, int N, int K) {
     if (N % 16 != 0 || K % 32 != 0) return nullptr;
@@ -227,17 +248,8 @@ void Engine::finalize_decoder() {
     max_pos_ = cfg_.max_batch * max_prompt_;
     // RoPE tables: theta_i = base^(-i/half), f32 like MLXNN.RoPE(traditional: false)
     {
-        const int half = hd / 2;
-        std::vector<float> c((size_t)max_ctx_ * half), sn((size_t)max_ctx_ * half);
-        const float k = (float)(-std::log((double)cfg_.rope_theta) / (double)half);
-        for (int i = 0; i < half; ++i) {
-            const float inv = expf((float)i * k);
-            for (int p = 0; p < max_ctx_; ++p) {
-                const float ang = (float)p * inv;
-                c[(size_t)p * half + i] = cosf(ang);
-                sn[(size_t)p * half + i] = sinf(ang);
-            }
-        }
+        std::vector<float> c, sn;
+        rope_tables_host(cfg_.rope_theta, hd / 2, max_ctx_, c, sn);
         d_rope_cos_.alloc(c.size() * sizeof(float));
         d_rope_sin_.alloc(sn.size() * sizeof(float));
         QASR_HIP(hipMemcpyAsync(d_rope_cos_.p, c.data(), c.size() * sizeof(float), hipMemcpyHostToDevice, stream_));
@@ -841,7 +853,7 @@ __global__ void set_ints_kernel(int* dst, const int* src, int n) {
 // qasr_decode_forced (B = 1) and qasr_batch_decode_forced all step through here.
 void Engine::forced_step(const int* d_ids, int B) {
     embed_rows(d_ids, d_dx_.as<bf16_t>(), B, stream_);
-    hipLaunchKernelGGL(refresh_rope_rows_kernel, dim3(B), dim3(64), 0, stream_, gstate_.ctx_len, rope_rows(0));
+    refresh_rope_rows_launch(gstate_.ctx_len, rope_rows(0), B, stream_);
     run_decode_step(true, false, 0, B, stream_, true);
     hipLaunchKernelGGL(add_scalar_kernel, dim3(cdiv(B, 64)), dim3(64), 0, stream_, gstate_.ctx_len, B, 1);
 }

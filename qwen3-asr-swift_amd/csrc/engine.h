@@ -112,6 +112,10 @@ public:
     // qasr_gemm_case_probe (csrc/gemm_cases.hip): one operand gather + epilogue pair of the product, launched once on host data
     void gemm_case_probe(int which, int form, const qasr_gemm_case& g, const uint16_t* A, const uint16_t* W, const void* bias,
                          const int32_t* aux_i, const int64_t* aux_l, const float* aux_f, void* out);
+    // qasr_attn_case_probe (csrc/attn_cases.hip): the prompt-side cache writers + prompt attention, or one decode attention launch, on host data
+    void attn_case_probe(int op, const qasr_attn_case& g, uint16_t* qkv, const uint16_t* x, const uint16_t* W, const int32_t* cu,
+                         const int32_t* slot_of_clip, const int32_t* pos, const int32_t* slot, const uint16_t* qn_w, const uint16_t* kn_w,
+                         uint16_t* kcache, uint16_t* vfrag, const uint16_t* vt, uint16_t* qr, uint16_t* out);
     void kernel_probe(int which, int reps, float* avg_ms, double* bytes_per_launch);
     int batch_size() const { return batch_; }
     void decode_structure(int* fused_qa, int* chain, int* launches_per_layer);
