@@ -900,7 +900,8 @@ int qasr_xvec_timing(const qasr_xvec* x, float* ms);
  * HBM: the packed weights (0.6B 4-bit: about 0.5 GB with the bf16 embedding tables) plus the Talker KV cache, 2 images x layers x
  * kv_heads x head_dim x 2 bytes x positions per row: 28 x 8 x 128 x 2 x 2 = 114,688 bytes per position; positions = max_instruct + 11
  * prompt + max_frames + 1, rounded up to 32 (544 by default; the 510 a row can reach are 3.8 GB of it at max_batch 64, the allocation 4.0 GB).
- * Not covered: ICL voice cloning, streaming, top_p < 1, the text tokenizer. */
+ * ICL voice cloning (Qwen3TTS+ICL.swift: synthesizeWithVoiceCloneICL) is qasr_tts_*_icl / qasr_tts_clone below, on a handle from
+ * qasr_tts_create_icl.  Not covered: streaming, top_p < 1, the text tokenizer, host resampling, ReferenceAudioCache. */
 typedef struct qasr_tts qasr_tts;
 typedef struct qasr_tts_config {
     int32_t hidden, layers, heads, kv_heads, head_dim, inter;          /* Talker: 1024 28 16 8 128 3072 (1.7B: 2048 .. 6144) */
@@ -960,6 +961,46 @@ int qasr_tts_sample_host(const qasr_tts_config* cfg, const float* logits, int32_
  * codes / n_frames as qasr_tts_generate, may be NULL. */
 int qasr_tts_synthesize(qasr_tts* t, qasr_codec* codec, const qasr_tts_request* rq, const qasr_tts_sampling* s, uint64_t seed,
                         float* const* pcm, size_t* n_samples, int32_t* codes, int32_t* n_frames);
+
+/* ---- ICL voice cloning (Sources/Qwen3TTS/Qwen3TTS+ICL.swift) ---------------------------------------------------
+ * The reference clip's codes (qasr_codec_enc_encode) and transcript go into the Talker's context beside the x-vector.  A row's prompt has
+ * P = 11 + ref_text_len + target ids + ref_frames positions (buildICLPrefillEmbeddings): role 3 | tts_pad x 5 + tts_bos over think,
+ * think_bos, language, think_eos, x-vector, codec_pad | reference-text ids, then target ids, then tts_eos, each over codec_pad | tts_pad
+ * over codec_bos | tts_pad over the summed 16 code embeddings of every reference frame.  No trailing text: every generated frame adds tts_pad.
+ * rq->text stays templated (role = text[0..3), target ids = text[3 .. n-5)); rq->xvector[b] is required; a speaker token or an instruct
+ * prefix -> QASR_ERR_INVALID; a reference code outside its table (stream 0: codec_vocab, streams 1..15: cp_vocab) -> QASR_ERR_INVALID (not
+ * clamped); ref_frames / ref_text_len over the handle's capacity -> QASR_ERR_CAPACITY (a handle from qasr_tts_create has capacity 0).
+ * Every refusal names the row in qasr_tts_last_error.
+ * qasr_tts_create_icl is qasr_tts_create with the Talker cache, the RoPE tables and the prompt buffers sized for 11 + max_ref_text +
+ * max_text + max_ref_frames + max_frames + 1 positions, rounded up to 64 (the prompt pass moves the V images in blocks of 64 keys), at most
+ * 32768; over that, max_ref_frames < 1 or max_ref_text < 0 -> QASR_ERR_INVALID before any device call.  It also allocates the packed
+ * prompt pass's scratch: one layer of bf16 weights (0.6B: 31 MB) and, per prompt position and batch row, 2 x hidden + 3 x heads x
+ * head_dim + 2 x kv_heads x head_dim + inter bf16 values plus one V^T column (0.6B: 26,624 + 2,048 bytes) next to the 114,688 bytes
+ * of the cache.  qasr_tts_device_bytes counts all of it.  Tuning knob tts_packed_prompt: 1 = ICL prompts take one packed pass, 0 = one
+ * decode step per position; calls without ICL always take the step path. */
+typedef struct qasr_tts_icl {                                     /* accompanies a qasr_tts_request, one entry per row */
+    const int32_t* const* ref_text;  const int32_t* ref_text_len;  /* [B] tokenizer.encode(referenceText), no template; length >= 0 */
+    const int32_t* const* ref_codes; const int32_t* ref_frames;    /* [B] [16][ref_frames[b]] as qasr_codec_enc_encode writes them; >= 1 frame */
+} qasr_tts_icl;
+int qasr_tts_create_icl(const char* model_dir, const qasr_tts_config* cfg, int32_t max_ref_frames, int32_t max_ref_text, qasr_tts** out);
+int qasr_tts_icl_capacity(const qasr_tts* t, int32_t* max_ref_frames, int32_t* max_ref_text);     /* 0, 0 on a plain handle */
+/* as qasr_tts_generate / _forced / _synthesize with the ICL prompt */
+int qasr_tts_generate_icl(qasr_tts* t, const qasr_tts_request* rq, const qasr_tts_icl* icl, const qasr_tts_sampling* s, uint64_t seed,
+                          int32_t* codes, int32_t* n_frames);
+int qasr_tts_forced_icl(qasr_tts* t, const qasr_tts_request* rq, const qasr_tts_icl* icl, const int32_t* codes, size_t T, float* talker_logits,
+                        float* cp_logits, float* hidden);
+int qasr_tts_synthesize_icl(qasr_tts* t, qasr_codec* codec, const qasr_tts_request* rq, const qasr_tts_icl* icl, const qasr_tts_sampling* s,
+                            uint64_t seed, float* const* pcm, size_t* n_samples, int32_t* codes, int32_t* n_frames);
+/* the prompt rows as the Talker reads them: rows [B][P_max][hidden] (bf16 values widened, zeros past a row's P; P_max = the call's longest,
+ * at most 11 + max_ref_text + max_text + max_ref_frames), P [B] */
+int qasr_tts_icl_prompt(qasr_tts* t, const qasr_tts_request* rq, const qasr_tts_icl* icl, float* rows, int32_t* P);
+/* synthesizeWithVoiceCloneICL end to end for B rows: qasr_codec_enc_encode_batch -> qasr_xvec_embed_batch -> qasr_tts_synthesize_icl.
+ * rq->xvector is ignored; ref_pcm[b] [ref_n[b]] is 24 kHz mono (the reference resamples on the host: not rebuilt, nor its
+ * ReferenceAudioCache -- a caller who wants the cache keeps codes and x-vector and calls qasr_tts_synthesize_icl).  A speaker encoder
+ * whose embedding dimension is not the Talker's hidden size -> QASR_ERR_INVALID. */
+int qasr_tts_clone(qasr_tts* t, qasr_codec_enc* codec_enc, qasr_xvec* xvec, qasr_codec* codec, const qasr_tts_request* rq,
+                   const int32_t* const* ref_text, const int32_t* ref_text_len, const float* const* ref_pcm, const size_t* ref_n,
+                   const qasr_tts_sampling* s, uint64_t seed, float* const* pcm, size_t* n_samples, int32_t* codes, int32_t* n_frames);
 
 /* transducer greedy loops (pure CPU).  The caller owns the networks and their state:
  *   decoder_step(ctx, token)  advance the prediction network with `token` (the loops prime it with the blank id where the reference does)

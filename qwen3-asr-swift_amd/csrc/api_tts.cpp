@@ -55,6 +55,94 @@ static int check_request(qasr_tts* t, const qasr_tts_request* rq, std::vector<Tt
     return QASR_OK;
 }
 
+// the ICL side of a request (qasr_tts_icl), checked against the handle's capacity and the code tables; fills the rows' ICL fields
+static int check_icl(qasr_tts* t, const qasr_tts_icl* icl, std::vector<TtsRow>& rows) {
+    if (rows.empty()) return QASR_OK;
+    const qasr_tts_config& c = t->impl->config();
+    const int cap_f = t->impl->max_ref_frames(), cap_t = t->impl->max_ref_text();
+    if (!icl || !icl->ref_codes || !icl->ref_frames || !icl->ref_text_len) return fail(t, QASR_ERR_INVALID, WHO + ": null ICL argument");
+    for (size_t b = 0; b < rows.size(); ++b) {
+        const std::string row = WHO + ": row " + std::to_string(b) + ": ";
+        TtsRow& r = rows[b];
+        if (!r.xvector) return fail(t, QASR_ERR_INVALID, row + "an ICL row needs an x-vector");
+        if (r.speaker >= 0) return fail(t, QASR_ERR_INVALID, row + "a speaker token on an ICL call");
+        if (r.n_instruct > 0) return fail(t, QASR_ERR_INVALID, row + "an instruct prefix on an ICL call");
+        r.n_ref_text = icl->ref_text_len[b];
+        r.ref_text = icl->ref_text ? icl->ref_text[b] : nullptr;
+        r.ref_frames = icl->ref_frames[b];
+        r.ref_codes = icl->ref_codes[b];
+        if (r.n_ref_text < 0) return fail(t, QASR_ERR_INVALID, row + "negative reference text length");
+        if (r.ref_frames < 1) return fail(t, QASR_ERR_INVALID, row + "an ICL row needs at least 1 reference frame");
+        if (r.ref_frames > cap_f)
+            return fail(t, QASR_ERR_CAPACITY, row + std::to_string(r.ref_frames) + " reference frames, more than max_ref_frames = " + std::to_string(cap_f));
+        if (r.n_ref_text > cap_t)
+            return fail(t, QASR_ERR_CAPACITY, row + "reference text of " + std::to_string(r.n_ref_text) + " ids, more than max_ref_text = " + std::to_string(cap_t));
+        if (!r.ref_codes || (r.n_ref_text > 0 && !r.ref_text)) return fail(t, QASR_ERR_INVALID, row + "null reference codes or text");
+        for (int i = 0; i < r.n_ref_text; ++i)
+            if (r.ref_text[i] < 0 || r.ref_text[i] >= c.text_vocab)
+                return fail(t, QASR_ERR_INVALID, row + "reference text id " + std::to_string(r.ref_text[i]) + " outside the text vocabulary");
+        for (int g = 0; g < TTS_GROUPS; ++g)
+            for (int f = 0; f < r.ref_frames; ++f) {
+                const int v = r.ref_codes[(size_t)g * r.ref_frames + f];
+                if (v < 0 || v >= (g == 0 ? c.codec_vocab : c.cp_vocab))
+                    return fail(t, QASR_ERR_INVALID, row + "reference code " + std::to_string(v) + " of stream " + std::to_string(g) + " outside its table");
+            }
+    }
+    return QASR_OK;
+}
+
+static int check_forced_codes(qasr_tts* t, size_t B, const int32_t* codes, size_t T) {
+    const qasr_tts_config& c = t->impl->config();
+    if (!codes) return fail(t, QASR_ERR_INVALID, WHO + ": null codes");
+    if (T > (size_t)c.max_frames) return fail(t, QASR_ERR_CAPACITY, WHO + ": " + std::to_string(T) + " forced frames, more than max_frames");
+    for (size_t b = 0; b < B; ++b)
+        for (int g = 0; g < TTS_GROUPS; ++g)
+            for (size_t i = 0; i < T; ++i) {
+                const int v = codes[(b * TTS_GROUPS + g) * T + i];
+                if (v < 0 || v >= (g == 0 ? c.codec_vocab : c.cp_vocab))
+                    return fail(t, QASR_ERR_INVALID, WHO + ": forced code " + std::to_string(v) + " of stream " + std::to_string(g) + " outside its vocabulary");
+            }
+    return QASR_OK;
+}
+
+static int create_handle(const char* model_dir, const qasr_tts_config* cfg, bool icl, int max_ref_frames, int max_ref_text, qasr_tts** out) {
+    if (!out) return QASR_ERR_INVALID;
+    *out = nullptr;
+    if (!model_dir || !cfg) return fail<qasr_tts>(nullptr, QASR_ERR_INVALID, WHO + ": model_dir or cfg is NULL");
+    try {
+        TtsTalker::check_geometry(*cfg);
+        if (icl) (void)TtsTalker::icl_context(*cfg, max_ref_frames, max_ref_text);
+    } catch (const std::exception& ex) { return fail<qasr_tts>(nullptr, QASR_ERR_INVALID, ex.what()); }
+    std::unique_ptr<SafeTensorsDir> st;            // all *.safetensors of the directory (TTSWeightLoading.swift:24-30); other keys are not read
+    try { st = std::make_unique<SafeTensorsDir>(model_dir); }
+    catch (const std::exception& ex) { return fail<qasr_tts>(nullptr, QASR_ERR_IO, WHO + ": " + ex.what()); }
+    qasr_tts* h = new qasr_tts();
+    try { h->impl = std::make_unique<TtsTalker>(*cfg, *st, icl ? max_ref_frames : 0, icl ? max_ref_text : 0); }
+    catch (const WeightLoadError& ex) { delete h; return fail<qasr_tts>(nullptr, ex.code, ex.what()); }
+    catch (const HipError& ex) { delete h; return fail<qasr_tts>(nullptr, QASR_ERR_HIP, ex.what()); }
+    catch (const std::exception& ex) { delete h; return fail<qasr_tts>(nullptr, QASR_ERR_INVALID, ex.what()); }
+    *out = h;
+    return QASR_OK;
+}
+
+// codes [B][16][max_frames] of a generate call -> pcm through the caller's codec handle
+static int decode_rows(qasr_tts* t, qasr_codec* codec, size_t B, const int32_t* codes, const int32_t* n_frames, float* const* pcm, size_t* n_samples) {
+    const size_t F = (size_t)t->impl->config().max_frames, spf = (size_t)qasr_codec_samples_per_frame();
+    std::vector<int32_t> row;
+    for (size_t b = 0; b < B; ++b) {
+        const size_t T = (size_t)n_frames[b];
+        n_samples[b] = spf * T;
+        if (T == 0) continue;                                            // EOS first: an empty waveform
+        if (!pcm[b]) return fail(t, QASR_ERR_INVALID, WHO + ": null pcm buffer");
+        row.resize(TTS_GROUPS * T);                                      // [16][T] of the row's [16][max_frames]
+        for (int g = 0; g < TTS_GROUPS; ++g)
+            for (size_t i = 0; i < T; ++i) row[g * T + i] = codes[(b * TTS_GROUPS + g) * F + i];
+        if (int rc = qasr_codec_decode(codec, row.data(), T, pcm[b]))
+            return fail(t, rc, WHO + ": codec: " + qasr_codec_last_error(codec));
+    }
+    return QASR_OK;
+}
+
 static int check_sampling(qasr_tts* t, const qasr_tts_sampling* s) {
     if (!s) return fail(t, QASR_ERR_INVALID, WHO + ": null sampling");
     if (s->top_p < 1.0f)
@@ -95,20 +183,17 @@ void qasr_tts_default_sampling(int greedy, qasr_tts_sampling* out) {
 int qasr_tts_poll_interval(void) { return TTS_POLL; }
 
 int qasr_tts_create(const char* model_dir, const qasr_tts_config* cfg, qasr_tts** out) {
-    if (!out) return QASR_ERR_INVALID;
-    *out = nullptr;
-    if (!model_dir || !cfg) return fail<qasr_tts>(nullptr, QASR_ERR_INVALID, WHO + ": model_dir or cfg is NULL");
-    try { TtsTalker::check_geometry(*cfg); }
-    catch (const std::exception& ex) { return fail<qasr_tts>(nullptr, QASR_ERR_INVALID, ex.what()); }
-    std::unique_ptr<SafeTensorsDir> st;            // all *.safetensors of the directory (TTSWeightLoading.swift:24-30); other keys are not read
-    try { st = std::make_unique<SafeTensorsDir>(model_dir); }
-    catch (const std::exception& ex) { return fail<qasr_tts>(nullptr, QASR_ERR_IO, WHO + ": " + ex.what()); }
-    qasr_tts* h = new qasr_tts();
-    try { h->impl = std::make_unique<TtsTalker>(*cfg, *st); }
-    catch (const WeightLoadError& ex) { delete h; return fail<qasr_tts>(nullptr, ex.code, ex.what()); }
-    catch (const HipError& ex) { delete h; return fail<qasr_tts>(nullptr, QASR_ERR_HIP, ex.what()); }
-    catch (const std::exception& ex) { delete h; return fail<qasr_tts>(nullptr, QASR_ERR_INVALID, ex.what()); }
-    *out = h;
+    return create_handle(model_dir, cfg, false, 0, 0, out);
+}
+
+int qasr_tts_create_icl(const char* model_dir, const qasr_tts_config* cfg, int32_t max_ref_frames, int32_t max_ref_text, qasr_tts** out) {
+    return create_handle(model_dir, cfg, true, max_ref_frames, max_ref_text, out);
+}
+
+int qasr_tts_icl_capacity(const qasr_tts* t, int32_t* max_ref_frames, int32_t* max_ref_text) {
+    if (!t || !t->impl) return QASR_ERR_INVALID;
+    if (max_ref_frames) *max_ref_frames = t->impl->max_ref_frames();
+    if (max_ref_text) *max_ref_text = t->impl->max_ref_text();
     return QASR_OK;
 }
 
@@ -133,18 +218,42 @@ int qasr_tts_forced(qasr_tts* t, const qasr_tts_request* rq, const int32_t* code
     std::vector<TtsRow> rows;
     if (int rc = check_request(t, rq, rows)) return rc;
     if (rows.empty() || T == 0) return QASR_OK;
-    const qasr_tts_config& c = t->impl->config();
-    if (!codes) return fail(t, QASR_ERR_INVALID, WHO + ": null codes");
-    if (T > (size_t)c.max_frames) return fail(t, QASR_ERR_CAPACITY, WHO + ": " + std::to_string(T) + " forced frames, more than max_frames");
-    for (size_t b = 0; b < rows.size(); ++b)
-        for (int g = 0; g < TTS_GROUPS; ++g)
-            for (size_t i = 0; i < T; ++i) {
-                const int v = codes[(b * TTS_GROUPS + g) * T + i];
-                if (v < 0 || v >= (g == 0 ? c.codec_vocab : c.cp_vocab))
-                    return fail(t, QASR_ERR_INVALID, WHO + ": forced code " + std::to_string(v) + " of stream " + std::to_string(g) + " outside its vocabulary");
-            }
+    if (int rc = check_forced_codes(t, rows.size(), codes, T)) return rc;
     TtsForcedOut f{codes, (int)T, talker_logits, cp_logits, hidden};
     return guarded(t, [&] { t->impl->forced(rows, f); });
+}
+
+int qasr_tts_generate_icl(qasr_tts* t, const qasr_tts_request* rq, const qasr_tts_icl* icl, const qasr_tts_sampling* s, uint64_t seed,
+                          int32_t* codes, int32_t* n_frames) {
+    std::vector<TtsRow> rows;
+    if (int rc = check_request(t, rq, rows)) return rc;
+    if (int rc = check_icl(t, icl, rows)) return rc;
+    if (int rc = check_sampling(t, s)) return rc;
+    if (rows.empty()) return QASR_OK;
+    if (!codes || !n_frames) return fail(t, QASR_ERR_INVALID, WHO + ": null output");
+    const int cap = t->impl->config().max_frames;
+    const int frames = s->max_tokens > 0 && s->max_tokens < cap ? s->max_tokens : cap;
+    return guarded(t, [&] { t->impl->generate(rows, *s, seed, frames, codes, n_frames); });
+}
+
+int qasr_tts_forced_icl(qasr_tts* t, const qasr_tts_request* rq, const qasr_tts_icl* icl, const int32_t* codes, size_t T, float* talker_logits,
+                        float* cp_logits, float* hidden) {
+    std::vector<TtsRow> rows;
+    if (int rc = check_request(t, rq, rows)) return rc;
+    if (int rc = check_icl(t, icl, rows)) return rc;
+    if (rows.empty() || T == 0) return QASR_OK;
+    if (int rc = check_forced_codes(t, rows.size(), codes, T)) return rc;
+    TtsForcedOut f{codes, (int)T, talker_logits, cp_logits, hidden};
+    return guarded(t, [&] { t->impl->forced(rows, f); });
+}
+
+int qasr_tts_icl_prompt(qasr_tts* t, const qasr_tts_request* rq, const qasr_tts_icl* icl, float* rows_out, int32_t* P) {
+    std::vector<TtsRow> rows;
+    if (int rc = check_request(t, rq, rows)) return rc;
+    if (int rc = check_icl(t, icl, rows)) return rc;
+    if (rows.empty()) return QASR_OK;
+    if (!rows_out || !P) return fail(t, QASR_ERR_INVALID, WHO + ": null output");
+    return guarded(t, [&] { t->impl->icl_prompt(rows, rows_out, P); });
 }
 
 int qasr_tts_sample_host(const qasr_tts_config* cfg, const float* logits, int32_t V, int talker, const qasr_tts_sampling* s,
@@ -172,20 +281,60 @@ int qasr_tts_synthesize(qasr_tts* t, qasr_codec* codec, const qasr_tts_request* 
     if (!codes) { own_codes.resize(B * TTS_GROUPS * F); codes = own_codes.data(); }
     if (!n_frames) { own_frames.resize(B); n_frames = own_frames.data(); }
     if (int rc = qasr_tts_generate(t, rq, s, seed, codes, n_frames)) return rc;
-    const size_t spf = (size_t)qasr_codec_samples_per_frame();
-    std::vector<int32_t> row;
+    return decode_rows(t, codec, B, codes, n_frames, pcm, n_samples);
+}
+
+int qasr_tts_synthesize_icl(qasr_tts* t, qasr_codec* codec, const qasr_tts_request* rq, const qasr_tts_icl* icl, const qasr_tts_sampling* s,
+                            uint64_t seed, float* const* pcm, size_t* n_samples, int32_t* codes, int32_t* n_frames) {
+    if (!t || !t->impl) return QASR_ERR_INVALID;
+    if (!codec || !rq || !pcm || !n_samples) return fail(t, QASR_ERR_INVALID, WHO + ": null argument");
+    const size_t B = rq->B, F = (size_t)t->impl->config().max_frames;
+    std::vector<int32_t> own_codes, own_frames;
+    if (!codes) { own_codes.resize(B * TTS_GROUPS * F); codes = own_codes.data(); }
+    if (!n_frames) { own_frames.resize(B); n_frames = own_frames.data(); }
+    if (int rc = qasr_tts_generate_icl(t, rq, icl, s, seed, codes, n_frames)) return rc;
+    return decode_rows(t, codec, B, codes, n_frames, pcm, n_samples);
+}
+
+// synthesizeWithVoiceCloneICL (Qwen3TTS+ICL.swift:49-145) for B rows: codes and x-vector of every reference clip, then the ICL call
+int qasr_tts_clone(qasr_tts* t, qasr_codec_enc* codec_enc, qasr_xvec* xvec, qasr_codec* codec, const qasr_tts_request* rq,
+                   const int32_t* const* ref_text, const int32_t* ref_text_len, const float* const* ref_pcm, const size_t* ref_n,
+                   const qasr_tts_sampling* s, uint64_t seed, float* const* pcm, size_t* n_samples, int32_t* codes, int32_t* n_frames) {
+    if (!t || !t->impl) return QASR_ERR_INVALID;
+    if (!codec_enc || !xvec || !codec || !rq || !ref_pcm || !ref_n || !ref_text_len) return fail(t, QASR_ERR_INVALID, WHO + ": null argument");
+    const size_t B = rq->B;
+    const int H = t->impl->config().hidden, E = qasr_xvec_embedding_dim(xvec);
+    if (E != H)
+        return fail(t, QASR_ERR_INVALID, WHO + ": the speaker encoder's embedding holds " + std::to_string(E) + " floats, the Talker's hidden size is " + std::to_string(H));
+    if (B > (size_t)t->impl->config().max_batch)
+        return fail(t, QASR_ERR_CAPACITY, WHO + ": " + std::to_string(B) + " rows, more than max_batch = " + std::to_string(t->impl->config().max_batch));
+    if (B == 0) return QASR_OK;
+    std::vector<std::vector<int32_t>> rc_store(B);
+    std::vector<int32_t*> rc_ptr(B);
+    std::vector<const int32_t*> rc_cptr(B);
+    std::vector<int32_t> frames(B);
     for (size_t b = 0; b < B; ++b) {
-        const size_t T = (size_t)n_frames[b];
-        n_samples[b] = spf * T;
-        if (T == 0) continue;                                            // EOS first: an empty waveform
-        if (!pcm[b]) return fail(t, QASR_ERR_INVALID, WHO + ": null pcm buffer");
-        row.resize(TTS_GROUPS * T);                                      // [16][T] of the row's [16][max_frames]
-        for (int g = 0; g < TTS_GROUPS; ++g)
-            for (size_t i = 0; i < T; ++i) row[g * T + i] = codes[(b * TTS_GROUPS + g) * F + i];
-        if (int rc = qasr_codec_decode(codec, row.data(), T, pcm[b]))
-            return fail(t, rc, WHO + ": codec: " + qasr_codec_last_error(codec));
+        const std::string row = WHO + ": row " + std::to_string(b) + ": ";
+        if (!ref_pcm[b] || ref_n[b] == 0) return fail(t, QASR_ERR_INVALID, row + "empty reference clip");
+        const size_t f = qasr_codec_enc_num_frames(ref_n[b]);
+        if (f > (size_t)t->impl->max_ref_frames())
+            return fail(t, QASR_ERR_CAPACITY, row + std::to_string(f) + " reference frames, more than max_ref_frames = " + std::to_string(t->impl->max_ref_frames()));
+        frames[b] = (int32_t)f;
+        rc_store[b].resize(TTS_GROUPS * f);
+        rc_ptr[b] = rc_store[b].data();
+        rc_cptr[b] = rc_store[b].data();
     }
-    return QASR_OK;
+    if (qasr_codec_enc_num_quantizers(codec_enc) != TTS_GROUPS) return fail(t, QASR_ERR_INVALID, WHO + ": the speech tokenizer encoder does not write 16 code streams");
+    if (int rc = qasr_codec_enc_encode_batch(codec_enc, ref_pcm, ref_n, B, rc_ptr.data()))
+        return fail(t, rc, WHO + ": codec encoder: " + qasr_codec_enc_last_error(codec_enc));
+    std::vector<float> xv(B * (size_t)H);
+    if (int rc = qasr_xvec_embed_batch(xvec, ref_pcm, ref_n, B, xv.data())) return fail(t, rc, WHO + ": speaker encoder: " + qasr_xvec_last_error(xvec));
+    std::vector<const float*> xp(B);
+    for (size_t b = 0; b < B; ++b) xp[b] = xv.data() + b * (size_t)H;
+    qasr_tts_request q = *rq;
+    q.xvector = xp.data();
+    qasr_tts_icl icl{ref_text, ref_text_len, rc_cptr.data(), frames.data()};
+    return qasr_tts_synthesize_icl(t, codec, &q, &icl, s, seed, pcm, n_samples, codes, n_frames);
 }
 
 }  // extern "C"

@@ -5,7 +5,8 @@
 // generateWithCodePredictor, predictCodebooksForTimestep), TTSWeightLoading.swift:24-158 (keys).  MLX affine 4 / 8 bit Linears stay packed
 // (dec_quant.h); bf16 activations between layers, f32 accumulation, f32 norms / softmax / logits.  Nothing here is shared with the Engine
 // class: the layer GEMVs and the Talker's attention are the decode step's launch functions (decode_gemv_q_launch,
-// decode_attention_launch), everything else is in tts_talker.hip.  DESIGN.md section 18.
+// decode_attention_launch), and for ICL prompts the engine's prompt-pass launch functions (quant_dequant_multi_launch, gemm_nt*,
+// qk_norm_rope_launch, prefill_attention_launch); everything else is in tts_talker.hip.  DESIGN.md section 18.
 #pragma once
 #include "engine.h"
 #include "dec_quant.h"
@@ -24,6 +25,9 @@ constexpr int TTS_MAX_FRAMES = 500;     // the reference's safeMaxTokens (Qwen3T
 constexpr int TTS_POLL = 8;             // frames between two host reads of the finished flags
 constexpr int TTS_MAX_VOCAB = 4096;     // logits of one sampler workgroup (LDS image)
 constexpr int TTS_TEMPLATE = 9;         // <|im_start|>assistant\n ... <|im_end|>\n<|im_start|>assistant\n
+constexpr int TTS_ICL_FIXED = 11;       // positions of an ICL prompt beside its texts and frames: role 3, codec prefix 6, tts_eos, codec_bos
+constexpr int TTS_MAX_CTX = 32768;      // positions of a row: the Talker's max_position_embeddings (Configuration.swift), which is also what
+                                        // the prompt kernels were checked for (32-bit byte offsets inside one V^T row block: 128 x stride x 2)
 
 // ---- the sampler, stated once for the device kernel and the host twin (tts_sampler.cpp) ------------------------------------------
 struct TtsSampleParams {
@@ -59,6 +63,9 @@ struct TtsRow {                         // one row of a request, checked by the 
     const float* xvector;               // [hidden] or null
     const int32_t* instruct; int n_instruct;
     long long index;                    // the caller's row index (random stream)
+    // ICL voice cloning (Qwen3TTS+ICL.swift): the reference clip's transcript ids and its codes [16][ref_frames]; ref_codes null: a plain row
+    const int32_t* ref_text = nullptr; int n_ref_text = 0;
+    const int32_t* ref_codes = nullptr; int ref_frames = 0;
 };
 
 struct TtsForcedOut {                   // qasr_tts_forced: any pointer may be null
@@ -71,7 +78,8 @@ struct TtsForcedOut {                   // qasr_tts_forced: any pointer may be n
 class TtsTalker {
   public:
     // every key, shape and dtype is checked on the host before any HIP call (WeightLoadError); `cfg` is complete (api_tts.cpp)
-    TtsTalker(const qasr_tts_config& cfg, const SafeTensorsDir& st);
+    // max_ref_frames > 0: an ICL handle (context, prompt buffers and the packed prompt pass's scratch sized for reference clips)
+    TtsTalker(const qasr_tts_config& cfg, const SafeTensorsDir& st, int max_ref_frames = 0, int max_ref_text = 0);
     ~TtsTalker();
     const qasr_tts_config& config() const { return cfg_; }
     size_t footprint() const { return param_bytes_; }
@@ -80,7 +88,12 @@ class TtsTalker {
     void generate(const std::vector<TtsRow>& rows, const qasr_tts_sampling& s, unsigned long long seed, int max_frames, int32_t* codes,
                   int32_t* n_frames);
     void forced(const std::vector<TtsRow>& rows, const TtsForcedOut& f);
+    // the prompt rows of an ICL call as the Talker would read them: rows [B][P_max][hidden] (bf16 values widened, zeros past a row's P), P [B]
+    void icl_prompt(const std::vector<TtsRow>& rows, float* out, int32_t* P);
+    int max_ref_frames() const { return max_ref_frames_; }
+    int max_ref_text() const { return max_ref_text_; }
     static void check_geometry(const qasr_tts_config& c);      // std::invalid_argument for what the kernels do not serve
+    static int icl_context(const qasr_tts_config& c, int max_ref_frames, int max_ref_text);   // positions of an ICL handle; throws over TTS_MAX_CTX
     struct Knobs;                        // device-side per-call values (tts_talker.hip)
 
   private:
@@ -92,7 +105,8 @@ class TtsTalker {
     void load_net(const SafeTensorsDir& st, const std::string& prefix, Net& n, int layers);
     void load_all(const SafeTensorsDir& st);
     void* dev_upload(const void* src, size_t bytes);
-    void prefill(const std::vector<TtsRow>& rows);
+    void prefill(const std::vector<TtsRow>& rows, bool build_only = false);
+    void packed_prompt(int B, int Pmax);
     void layer_steps(const Net& n, bf16_t* x, int B, bool talker, int cp_pos, bool kv_only_last);
     void issue_frame(int B, bool forced_mode);
     void run_frame(int B);
@@ -109,6 +123,15 @@ class TtsTalker {
     const bf16_t *codec_emb_ = nullptr, *text_emb_ = nullptr, *cp_emb_[TTS_GROUPS - 1] = {};
     const bf16_t** d_cp_emb_ = nullptr;
     int max_ctx_ = 0, max_prefill_ = 0, max_tp_ = 0;
+    int max_ref_frames_ = 0, max_ref_text_ = 0;
+    // ICL handles: the reference codes of a call, and the packed prompt pass's scratch (one layer of bf16 weights, activations of every
+    // packed position, the V^T image, the per-position slot / position and per-row offsets)
+    int* d_ref_codes_ = nullptr;
+    int max_pos_ = 0, vt_stride_ = 0;
+    bf16_t *d_w_ = nullptr, *d_vt_ = nullptr, *d_px_ = nullptr, *d_ph_ = nullptr, *d_pqkv_ = nullptr, *d_pqr_ = nullptr, *d_pattn_ = nullptr,
+           *d_pact_ = nullptr;
+    int* d_pmeta_ = nullptr;
+    std::vector<int> pf_len_;                                  // prompt length of every row of the last prefill
     float *d_rope_cos_ = nullptr, *d_rope_sin_ = nullptr, *d_cp_cos_ = nullptr, *d_cp_sin_ = nullptr, *d_rope_rows_ = nullptr;
     bf16_t *d_k_ = nullptr, *d_vf_ = nullptr, *d_cpk_ = nullptr, *d_cpv_ = nullptr;
     bf16_t *d_x_ = nullptr, *d_hn_ = nullptr, *d_qkv_ = nullptr, *d_attn_ = nullptr, *d_act_ = nullptr, *d_scratch_ = nullptr;

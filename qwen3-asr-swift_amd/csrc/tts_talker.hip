@@ -338,18 +338,39 @@ __global__ __launch_bounds__(256) void tts_gather_rows_kernel(const bf16_t* __re
     for (int i = threadIdx.x; i < W; i += 256) out[r * W + i] = table[(long)ids[r] * W + i];
 }
 
-// pf[b][p] = bf16(text side + codec side): text side = tp[pf_text] (or nothing), codec side = codec_embedding[pf_codec] | the x-vector (-2)
+// pf[b][p] = bf16(text side + codec side): text side = tp[pf_text] (or nothing), codec side = codec_embedding[pf_codec] | the x-vector (-2) |
+// frame f = -3 - pf_codec of the row's ICL reference codes ref[b][16][ref_ld]: codec_embedding[c0] + the 15 code-predictor embeddings, added
+// in the order of tts_next_input_kernel (text, code 0, streams 1 .. 15) in f32 and rounded once.  The codes were checked by the C ABI.
 __global__ __launch_bounds__(256) void tts_prefill_build_kernel(const int* __restrict__ pf_text, const int* __restrict__ pf_codec, int P,
                                                                 const bf16_t* __restrict__ tp, const bf16_t* __restrict__ codec_emb,
-                                                                const float* __restrict__ xvec, int H, bf16_t* __restrict__ pf) {
+                                                                const float* __restrict__ xvec, int H, bf16_t* __restrict__ pf,
+                                                                const int* __restrict__ ref, int ref_ld, const bf16_t* const* __restrict__ cp_emb) {
+    __shared__ int s_c[TTS_GROUPS];
     const int p = blockIdx.x, b = blockIdx.y;
     const int ti = pf_text[(long)b * P + p], ci = pf_codec[(long)b * P + p];
+    if (ci <= -3) {                                                     // block-uniform
+        if (threadIdx.x < TTS_GROUPS) s_c[threadIdx.x] = ref[((long)b * TTS_GROUPS + threadIdx.x) * ref_ld + (-3 - ci)];
+        __syncthreads();
+    }
     for (int i = threadIdx.x; i < H; i += 256) {
         float s = ti >= 0 ? bf16_to_f32(tp[(long)ti * H + i]) : 0.0f;
         if (ci >= 0) s += bf16_to_f32(codec_emb[(long)ci * H + i]);
         else if (ci == -2) s += xvec[(long)b * H + i];
+        else if (ci <= -3) {
+            s += bf16_to_f32(codec_emb[(long)s_c[0] * H + i]);
+            for (int g = 0; g < TTS_GROUPS - 1; ++g) s += bf16_to_f32(cp_emb[g][(long)s_c[g + 1] * H + i]);
+        }
         pf[((long)b * P + p) * H + i] = f32_to_bf16(s);
     }
+}
+
+// packed prompt pass: x[p] = pf[slot[p]][pos[p]] for the packed positions (every prompt position of a row but its last)
+__global__ __launch_bounds__(128) void tts_pack_rows_kernel(const bf16_t* __restrict__ pf, int pf_ld, const int* __restrict__ slot,
+                                                            const int* __restrict__ pos, int H, bf16_t* __restrict__ x) {
+    const long p = blockIdx.x;
+    const uint4* src = reinterpret_cast<const uint4*>(pf + ((long)slot[p] * pf_ld + pos[p]) * H);
+    uint4* dst = reinterpret_cast<uint4*>(x + p * H);
+    for (int i = threadIdx.x; i < H / 8; i += 128) dst[i] = src[i];
 }
 
 // step s of the prompt pass over prompts that END together: row b feeds its position s - (P - len[b]); before its first position it
@@ -610,9 +631,25 @@ void TtsTalker::load_all(const SafeTensorsDir& st) {
     }
 }
 
-TtsTalker::TtsTalker(const qasr_tts_config& cfg, const SafeTensorsDir& st) : cfg_(cfg) {
+int TtsTalker::icl_context(const qasr_tts_config& c, int max_ref_frames, int max_ref_text) {
+    auto bad = [](const std::string& m) { throw std::invalid_argument(std::string(WHO) + ": " + m); };
+    if (max_ref_frames < 1) bad("max_ref_frames must be at least 1 for an ICL handle");
+    if (max_ref_text < 0) bad("max_ref_text must not be negative");
+    // 64: the prompt pass writes and reads the V images in blocks of 64 keys (v_transpose_kernel, prefill_attention2_kernel)
+    const long prompt = std::max<long>((long)c.max_instruct + 11, (long)TTS_ICL_FIXED + max_ref_text + c.max_text + max_ref_frames);
+    const long ctx = (prompt + c.max_frames + 1 + 63) / 64 * 64;
+    if (ctx > TTS_MAX_CTX)
+        bad("an ICL context of " + std::to_string(ctx) + " positions (11 + max_ref_text + max_text + max_ref_frames + max_frames + 1) is over the limit of " +
+            std::to_string(TTS_MAX_CTX) + " positions");
+    return (int)ctx;
+}
+
+TtsTalker::TtsTalker(const qasr_tts_config& cfg, const SafeTensorsDir& st, int max_ref_frames, int max_ref_text)
+    : cfg_(cfg), max_ref_frames_(max_ref_frames), max_ref_text_(max_ref_frames > 0 ? max_ref_text : 0) {
     check_geometry(cfg_);
     const auto& c = cfg_;
+    const bool icl = max_ref_frames_ > 0;
+    const int icl_ctx = icl ? icl_context(c, max_ref_frames_, max_ref_text_) : 0;
     dry_ = true;
     load_all(st);                                                          // throws before any HIP call
     dry_ = false;
@@ -623,8 +660,9 @@ TtsTalker::TtsTalker(const qasr_tts_config& cfg, const SafeTensorsDir& st) : cfg
         // ---- tables, caches, workspaces -------------------------------------------------------------------------------------
         const int B = c.max_batch, H = c.hidden, half = c.head_dim / 2;
         max_prefill_ = c.max_instruct + 11;                                 // instruct + role 3 + codec prefix (<= 8) - 1 + first text
-        max_ctx_ = ((max_prefill_ + c.max_frames + 1 + 31) / 32) * 32;
-        max_tp_ = 3 + B * (c.max_text + c.max_instruct);
+        if (icl) max_prefill_ = std::max(max_prefill_, TTS_ICL_FIXED + max_ref_text_ + c.max_text + max_ref_frames_);
+        max_ctx_ = icl ? icl_ctx : ((max_prefill_ + c.max_frames + 1 + 31) / 32) * 32;
+        max_tp_ = 3 + B * (c.max_text + c.max_instruct + max_ref_text_);
         std::vector<float> rc, rs;
         rope_tables(c.rope_theta, half, max_ctx_, rc, rs);
         d_rope_cos_ = (float*)dev_upload(rc.data(), rc.size() * 4);
@@ -670,6 +708,23 @@ TtsTalker::TtsTalker(const qasr_tts_config& cfg, const SafeTensorsDir& st) : cfg
         d_row_index_ = (long long*)dev_upload(nullptr, (size_t)B * 8);
         d_seen_ = (unsigned char*)dev_upload(nullptr, (size_t)B * c.codec_vocab);
         d_knobs_ = (Knobs*)dev_upload(nullptr, sizeof(Knobs));
+        if (icl) {
+            const int nq = c.heads * c.head_dim, nkv = c.kv_heads * c.head_dim, I = c.inter;
+            d_ref_codes_ = (int*)dev_upload(nullptr, (size_t)B * TTS_GROUPS * max_ref_frames_ * 4);
+            max_pos_ = B * (max_prefill_ - 1);
+            vt_stride_ = (max_prefill_ + 63) / 64 * 64;
+            d_w_ = (bf16_t*)dev_upload(nullptr, ((size_t)(nq + 2 * nkv) * H + (size_t)H * nq + (size_t)2 * I * H + (size_t)H * I) * 2);
+            const size_t vt_bytes = (size_t)B * c.kv_heads * c.head_dim * vt_stride_ * 2;
+            d_vt_ = (bf16_t*)dev_upload(nullptr, vt_bytes);
+            QASR_HIP(hipMemsetAsync(d_vt_, 0, vt_bytes, stream_));          // masked keys multiply stale bytes by P = 0
+            d_px_ = (bf16_t*)dev_upload(nullptr, (size_t)max_pos_ * H * 2);
+            d_ph_ = (bf16_t*)dev_upload(nullptr, (size_t)max_pos_ * H * 2);
+            d_pqkv_ = (bf16_t*)dev_upload(nullptr, (size_t)max_pos_ * (nq + 2 * nkv) * 2);
+            d_pqr_ = (bf16_t*)dev_upload(nullptr, (size_t)max_pos_ * nq * 2);
+            d_pattn_ = (bf16_t*)dev_upload(nullptr, (size_t)max_pos_ * nq * 2);
+            d_pact_ = (bf16_t*)dev_upload(nullptr, (size_t)max_pos_ * I * 2);
+            d_pmeta_ = (int*)dev_upload(nullptr, ((size_t)2 * max_pos_ + 2 * B + 1) * 4);
+        }
         QASR_HIP(hipStreamSynchronize(stream_));
     } catch (...) {
         bufs_.clear();
@@ -795,13 +850,18 @@ void TtsTalker::run_frame(int B) {
 }
 
 // buildPrefillEmbeddings (Qwen3TTS.swift:1313-1390) for every row, then the prompt positions but the last through the Talker's layers.
-void TtsTalker::prefill(const std::vector<TtsRow>& rows) {
+void TtsTalker::prefill(const std::vector<TtsRow>& rows, bool build_only) {
     const auto& c = cfg_;
     const int B = (int)rows.size(), MB = c.max_batch, H = c.hidden, P = max_prefill_, half = c.head_dim / 2;
     std::vector<int> tp_ids = {c.tts_pad, c.tts_bos, c.tts_eos};          // rows 0 1 2 of the projected text table
     std::vector<int> pf_text((size_t)B * P, -1), pf_codec((size_t)B * P, -1), trail((size_t)B * c.max_text, 0), state((size_t)6 * MB, 0);
     std::vector<float> xv((size_t)B * H, 0.0f);
     std::vector<long long> ridx(MB, 0);
+    std::vector<int> ref;
+    bool icl = false;
+    for (const TtsRow& r : rows) icl = icl || r.ref_codes;
+    if (icl) ref.assign((size_t)B * TTS_GROUPS * max_ref_frames_, 0);
+    pf_len_.assign(B, 0);
     int Pmax = 0;
     for (int b = 0; b < B; ++b) {
         const TtsRow& r = rows[b];
@@ -819,11 +879,24 @@ void TtsTalker::prefill(const std::vector<TtsRow>& rows) {
         codec.push_back(c.codec_bos);
         const int L = (int)codec.size();
         for (int i = 0; i < L - 1; ++i) { pt[n] = i < L - 2 ? 0 : 1; pc[n++] = codec[i]; }        // tts_pad ... tts_bos over the prefix
-        pt[n] = text_row(r.text[3]); pc[n++] = codec[L - 1];                                       // first text + codec_bos
         int nt = 0;
-        int* tr = &trail[(size_t)b * c.max_text];
-        for (int i = 4; i < r.n_text - 5; ++i) tr[nt++] = text_row(r.text[i]);
-        tr[nt++] = 2;                                                                              // tts_eos
+        if (r.ref_codes) {
+            // buildICLPrefillEmbeddings (Qwen3TTS+ICL.swift:158-242): the prefix's own codec_bos is dropped; every text id over codec_pad,
+            // tts_eos over codec_pad, tts_pad over codec_bos, tts_pad over every reference frame; no trailing text
+            for (int i = 0; i < r.n_ref_text; ++i) { pt[n] = text_row(r.ref_text[i]); pc[n++] = c.codec_pad; }
+            for (int i = 3; i < r.n_text - 5; ++i) { pt[n] = text_row(r.text[i]); pc[n++] = c.codec_pad; }
+            pt[n] = 2; pc[n++] = c.codec_pad;
+            pt[n] = 0; pc[n++] = c.codec_bos;
+            for (int f = 0; f < r.ref_frames; ++f) { pt[n] = 0; pc[n++] = -3 - f; }
+            for (int g = 0; g < TTS_GROUPS; ++g)
+                std::memcpy(&ref[((size_t)b * TTS_GROUPS + g) * max_ref_frames_], r.ref_codes + (size_t)g * r.ref_frames, (size_t)r.ref_frames * 4);
+        } else {
+            pt[n] = text_row(r.text[3]); pc[n++] = codec[L - 1];                                   // first text + codec_bos
+            int* tr = &trail[(size_t)b * c.max_text];
+            for (int i = 4; i < r.n_text - 5; ++i) tr[nt++] = text_row(r.text[i]);
+            tr[nt++] = 2;                                                                          // tts_eos
+        }
+        pf_len_[b] = n;
         int* s = state.data();
         s[4 * MB + b] = nt;
         s[5 * MB + b] = n;
@@ -837,6 +910,7 @@ void TtsTalker::prefill(const std::vector<TtsRow>& rows) {
     QASR_HIP(hipMemcpyAsync(d_trail_, trail.data(), trail.size() * 4, hipMemcpyHostToDevice, stream_));
     QASR_HIP(hipMemcpyAsync(d_state_, state.data(), state.size() * 4, hipMemcpyHostToDevice, stream_));
     QASR_HIP(hipMemcpyAsync(d_xvec_, xv.data(), xv.size() * 4, hipMemcpyHostToDevice, stream_));
+    if (icl) QASR_HIP(hipMemcpyAsync(d_ref_codes_, ref.data(), ref.size() * 4, hipMemcpyHostToDevice, stream_));
     QASR_HIP(hipMemcpyAsync(d_row_index_, ridx.data(), ridx.size() * 8, hipMemcpyHostToDevice, stream_));
     QASR_HIP(hipMemsetAsync(d_seen_, 0, (size_t)MB * c.codec_vocab, stream_));
     QASR_HIP(hipMemsetAsync(d_codes_, 0xff, (size_t)MB * TTS_GROUPS * c.max_frames * 4, stream_));
@@ -845,15 +919,85 @@ void TtsTalker::prefill(const std::vector<TtsRow>& rows) {
     gemv_rows(fc1_.img.raw, d_tp_in_, ntp, fc1_.bias, nullptr, d_tp_mid_, c.text_hidden, true, stream_);
     gemv_rows(fc2_.img.raw, d_tp_mid_, ntp, fc2_.bias, nullptr, d_tp_, H, false, stream_);
     hipLaunchKernelGGL(tts_prefill_build_kernel, dim3(P, B), dim3(256), 0, stream_, (const int*)d_pf_text_, (const int*)d_pf_codec_, P,
-                       (const bf16_t*)d_tp_, codec_emb_, (const float*)d_xvec_, H, d_pf_);
+                       (const bf16_t*)d_tp_, codec_emb_, (const float*)d_xvec_, H, d_pf_, (const int*)d_ref_codes_, max_ref_frames_,
+                       (const bf16_t* const*)d_cp_emb_);
     TtsState st = state_of(d_state_, MB);
-    for (int s = 0; s < Pmax; ++s) {
+    // ICL calls under tts_packed_prompt: every prompt position but the last of every row as one packed sequence, then the rows' state
+    const bool packed = icl && tuning().tts_packed_prompt != 0;
+    if (packed && !build_only) packed_prompt(B, Pmax);
+    for (int s = packed ? Pmax - 1 : 0; s < Pmax && !build_only; ++s) {
         hipLaunchKernelGGL(tts_prefill_feed_kernel, dim3(B), dim3(256), 0, stream_, st, s, Pmax, (const bf16_t*)d_pf_, P, H, d_x_,
                            (const float*)d_rope_cos_, (const float*)d_rope_sin_, d_rope_rows_, d_rope_rows_ + (size_t)MB * half, half);
         if (s + 1 < Pmax) layer_steps(tk_, d_x_, B, true, 0, false);      // the last position is the Talker step of frame 0
     }
     QASR_HIP(hipGetLastError());
     QASR_HIP(hipStreamSynchronize(stream_));                              // the host vectors above go out of scope
+}
+
+// The prompt pass of the ASR engine (Engine::run_prefill) on the Talker's layers: per layer one dequantisation of its four matrices to
+// bf16 (q|k|v and gate|up are kept fused by the loader, gate|up already in the 16-row interleave the SwiGLU GEMM reads), then the
+// engine's launch functions.  K rows and the V fragments land in the Talker's cache at slot = row, where the frame step reads them.
+void TtsTalker::packed_prompt(int B, int Pmax) {
+    const auto& c = cfg_;
+    const int H = c.hidden, hd = c.head_dim, nq = c.heads * hd, nkv = c.kv_heads * hd, nh = c.heads + 2 * c.kv_heads, I = c.inter;
+    const int MB = c.max_batch;
+    std::vector<int> meta((size_t)2 * max_pos_ + 2 * MB + 1, 0);
+    int *slot = meta.data(), *pos = slot + max_pos_, *cu = pos + max_pos_, *clip = cu + MB + 1;
+    int n = 0, max_len = 0;
+    for (int b = 0; b < B; ++b) {
+        cu[b] = n;
+        clip[b] = b;
+        for (int i = 0; i + 1 < pf_len_[b]; ++i) { slot[n] = b; pos[n++] = i; }
+        max_len = std::max(max_len, pf_len_[b] - 1);
+    }
+    cu[B] = n;
+    if (n == 0 || n > max_pos_ || max_len > vt_stride_ || Pmax > max_prefill_) throw std::length_error("talker: packed prompt over the handle's capacity");
+    QASR_HIP(hipMemcpyAsync(d_pmeta_, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, stream_));
+    const int *d_slot = d_pmeta_, *d_pos = d_pmeta_ + max_pos_, *d_cu = d_pmeta_ + 2 * (size_t)max_pos_, *d_clip = d_cu + MB + 1;
+    hipStream_t s = stream_;
+    hipLaunchKernelGGL(tts_pack_rows_kernel, dim3(n), dim3(128), 0, s, (const bf16_t*)d_pf_, max_prefill_, d_slot, d_pos, H, d_px_);
+    bf16_t *wqkv = d_w_, *wo = wqkv + (size_t)(nq + 2 * nkv) * H, *wgu = wo + (size_t)H * nq, *wdown = wgu + (size_t)2 * I * H;
+    const size_t per = (size_t)MB * c.kv_heads * max_ctx_ * hd;
+    for (size_t l = 0; l < tk_.layers.size(); ++l) {
+        const Layer& L = tk_.layers[l];
+        KVLayout kv{d_k_ + l * per, nullptr, max_ctx_, c.kv_heads, hd, d_vf_ + l * per};
+        const DequantJob jobs[4] = {{L.qkv.img.raw, 0, nq + 2 * nkv, wqkv}, {L.o.img.raw, 0, H, wo}, {L.gu.img.raw, 0, 2 * I, wgu},
+                                    {L.down.img.raw, 0, H, wdown}};
+        quant_dequant_multi_launch(jobs, 4, s);
+        rmsnorm_rows_launch(d_px_, L.ln1, d_ph_, n, H, c.rms_eps, s);
+        const bool fuse_qk = qk_norm_rope_fusable(c.heads, c.kv_heads, hd);
+        if (fuse_qk)
+            gemm_nt_headtiles(ADense{d_ph_, H, n, H}, wqkv, H, n, nh * hd, H,
+                              EpiQkHeads{d_pqkv_, (long)nh * hd, d_pqr_, kv, d_slot, d_pos, L.qn, L.kn, c.rms_eps, d_rope_cos_, d_rope_sin_,
+                                         c.heads, c.kv_heads}, s);
+        else
+            gemm_nt(ADense{d_ph_, H, n, H}, wqkv, H, n, nh * hd, H, EpiStoreBf16{d_pqkv_, (long)nh * hd}, s);
+        qk_norm_rope_launch(d_pqkv_, d_slot, d_pos, n, c.heads, c.kv_heads, hd, L.qn, L.kn, c.rms_eps, d_rope_cos_, d_rope_sin_, d_pqr_, kv,
+                            d_vt_, vt_stride_, d_cu, d_clip, B, max_len, s, fuse_qk);
+        prefill_attention_launch(d_pqr_, kv, d_vt_, vt_stride_, d_cu, d_clip, B, max_len, c.heads, d_pattn_, s);
+        gemm_nt(ADense{d_pattn_, nq, n, nq}, wo, nq, n, H, nq, EpiResidBf16{d_px_, H}, s);
+        rmsnorm_rows_launch(d_px_, L.ln2, d_ph_, n, H, c.rms_eps, s);
+        gemm_nt_swiglu(ADense{d_ph_, H, n, H}, wgu, H, n, 2 * I, H, EpiStoreBf16{d_pact_, I}, s);
+        gemm_nt(ADense{d_pact_, I, n, I}, wdown, I, n, H, I, EpiResidBf16{d_px_, H}, s);
+    }
+    QASR_HIP(hipGetLastError());
+    QASR_HIP(hipStreamSynchronize(s));                                     // `meta` goes out of scope
+}
+
+void TtsTalker::icl_prompt(const std::vector<TtsRow>& rows, float* out, int32_t* P) {
+    const int B = (int)rows.size(), H = cfg_.hidden;
+    if (B == 0) return;
+    QASR_HIP(hipSetDevice(cfg_.device));
+    prefill(rows, true);
+    int Pmax = 0;
+    for (int b = 0; b < B; ++b) { P[b] = pf_len_[b]; Pmax = std::max(Pmax, pf_len_[b]); }
+    std::vector<bf16_t> h((size_t)B * max_prefill_ * H);
+    QASR_HIP(hipMemcpyAsync(h.data(), d_pf_, h.size() * 2, hipMemcpyDeviceToHost, stream_));
+    QASR_HIP(hipStreamSynchronize(stream_));
+    for (int b = 0; b < B; ++b)
+        for (int p = 0; p < Pmax; ++p)
+            for (int i = 0; i < H; ++i)
+                out[((size_t)b * Pmax + p) * H + i] = p < pf_len_[b] ? bf16_to_f32_host(h[((size_t)b * max_prefill_ + p) * H + i]) : 0.0f;
 }
 
 void TtsTalker::set_knobs(const qasr_tts_sampling& s, unsigned long long seed) {

@@ -89,6 +89,11 @@ class QasrTtsRequest(C.Structure):
                 ("instruct_len", C.POINTER(C.c_int32)), ("row_index", C.POINTER(C.c_int64))]
 
 
+class QasrTtsIcl(C.Structure):
+    _fields_ = [("ref_text", C.POINTER(C.POINTER(C.c_int32))), ("ref_text_len", C.POINTER(C.c_int32)),
+                ("ref_codes", C.POINTER(C.POINTER(C.c_int32))), ("ref_frames", C.POINTER(C.c_int32))]
+
+
 SC_TRANSCRIBE_FN = C.CFUNCTYPE(ScTranscriptionResult, C.c_void_p, C.POINTER(C.c_float), C.c_size_t, C.c_int)
 SC_RATE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p)
 
@@ -371,6 +376,15 @@ SIGNATURES = {
     "qasr_tts_sample_host": (C.c_int, [_P(QasrTtsConfig), _F, C.c_int32, C.c_int, _P(QasrTtsSampling), _I, C.c_int32, C.c_uint64,
                                        C.c_int64, C.c_int32, C.c_int32]),
     "qasr_tts_synthesize": (C.c_int, [_E, _E, _P(QasrTtsRequest), _P(QasrTtsSampling), C.c_uint64, _P(_F), _P(C.c_size_t), _I, _I]),
+    "qasr_tts_create_icl": (C.c_int, [C.c_char_p, _P(QasrTtsConfig), C.c_int32, C.c_int32, _P(_E)]),
+    "qasr_tts_icl_capacity": (C.c_int, [_E, _I, _I]),
+    "qasr_tts_generate_icl": (C.c_int, [_E, _P(QasrTtsRequest), _P(QasrTtsIcl), _P(QasrTtsSampling), C.c_uint64, _I, _I]),
+    "qasr_tts_forced_icl": (C.c_int, [_E, _P(QasrTtsRequest), _P(QasrTtsIcl), _I, C.c_size_t, _F, _F, _F]),
+    "qasr_tts_synthesize_icl": (C.c_int, [_E, _E, _P(QasrTtsRequest), _P(QasrTtsIcl), _P(QasrTtsSampling), C.c_uint64, _P(_F),
+                                          _P(C.c_size_t), _I, _I]),
+    "qasr_tts_icl_prompt": (C.c_int, [_E, _P(QasrTtsRequest), _P(QasrTtsIcl), _F, _I]),
+    "qasr_tts_clone": (C.c_int, [_E, _E, _E, _E, _P(QasrTtsRequest), _P(_I), _I, _P(_F), _P(C.c_size_t), _P(QasrTtsSampling), C.c_uint64,
+                                 _P(_F), _P(C.c_size_t), _I, _I]),
     "qasr_transducer_default_config": (C.c_int, [C.c_char_p, _P(QasrTransducerConfig)]),
     "qasr_tdt_greedy_decode": (C.c_int, [_P(QasrTransducerConfig), _P(QasrTransducerCallbacks), C.c_int32, _I, _F, C.c_int32, _F]),
     "qasr_rnnt_greedy_decode": (C.c_int, [_P(QasrTransducerConfig), _P(QasrTransducerCallbacks), C.c_int32, C.c_int32, _I, _F, C.c_int32, _I]),

@@ -1,7 +1,7 @@
 """The Qwen3-TTS Talker + code predictor on the GPU over the C ABI (include/qasr.h, qasr_tts_*).
 
 Reference: Sources/Qwen3TTS/Qwen3TTS.swift (Qwen3TTSModel.synthesize, synthesizeBatch, synthesizeWithVoiceClone in x-vector mode),
-Talker.swift, CodePredictor.swift, Sampling.swift, Configuration.swift.  Text -> ids stays with the caller: the wrapper builds the chat
+Qwen3TTS+ICL.swift (synthesizeWithVoiceCloneICL), Talker.swift, CodePredictor.swift, Sampling.swift, Configuration.swift.  Text -> ids stays with the caller: the wrapper builds the chat
 template of prepareTextTokens / prepareInstructTokens around ids it is given.  Codes are int32 [16, n_frames] per row at 12.5 Hz; with a
 SpeechTokenizerDecoder (qasr.codec) they become 24 kHz float32 audio.  No CPU fallback.
 """
@@ -131,6 +131,25 @@ class _Request:
         self.rq = rq
 
 
+class _Icl:
+    """The C ICL side of a batch (qasr_tts_icl); keeps the arrays it points to alive."""
+
+    def __init__(self, ref_texts, ref_codes):
+        B = len(ref_codes)
+        if len(ref_texts) != B:
+            raise QasrError("qasr error 1: one reference text per row")
+        self.text = [np.ascontiguousarray([] if t is None else t, dtype=np.int32).reshape(-1) for t in ref_texts]
+        self.codes = [np.ascontiguousarray(c, dtype=np.int32) for c in ref_codes]
+        for c in self.codes:
+            if c.ndim != 2 or c.shape[0] != NUM_CODE_GROUPS:
+                raise QasrError("qasr error 1: reference codes are [16, frames] per row")
+        self.tp = (_I * B)(*[a.ctypes.data_as(_I) for a in self.text])
+        self.tl = (C.c_int32 * B)(*[a.size for a in self.text])
+        self.cp = (_I * B)(*[a.ctypes.data_as(_I) for a in self.codes])
+        self.cf = (C.c_int32 * B)(*[a.shape[1] for a in self.codes])
+        self.icl = _lib.QasrTtsIcl(self.tp, self.tl, self.cp, self.cf)
+
+
 class Qwen3TTSModel:
     """Qwen3TTSModel on the device: ids in, codes (and with a codec, audio) out."""
 
@@ -138,15 +157,19 @@ class Qwen3TTSModel:
         self.lib, self.h, self.cfg = _lib.load(strict=True), handle, cfg
 
     @classmethod
-    def from_pretrained(cls, model_dir, cfg=None, **over):
+    def from_pretrained(cls, model_dir, cfg=None, max_ref_frames=None, max_ref_text=None, **over):
         """model_dir: the main model directory (talker.* keys in any *.safetensors file).  cfg: a qasr_tts_config (default_config());
-        keyword arguments replace fields of it (max_batch, max_frames, max_text, max_instruct, device, ...)."""
+        keyword arguments replace fields of it (max_batch, max_frames, max_text, max_instruct, device, ...).  max_ref_frames (and
+        max_ref_text, default 0): an ICL handle (qasr_tts_create_icl) that holds reference clips of that many frames and transcript ids."""
         lib = _lib.load(strict=True)
         cfg = cfg if cfg is not None else default_config()
         for k, v in over.items():
             setattr(cfg, k, v)
         h = C.c_void_p()
-        rc = lib.qasr_tts_create(str(model_dir).encode(), C.byref(cfg), C.byref(h))
+        if max_ref_frames is None and max_ref_text is None:
+            rc = lib.qasr_tts_create(str(model_dir).encode(), C.byref(cfg), C.byref(h))
+        else:
+            rc = lib.qasr_tts_create_icl(str(model_dir).encode(), C.byref(cfg), int(max_ref_frames or 0), int(max_ref_text or 0), C.byref(h))
         if rc != 0:
             raise QasrError(f"qasr error {rc}: {lib.qasr_tts_last_error(None).decode()}")
         return cls(h, cfg)
@@ -208,6 +231,109 @@ class Qwen3TTSModel:
         ptr = lambda k: out[k].ctypes.data_as(_F) if k in out else None
         self._check(self.lib.qasr_tts_forced(self.h, C.byref(rq.rq), c.ctypes.data_as(_I), T, ptr("talker"), ptr("cp"), ptr("hidden")))
         return out
+
+    # ---- ICL voice cloning (Qwen3TTS+ICL.swift) ----
+    @property
+    def icl_capacity(self):
+        """(max_ref_frames, max_ref_text) of the handle; (0, 0) on a plain one."""
+        f, t = C.c_int32(), C.c_int32()
+        self._check(self.lib.qasr_tts_icl_capacity(self.h, C.byref(f), C.byref(t)))
+        return int(f.value), int(t.value)
+
+    def generate_codes_icl(self, texts, languages, xvectors, ref_texts, ref_codes, sampling: Optional[SamplingConfig] = None, seed: int = 0,
+                           row_index=None, speakers=None, instructs=None) -> List[np.ndarray]:
+        """generate_codes with the ICL prompt: ref_texts = tokenizer.encode(referenceText) per row (no template), ref_codes int32
+        [16, frames] per row (qasr.codec SpeechTokenizerEncoder.encode), xvectors [hidden] per row."""
+        rq = self._request(texts, languages, speakers, xvectors, instructs, row_index)
+        icl = _Icl(ref_texts, ref_codes)
+        s = (sampling or SamplingConfig()).c_struct()
+        B, F = len(texts), self.cfg.max_frames
+        codes = np.zeros((B, NUM_CODE_GROUPS, F), dtype=np.int32)
+        n = np.zeros(B, dtype=np.int32)
+        self._check(self.lib.qasr_tts_generate_icl(self.h, C.byref(rq.rq), C.byref(icl.icl), C.byref(s), int(seed), codes.ctypes.data_as(_I),
+                                                   n.ctypes.data_as(_I)))
+        return [codes[b, :, :int(n[b])].copy() for b in range(B)]
+
+    def forced_icl(self, texts, languages, xvectors, ref_texts, ref_codes, codes, want=("talker", "cp", "hidden")):
+        """forced with the ICL prompt."""
+        rq = self._request(texts, languages, None, xvectors, None, None)
+        icl = _Icl(ref_texts, ref_codes)
+        c = np.ascontiguousarray(codes, dtype=np.int32)
+        B, G, T = c.shape
+        if B != len(texts) or G != NUM_CODE_GROUPS:
+            raise QasrError("qasr error 1: forced codes are [B, 16, T]")
+        out = {}
+        if "talker" in want:
+            out["talker"] = np.zeros((B, T, self.cfg.codec_vocab), dtype=np.float32)
+        if "cp" in want:
+            out["cp"] = np.zeros((B, T, NUM_CODE_GROUPS - 1, self.cfg.cp_vocab), dtype=np.float32)
+        if "hidden" in want:
+            out["hidden"] = np.zeros((B, T, self.cfg.hidden), dtype=np.float32)
+        ptr = lambda k: out[k].ctypes.data_as(_F) if k in out else None
+        self._check(self.lib.qasr_tts_forced_icl(self.h, C.byref(rq.rq), C.byref(icl.icl), c.ctypes.data_as(_I), T, ptr("talker"), ptr("cp"),
+                                                 ptr("hidden")))
+        return out
+
+    def icl_prompt(self, texts, languages, xvectors, ref_texts, ref_codes) -> List[np.ndarray]:
+        """The ICL prompt rows as the Talker reads them: float32 [P, hidden] per row (bf16 values)."""
+        rq = self._request(texts, languages, None, xvectors, None, None)
+        icl = _Icl(ref_texts, ref_codes)
+        B = len(texts)
+        pmax = max(11 + icl.text[b].size + max(len(texts[b]) - 8, 0) + icl.codes[b].shape[1] for b in range(B)) if B else 0
+        rows = np.zeros((B, pmax, self.cfg.hidden), dtype=np.float32)
+        P = np.zeros(B, dtype=np.int32)
+        self._check(self.lib.qasr_tts_icl_prompt(self.h, C.byref(rq.rq), C.byref(icl.icl), rows.ctypes.data_as(_F), P.ctypes.data_as(_I)))
+        return [rows[b, :int(P[b])].copy() for b in range(B)]
+
+    def synthesize_batch_icl(self, codec, texts, languages, xvectors, ref_texts, ref_codes, sampling: Optional[SamplingConfig] = None,
+                             seed: int = 0, row_index=None, return_codes=False):
+        """qasr_tts_synthesize_icl: the ICL codes, then `codec` -> float32 [1920 * n_frames] per row."""
+        rq = self._request(texts, languages, None, xvectors, None, row_index)
+        icl = _Icl(ref_texts, ref_codes)
+        s = (sampling or SamplingConfig()).c_struct()
+        B, F = len(texts), self.cfg.max_frames
+        pcm = [np.zeros(1920 * F, dtype=np.float32) for _ in range(B)]
+        pp = (_F * B)(*[a.ctypes.data_as(_F) for a in pcm])
+        ns = (C.c_size_t * B)()
+        codes = np.zeros((B, NUM_CODE_GROUPS, F), dtype=np.int32)
+        n = np.zeros(B, dtype=np.int32)
+        self._check(self.lib.qasr_tts_synthesize_icl(self.h, getattr(codec, "h", codec), C.byref(rq.rq), C.byref(icl.icl), C.byref(s), int(seed),
+                                                     pp, ns, codes.ctypes.data_as(_I), n.ctypes.data_as(_I)))
+        audio = [pcm[b][:int(ns[b])].copy() for b in range(B)]
+        return (audio, [codes[b, :, :int(n[b])].copy() for b in range(B)]) if return_codes else audio
+
+    def clone_batch(self, codec, codec_encoder, speaker_encoder, texts, languages, reference_pcms, ref_texts,
+                    sampling: Optional[SamplingConfig] = None, seed: int = 0, row_index=None, return_codes=False):
+        """qasr_tts_clone: 24 kHz reference clips -> codes and x-vectors -> the ICL call -> audio, for B rows."""
+        rq = self._request(texts, languages, None, None, None, row_index)
+        B, F = len(texts), self.cfg.max_frames
+        if len(reference_pcms) != B or len(ref_texts) != B:
+            raise QasrError("qasr error 1: one reference clip and one reference text per row")
+        clips = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1) for p in reference_pcms]
+        rt = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1) for t in ref_texts]
+        cp = (_F * B)(*[a.ctypes.data_as(_F) for a in clips])
+        cn = (C.c_size_t * B)(*[a.size for a in clips])
+        tp = (_I * B)(*[a.ctypes.data_as(_I) for a in rt])
+        tl = (C.c_int32 * B)(*[a.size for a in rt])
+        s = (sampling or SamplingConfig()).c_struct()
+        pcm = [np.zeros(1920 * F, dtype=np.float32) for _ in range(B)]
+        pp = (_F * B)(*[a.ctypes.data_as(_F) for a in pcm])
+        ns = (C.c_size_t * B)()
+        codes = np.zeros((B, NUM_CODE_GROUPS, F), dtype=np.int32)
+        n = np.zeros(B, dtype=np.int32)
+        self._check(self.lib.qasr_tts_clone(self.h, getattr(codec_encoder, "h", codec_encoder), getattr(speaker_encoder, "h", speaker_encoder),
+                                            getattr(codec, "h", codec), C.byref(rq.rq), tp, tl, cp, cn, C.byref(s), int(seed), pp, ns,
+                                            codes.ctypes.data_as(_I), n.ctypes.data_as(_I)))
+        audio = [pcm[b][:int(ns[b])].copy() for b in range(B)]
+        return (audio, [codes[b, :, :int(n[b])].copy() for b in range(B)]) if return_codes else audio
+
+    def synthesize_with_voice_clone_icl(self, codec, codec_encoder, speaker_encoder, text_ids, language, reference_pcm, reference_text_ids,
+                                        sampling: Optional[SamplingConfig] = None, seed: int = 0):
+        """synthesizeWithVoiceCloneICL: text_ids / reference_text_ids are plain tokenizer ids (the template is added here), language a
+        name, a two-letter code or a codec id (an unknown name falls back to english, as the reference does), reference_pcm 24 kHz mono."""
+        lang = language if isinstance(language, (int, np.integer)) else (CodecTokens.language_id(language) or CodecTokens.languages["english"])
+        return self.clone_batch(codec, codec_encoder, speaker_encoder, [prepare_text_tokens(text_ids)], [int(lang)], [reference_pcm],
+                                [reference_text_ids], sampling, seed)[0]
 
     # ---- audio ----
     def synthesize_batch(self, codec, texts, languages, sampling: Optional[SamplingConfig] = None, seed: int = 0, speakers=None,
