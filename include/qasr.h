@@ -760,7 +760,8 @@ int qasr_sep_istft(qasr_sep* s, const float* re, const float* im, int n_spectra,
  * Codes are int32, one utterance [num_quantizers][T] with quantizer 0 the semantic stream.  Precision: f32 throughout, as the reference.
  * The chunking is part of the result (windows of 25 frames after 10 frames of context, one pass up to 35 frames).  A window's samples are
  * bit-identical alone, in any batch and place, under any max_windows, and run to run.  One object, one thread
- * at a time.  Not covered: the tokenizer's encoder, the Talker, the code predictor, bf16 or quantised forms, streaming decode. */
+ * at a time.  Not covered: the tokenizer's encoder, the Talker, the code predictor, bf16 or quantised forms.  Streamed chunks (qasr_tts_pool_step) are
+ * windows decoded for their tail: qasr_codec_forward_tail. */
 typedef struct qasr_codec qasr_codec;
 /* model_dir holds model.safetensors with the decoder.* keys in the PyTorch layouts (conv [out][in][k], transposed conv [in][out][k]); a
  * codebook is read from `..._codebook.embed`, else from embedding_sum / max(cluster_usage, 1e-7) (TTSWeightLoading.swift:280-301).  The
@@ -789,6 +790,15 @@ int qasr_codec_latent_dim(const qasr_codec* c);                     /* 1024: row
 int qasr_codec_forward(qasr_codec* c, const int32_t* codes, size_t B, size_t T, int clip, float* out);
 /* chunkedDecode's windows for T frames (:696-733): window i decodes frames starts[i] .. ends[i] and drops its first context[i] frames.
  * Returns the window count or -status (-QASR_ERR_CAPACITY when it exceeds cap; nothing is written then).  Pure CPU. */
+/* a window decoded for its tail: out [B][(T - context) x 1920], bit-identical to the last (T - context) x 1920 samples of each row of
+ * qasr_codec_forward; 0 <= context < T <= 35, else QASR_ERR_INVALID.  From decoder.decoder.0 on, no launch of the vocoder does work before
+ * the first row of a window that a kept sample depends on (qasr_codec_tail_leads; at T 35 / context 10 that skips 27 % of the vocoder's
+ * rows), and only the kept samples are copied back.  Tuning knob codec_tail_rows: 1 skips, 0 runs whole windows; the same bits.
+ * qasr_codec_forward, _decode and _decode_batch always run whole windows. */
+int qasr_codec_forward_tail(qasr_codec* c, const int32_t* codes, size_t B, size_t T, size_t context, int clip, float* out);
+/* pure CPU: input rows before the first kept one that each stage of the vocoder needs, from the geometry: leads[0] decoder.decoder.0 and
+ * leads[1..4] blocks 1..4 (each at its input's rate), leads[5] the output conv.  upsample_rates 8 5 4 3 -> 20 14 23 28 29 6. */
+int qasr_codec_tail_leads(const int32_t upsample_rates[4], int32_t leads[6]);
 int64_t qasr_codec_window_positions(size_t T, int32_t* starts, int32_t* context, int32_t* ends, size_t cap);
 /* decode(codes:) (:739-744): codes [Q][T], any T >= 1 -> out [samples_per_frame T], chunked as above */
 int qasr_codec_decode(qasr_codec* c, const int32_t* codes, size_t T, float* out);
@@ -901,7 +911,8 @@ int qasr_xvec_timing(const qasr_xvec* x, float* ms);
  * kv_heads x head_dim x 2 bytes x positions per row: 28 x 8 x 128 x 2 x 2 = 114,688 bytes per position; positions = max_instruct + 11
  * prompt + max_frames + 1, rounded up to 32 (544 by default; the 510 a row can reach are 3.8 GB of it at max_batch 64, the allocation 4.0 GB).
  * ICL voice cloning (Qwen3TTS+ICL.swift: synthesizeWithVoiceCloneICL) is qasr_tts_*_icl / qasr_tts_clone below, on a handle from
- * qasr_tts_create_icl.  Not covered: streaming, top_p < 1, the text tokenizer, host resampling, ReferenceAudioCache. */
+ * qasr_tts_create_icl; streaming synthesis (synthesizeStream) is the stream pool qasr_tts_pool_* further below.  Not covered: top_p < 1,
+ * the text tokenizer, host resampling, ReferenceAudioCache. */
 typedef struct qasr_tts qasr_tts;
 typedef struct qasr_tts_config {
     int32_t hidden, layers, heads, kv_heads, head_dim, inter;          /* Talker: 1024 28 16 8 128 3072 (1.7B: 2048 .. 6144) */
@@ -1001,6 +1012,55 @@ int qasr_tts_icl_prompt(qasr_tts* t, const qasr_tts_request* rq, const qasr_tts_
 int qasr_tts_clone(qasr_tts* t, qasr_codec_enc* codec_enc, qasr_xvec* xvec, qasr_codec* codec, const qasr_tts_request* rq,
                    const int32_t* const* ref_text, const int32_t* ref_text_len, const float* const* ref_pcm, const size_t* ref_n,
                    const qasr_tts_sampling* s, uint64_t seed, float* const* pcm, size_t* n_samples, int32_t* codes, int32_t* n_frames);
+
+/* ---- streaming synthesis: a pool of concurrent streams (Qwen3TTS.swift:297-608 synthesizeStream, runStreamingGeneration,
+ * decodeAndEmitChunk) -------------------------------------------------------------------------------------------
+ * A pool borrows a Talker handle and a codec handle and holds up to max_batch streams, one per batch row (slot) of the frame step.  A
+ * stream joins at any frame and leaves at any frame without changing a bit of any other: its codes equal qasr_tts_generate of the same
+ * request (B = 1, the pool's sampling and seed, rq->row_index[0] keying its random numbers), its chunks are those qasr_tts_stream_chunks
+ * names, and a chunk's samples are the last 1920 x n_frames samples of qasr_codec_forward (clip = 1) on the frames
+ * max(frame_index - decoder_left_context, 0) .. frame_index + n_frames, all-zero frames prepended while they are fewer than 4.
+ * Chunk boundaries: a chunk when the stream's frame count reaches first_chunk_frames, then every chunk_frames; at EOS the remaining frames
+ * as the final chunk, or a final chunk without samples when nothing remains (EOS as the first token: one empty final chunk at frame 0);
+ * a stream that stops at max_tokens (capped by max_frames) ends with its last chunk marked final, no empty chunk behind it.  (The
+ * reference's loop agrees but for max_tokens = 1 with first_chunk_frames = 1, where it sends that frame as a non-final chunk and an empty
+ * final one behind it.)
+ * While a pool exists on a Talker handle, qasr_tts_generate / _forced / _synthesize, the ICL calls and a second qasr_tts_pool_create on it
+ * return QASR_ERR_INVALID: the pool owns the handle's rows.  After qasr_tts_pool_destroy they work as before.  Destroy the pool before
+ * the handles it borrows.  One thread at a time for the pool and both handles.
+ * Not covered: ICL streams (no entry takes a qasr_tts_icl; plain streams run on an ICL handle too), the sc_tts_vtable_t bridge (it takes a text string; the text tokenizer stays with the
+ * caller), warmUp, a packed prompt pass for admission (a stream's prompt runs one position per step while the other streams wait), the
+ * noChunking preset (decoder_left_context + chunk_frames > 35: use qasr_tts_synthesize). */
+typedef struct qasr_tts_pool qasr_tts_pool;
+typedef struct qasr_tts_stream_config { int32_t first_chunk_frames, chunk_frames, decoder_left_context; } qasr_tts_stream_config; /* 3, 25, 10 */
+typedef struct qasr_tts_chunk {
+    int32_t stream, frame_index, n_frames, is_final;   /* AudioChunk: frameIndex, isFinal */
+    const float* samples; size_t n_samples;            /* 1920 x n_frames, pool-owned, valid until the next step / close / destroy */
+    const int32_t* codes;                              /* [16][n_frames] of this chunk, same lifetime */
+} qasr_tts_chunk;
+void qasr_tts_default_stream_config(int preset, qasr_tts_stream_config* out);   /* 0 default (3, 25, 10), 1 lowLatency (1, 15, 10) */
+/* top_p < 1 -> QASR_ERR_UNSUPPORTED; a handle that already has a pool, a NULL argument -> QASR_ERR_INVALID (message: qasr_tts_last_error(t)) */
+int qasr_tts_pool_create(qasr_tts* t, qasr_codec* codec, const qasr_tts_sampling* s, uint64_t seed, qasr_tts_pool** out);
+/* queues one stream (rq->B == 1; the request is copied) for the next step and names it in *stream: the slot index, 0 .. max_batch - 1,
+ * free again after the stream's final chunk or qasr_tts_pool_close.  first_chunk_frames < 1, chunk_frames < 1, decoder_left_context < 0,
+ * B != 1 -> QASR_ERR_INVALID; first_chunk_frames > 35, decoder_left_context + chunk_frames > 35 -> QASR_ERR_UNSUPPORTED;
+ * whatever qasr_tts_generate refuses -> its status; no free slot -> QASR_ERR_CAPACITY.  The pool stays usable. */
+int qasr_tts_pool_open(qasr_tts_pool* p, const qasr_tts_request* rq, const qasr_tts_stream_config* sc, int32_t* stream);
+/* admits the queued streams (one prompt pass each), runs frames for all live streams until a chunk is due -- never past the nearest
+ * boundary of any stream, reading counts and finished flags every qasr_tts_poll_interval() frames -- and decodes every due chunk in one
+ * codec call.  *n chunks are written (at most one per stream); *n == 0 only when no stream is live.  cap below the number of live
+ * streams -> QASR_ERR_CAPACITY before anything runs. */
+int qasr_tts_pool_step(qasr_tts_pool* p, qasr_tts_chunk* chunks, size_t cap, size_t* n);
+/* ms[3]: host time of the last step: admission | frames, with the polls and the code reads | the codec call */
+int qasr_tts_pool_timing(const qasr_tts_pool* p, float* ms);
+int qasr_tts_pool_close(qasr_tts_pool* p, int32_t stream);                       /* cancel (TTSBridge.cancel): the slot is free at once */
+int qasr_tts_pool_live(const qasr_tts_pool* p);                                 /* streams queued or running */
+void qasr_tts_pool_destroy(qasr_tts_pool* p);
+const char* qasr_tts_pool_last_error(const qasr_tts_pool* p);
+/* pure CPU: the chunks a stream of n_frames frames is cut into; ended_by_eos = 0: it stopped at max_tokens (then n_frames >= 1).  Writes
+ * frame_index / frames / is_final (any may be NULL) and returns the number of chunks, or -status (cap too small: -QASR_ERR_CAPACITY). */
+int64_t qasr_tts_stream_chunks(int32_t n_frames, int ended_by_eos, const qasr_tts_stream_config* sc,
+                               int32_t* frame_index, int32_t* frames, int32_t* is_final, size_t cap);
 
 /* transducer greedy loops (pure CPU).  The caller owns the networks and their state:
  *   decoder_step(ctx, token)  advance the prediction network with `token` (the loops prime it with the blank id where the reference does)

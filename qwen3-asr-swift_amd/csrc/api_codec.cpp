@@ -84,6 +84,18 @@ static int ready(qasr_codec* c) {
     return QASR_OK;
 }
 
+int qasr::codec_run_windows(qasr_codec* c, const std::vector<CodecWin>& wins, bool clip) {
+    if (int rc = ready(c)) return rc;
+    for (size_t i = 0; i < wins.size(); ++i) {
+        const CodecWin& w = wins[i];
+        if (!w.codes || !w.out || w.start != 0 || w.frames < 1 || w.frames > CODEC_MAX_T || w.ld != w.frames || w.context < 0 || w.context >= w.frames)
+            return fail(c, QASR_ERR_INVALID, std::string(WHO) + ": window " + std::to_string(i) + " is not 1..35 whole frames with a shorter context");
+        if (int rc = check_codes(c, w.codes, (size_t)w.frames, i)) return rc;
+    }
+    if (wins.empty()) return QASR_OK;
+    return guarded(c, [&] { c->impl->run(wins, clip, true); });
+}
+
 extern "C" {
 
 int qasr_codec_create(int device, const char* model_dir, int max_windows, qasr_engine* order_with, qasr_codec** out) {
@@ -155,6 +167,31 @@ int qasr_codec_forward(qasr_codec* c, const int32_t* codes, size_t B, size_t T, 
         wins.push_back({cb, (long)T, 0, (int)T, 0, out + b * spf * T});
     }
     return guarded(c, [&] { c->impl->run(wins, clip != 0); });
+}
+
+int qasr_codec_forward_tail(qasr_codec* c, const int32_t* codes, size_t B, size_t T, size_t context, int clip, float* out) {
+    if (int rc = ready(c)) return rc;
+    if (!codes || !out) return fail(c, QASR_ERR_INVALID, std::string(WHO) + ": null argument");
+    if (B == 0 || B > ((size_t)1 << 20)) return fail(c, QASR_ERR_INVALID, std::string(WHO) + ": 1..2^20 windows");
+    if (T == 0 || T > (size_t)CODEC_MAX_T || context >= T)
+        return fail(c, QASR_ERR_INVALID, std::string(WHO) + ": forward_tail takes 1..35 frames and a context shorter than the window");
+    const CodecGeom& g = c->impl->geom();
+    const size_t kept = (size_t)g.samples_per_frame() * (T - context);
+    std::vector<CodecWin> wins;
+    for (size_t b = 0; b < B; ++b) wins.push_back({codes + b * g.quantizers * T, (long)T, 0, (int)T, (int)context, out + b * kept});
+    return codec_run_windows(c, wins, clip != 0);
+}
+
+int qasr_codec_tail_leads(const int32_t upsample_rates[4], int32_t leads[6]) {
+    if (!upsample_rates || !leads) return QASR_ERR_INVALID;
+    int r[4], l[6];
+    for (int i = 0; i < 4; ++i) {
+        if (upsample_rates[i] < 1 || upsample_rates[i] > 64) return QASR_ERR_INVALID;
+        r[i] = upsample_rates[i];
+    }
+    codec_tail_leads(r, l);
+    for (int i = 0; i < 6; ++i) leads[i] = l[i];
+    return QASR_OK;
 }
 
 int qasr_codec_decode_batch(qasr_codec* c, const int32_t* const* codes, const size_t* T, size_t B, float* const* out) {

@@ -1,21 +1,48 @@
 // api_tts.cpp -- extern "C" boundary of the Qwen3-TTS Talker + code predictor (include/qasr.h, qasr_tts_*).  Exceptions never cross it.
 #include "api_guard.h"
+#include "codec_qwen3tts.h"
 #include "tts_talker.h"
+#include <chrono>
+#include <climits>
 #include <memory>
 
 struct qasr_tts {
     std::unique_ptr<qasr::TtsTalker> impl;
     mutable std::string last_error;
+    qasr_tts_pool* pool = nullptr;       // the stream pool that owns the handle's rows, if any
 };
 static std::string& error_slot(const qasr_tts* t) { return t ? t->last_error : create_error<qasr_tts>(); }
+
+// One stream of a pool = one batch row (slot) of the Talker.  frames: what the device has stored, emitted: what went out in chunks.
+struct TtsStream {
+    enum { FREE, QUEUED, RUNNING } state = FREE;
+    qasr_tts_stream_config sc{};
+    int frames = 0, emitted = 0, cap = 0;
+    qasr::TtsRow row{};                  // points into the copies below
+    std::vector<int32_t> text, instruct;
+    std::vector<float> xvector;
+};
+struct qasr_tts_pool {
+    qasr_tts* t = nullptr;
+    qasr_codec* codec = nullptr;
+    int max_tokens = 0;
+    std::vector<TtsStream> streams;      // [max_batch]
+    std::vector<float> pcm;              // the chunks of the last step
+    std::vector<int32_t> chunk_codes, window_codes;
+    float timing[3] = {0, 0, 0};         // host ms of the last step: admission, frames (with the polls and code reads), codec
+    mutable std::string last_error;
+};
+static std::string& error_slot(const qasr_tts_pool* p) { return p ? p->last_error : create_error<qasr_tts_pool>(); }
 
 using namespace qasr;
 
 static const std::string WHO = "talker";
 
 // the rows of one request, checked on the host before anything is uploaded
-static int check_request(qasr_tts* t, const qasr_tts_request* rq, std::vector<TtsRow>& rows) {
+static int check_request(qasr_tts* t, const qasr_tts_request* rq, std::vector<TtsRow>& rows, bool one_shot = true) {
     if (!t || !t->impl) return QASR_ERR_INVALID;
+    if (one_shot && t->pool)
+        return fail(t, QASR_ERR_INVALID, WHO + ": a stream pool owns this handle's rows (qasr_tts_pool_destroy it before a one-shot call)");
     const qasr_tts_config& c = t->impl->config();
     if (!rq) return fail(t, QASR_ERR_INVALID, WHO + ": null request");
     if (rq->B > (size_t)c.max_batch)
@@ -151,6 +178,128 @@ static int check_sampling(qasr_tts* t, const qasr_tts_sampling* s) {
     return QASR_OK;
 }
 
+
+// ---- the stream pool ------------------------------------------------------------------------------------------
+// the chunks of a stream, stated once: the pool cuts by next_boundary() and the final rules of stream_chunks()
+static int next_boundary(const qasr_tts_stream_config& sc, int emitted) { return emitted == 0 ? sc.first_chunk_frames : emitted + sc.chunk_frames; }
+
+struct ChunkSpan { int frame_index, frames, is_final; };
+static std::vector<ChunkSpan> stream_chunks(int n, bool eos, const qasr_tts_stream_config& sc) {
+    std::vector<ChunkSpan> out;
+    int emitted = 0;
+    // a boundary the stream reached and went on from; the one it stopped on at max_tokens is its final chunk
+    for (int b = next_boundary(sc, 0); b < n || (b == n && eos); b = next_boundary(sc, emitted)) {
+        out.push_back({emitted, b - emitted, 0});
+        emitted = b;
+    }
+    if (eos || n > emitted) out.push_back({emitted, n - emitted, 1});       // at EOS with nothing left: the empty final chunk
+    return out;
+}
+
+static int check_stream_config(qasr_tts_pool* p, const qasr_tts_stream_config* sc) {
+    if (!sc) return fail(p, QASR_ERR_INVALID, WHO + ": null stream config");
+    if (sc->first_chunk_frames < 1) return fail(p, QASR_ERR_INVALID, WHO + ": first_chunk_frames must be at least 1");
+    if (sc->chunk_frames < 1) return fail(p, QASR_ERR_INVALID, WHO + ": chunk_frames must be at least 1");
+    if (sc->decoder_left_context < 0) return fail(p, QASR_ERR_INVALID, WHO + ": decoder_left_context must not be negative");
+    if (sc->first_chunk_frames > CODEC_MAX_T)
+        return fail(p, QASR_ERR_UNSUPPORTED, WHO + ": first_chunk_frames over the codec's window of " + std::to_string(CODEC_MAX_T) + " frames");
+    if ((long)sc->decoder_left_context + sc->chunk_frames > CODEC_MAX_T)
+        return fail(p, QASR_ERR_UNSUPPORTED, WHO + ": decoder_left_context + chunk_frames over the codec's window of " + std::to_string(CODEC_MAX_T) +
+                                                 " frames (the noChunking preset: use qasr_tts_synthesize)");
+    return QASR_OK;
+}
+
+// one chunk of slot `slot`: its codes through the host, its window queued for the codec pass
+struct DueChunk { int slot, frame_index, frames, is_final; size_t codes_at, pcm_at, win_at; int win_frames; };
+
+static int pool_step(qasr_tts_pool* p, qasr_tts_chunk* chunks, size_t cap, size_t* n_out) {
+    TtsTalker& tk = *p->t->impl;
+    const int MB = (int)p->streams.size(), spf = qasr_codec_samples_per_frame();
+    if ((size_t)qasr_tts_pool_live(p) > cap)
+        return fail(p, QASR_ERR_CAPACITY, WHO + ": " + std::to_string(qasr_tts_pool_live(p)) + " live streams may each send a chunk, cap is " + std::to_string(cap));
+    std::vector<DueChunk> due;
+    std::vector<int> frames(MB), fin(MB);
+    using Clock = std::chrono::steady_clock;
+    auto ms_since = [](Clock::time_point t0) { return std::chrono::duration<float, std::milli>(Clock::now() - t0).count(); };
+    Clock::time_point t0 = Clock::now();
+    p->timing[0] = p->timing[1] = p->timing[2] = 0.0f;
+    int rc = guarded(p, [&] {
+        for (int b = 0; b < MB; ++b) {                                       // 1. admission
+            TtsStream& st = p->streams[b];
+            if (st.state != TtsStream::QUEUED) continue;
+            tk.pool_admit(b, st.row);
+            st.state = TtsStream::RUNNING;
+        }
+        p->timing[0] = ms_since(t0);
+        t0 = Clock::now();
+        while (due.empty()) {
+            int B = 0, run = INT_MAX;                                      // 2. 3. frames up to the nearest boundary of any stream
+            for (int b = 0; b < MB; ++b) {
+                const TtsStream& st = p->streams[b];
+                if (st.state != TtsStream::RUNNING) continue;
+                B = b + 1;
+                run = std::min(run, std::min(next_boundary(st.sc, st.emitted), st.cap) - st.frames);
+            }
+            if (B == 0) return;
+            bool stop = false;
+            for (int f = 0; f < run && !stop; f += TTS_POLL) {              // 4. the counts and flags every TTS_POLL frames
+                tk.pool_frames(B, std::min(TTS_POLL, run - f));
+                tk.pool_poll(B, frames.data(), fin.data());
+                for (int b = 0; b < B; ++b) stop = stop || (p->streams[b].state == TtsStream::RUNNING && fin[b]);
+            }
+            // a stream already on its boundary: the step before failed behind its frames (a codec or HIP error) and its chunk is still owed
+            if (run <= 0) tk.pool_poll(B, frames.data(), fin.data());
+            for (int b = 0; b < B; ++b) {
+                TtsStream& st = p->streams[b];
+                if (st.state != TtsStream::RUNNING) continue;
+                st.frames = frames[b];
+                const bool eos = fin[b] != 0, capped = !eos && st.frames >= st.cap;
+                if (!eos && !capped && st.frames < next_boundary(st.sc, st.emitted)) continue;
+                due.push_back({b, st.emitted, st.frames - st.emitted, eos || capped ? 1 : 0, 0, 0, 0, 0});
+                if (capped) tk.pool_finish(b);                                // before another frame runs
+            }
+        }
+        // 5. the codes of every due chunk and of its left context, [zero pad | context | chunk] per window
+        size_t n_codes = 0, n_pcm = 0, n_win = 0;
+        for (DueChunk& d : due) {
+            const int ctx = std::min(p->streams[d.slot].sc.decoder_left_context, d.frame_index);
+            d.win_frames = d.frames > 0 ? std::max(ctx + d.frames, 4) : 0;
+            d.codes_at = n_codes; d.pcm_at = n_pcm; d.win_at = n_win;
+            n_codes += (size_t)TTS_GROUPS * d.frames; n_pcm += (size_t)spf * d.frames; n_win += (size_t)TTS_GROUPS * d.win_frames;
+        }
+        p->chunk_codes.assign(n_codes, 0); p->pcm.assign(n_pcm, 0.0f); p->window_codes.assign(n_win, 0);
+        for (const DueChunk& d : due) {
+            if (d.frames == 0) continue;
+            const int real = std::min(p->streams[d.slot].sc.decoder_left_context, d.frame_index) + d.frames, W = d.win_frames;
+            std::vector<int32_t> got((size_t)TTS_GROUPS * real);
+            tk.pool_codes(d.slot, d.frame_index + d.frames - real, real, got.data());
+            for (int g = 0; g < TTS_GROUPS; ++g) {
+                std::copy_n(&got[(size_t)g * real], real, &p->window_codes[d.win_at + (size_t)g * W + (W - real)]);
+                std::copy_n(&got[(size_t)g * real + (real - d.frames)], d.frames, &p->chunk_codes[d.codes_at + (size_t)g * d.frames]);
+            }
+        }
+        p->timing[1] = ms_since(t0);
+    });
+    if (rc) return rc;
+    t0 = Clock::now();
+    std::vector<CodecWin> wins;
+    for (const DueChunk& d : due)
+        if (d.frames > 0)
+            wins.push_back({&p->window_codes[d.win_at], (long)d.win_frames, 0, d.win_frames, d.win_frames - d.frames, &p->pcm[d.pcm_at]});
+    if (int crc = codec_run_windows(p->codec, wins, true)) return fail(p, crc, WHO + ": codec: " + qasr_codec_last_error(p->codec));
+    p->timing[2] = ms_since(t0);
+    for (size_t i = 0; i < due.size(); ++i) {
+        const DueChunk& d = due[i];
+        chunks[i] = qasr_tts_chunk{d.slot, d.frame_index, d.frames, d.is_final, d.frames ? &p->pcm[d.pcm_at] : nullptr, (size_t)spf * d.frames,
+                                   d.frames ? &p->chunk_codes[d.codes_at] : nullptr};
+        TtsStream& st = p->streams[d.slot];
+        st.emitted += d.frames;
+        if (d.is_final) st = TtsStream{};                                    // the slot is free for the next open
+    }
+    *n_out = due.size();
+    return QASR_OK;
+}
+
 extern "C" {
 
 int qasr_tts_default_config(const char* model, int bits, qasr_tts_config* out) {
@@ -181,6 +330,103 @@ void qasr_tts_default_sampling(int greedy, qasr_tts_sampling* out) {
 }
 
 int qasr_tts_poll_interval(void) { return TTS_POLL; }
+
+void qasr_tts_default_stream_config(int preset, qasr_tts_stream_config* out) {
+    if (out) *out = preset == 1 ? qasr_tts_stream_config{1, 15, 10} : qasr_tts_stream_config{3, 25, 10};     // StreamingConfig.lowLatency | .default
+}
+
+int64_t qasr_tts_stream_chunks(int32_t n_frames, int ended_by_eos, const qasr_tts_stream_config* sc, int32_t* frame_index, int32_t* frames,
+                               int32_t* is_final, size_t cap) {
+    if (!sc || sc->first_chunk_frames < 1 || sc->chunk_frames < 1 || n_frames < 0 || (!ended_by_eos && n_frames < 1)) return -QASR_ERR_INVALID;
+    const auto spans = stream_chunks(n_frames, ended_by_eos != 0, *sc);
+    if (spans.size() > cap) return -QASR_ERR_CAPACITY;
+    for (size_t i = 0; i < spans.size(); ++i) {
+        if (frame_index) frame_index[i] = spans[i].frame_index;
+        if (frames) frames[i] = spans[i].frames;
+        if (is_final) is_final[i] = spans[i].is_final;
+    }
+    return (int64_t)spans.size();
+}
+
+int qasr_tts_pool_create(qasr_tts* t, qasr_codec* codec, const qasr_tts_sampling* s, uint64_t seed, qasr_tts_pool** out) {
+    if (!t || !t->impl) return QASR_ERR_INVALID;
+    if (!out) return fail(t, QASR_ERR_INVALID, WHO + ": null argument");
+    *out = nullptr;
+    if (!codec) return fail(t, QASR_ERR_INVALID, WHO + ": null argument");
+    if (t->pool) return fail(t, QASR_ERR_INVALID, WHO + ": the handle already has a stream pool");
+    if (int rc = check_sampling(t, s)) return rc;
+    if (int rc = guarded(t, [&] { t->impl->pool_begin(*s, seed); })) return rc;
+    qasr_tts_pool* p = new qasr_tts_pool();
+    p->t = t; p->codec = codec; p->max_tokens = s->max_tokens;
+    p->streams.resize(t->impl->config().max_batch);
+    t->pool = p;
+    *out = p;
+    return QASR_OK;
+}
+
+void qasr_tts_pool_destroy(qasr_tts_pool* p) {
+    if (!p) return;
+    for (size_t b = 0; b < p->streams.size(); ++b) (void)qasr_tts_pool_close(p, (int32_t)b);
+    p->t->pool = nullptr;
+    delete p;
+}
+
+const char* qasr_tts_pool_last_error(const qasr_tts_pool* p) { return error_slot(p).c_str(); }
+
+int qasr_tts_pool_live(const qasr_tts_pool* p) {
+    int n = 0;
+    if (p) for (const TtsStream& st : p->streams) n += st.state != TtsStream::FREE;
+    return n;
+}
+
+int qasr_tts_pool_open(qasr_tts_pool* p, const qasr_tts_request* rq, const qasr_tts_stream_config* sc, int32_t* stream) {
+    if (!p) return QASR_ERR_INVALID;
+    if (!stream) return fail(p, QASR_ERR_INVALID, WHO + ": null argument");
+    if (int rc = check_stream_config(p, sc)) return rc;
+    if (rq && rq->B != 1) return fail(p, QASR_ERR_INVALID, WHO + ": a stream is one row: B must be 1, got " + std::to_string(rq->B));
+    std::vector<TtsRow> rows;
+    if (int rc = check_request(p->t, rq, rows, false)) return fail(p, rc, qasr_tts_last_error(p->t));
+    size_t slot = 0;
+    while (slot < p->streams.size() && p->streams[slot].state != TtsStream::FREE) ++slot;
+    if (slot == p->streams.size())
+        return fail(p, QASR_ERR_CAPACITY, WHO + ": no free slot: all " + std::to_string(slot) + " streams (max_batch) are live");
+    const int H = p->t->impl->config().hidden, F = p->t->impl->config().max_frames;
+    TtsStream& st = p->streams[slot];
+    st = TtsStream{};
+    st.state = TtsStream::QUEUED;
+    st.sc = *sc;
+    st.cap = p->max_tokens > 0 && p->max_tokens < F ? p->max_tokens : F;
+    st.row = rows[0];
+    st.text.assign(st.row.text, st.row.text + st.row.n_text);
+    st.row.text = st.text.data();
+    if (st.row.n_instruct > 0) { st.instruct.assign(st.row.instruct, st.row.instruct + st.row.n_instruct); st.row.instruct = st.instruct.data(); }
+    if (st.row.xvector) { st.xvector.assign(st.row.xvector, st.row.xvector + H); st.row.xvector = st.xvector.data(); }
+    *stream = (int32_t)slot;
+    return QASR_OK;
+}
+
+int qasr_tts_pool_step(qasr_tts_pool* p, qasr_tts_chunk* chunks, size_t cap, size_t* n) {
+    if (!p) return QASR_ERR_INVALID;
+    if (!n || (cap > 0 && !chunks)) return fail(p, QASR_ERR_INVALID, WHO + ": null argument");
+    *n = 0;
+    return pool_step(p, chunks, cap, n);
+}
+
+int qasr_tts_pool_timing(const qasr_tts_pool* p, float* ms) {
+    if (!p || !ms) return QASR_ERR_INVALID;
+    std::memcpy(ms, p->timing, sizeof(p->timing));
+    return QASR_OK;
+}
+
+int qasr_tts_pool_close(qasr_tts_pool* p, int32_t stream) {
+    if (!p) return QASR_ERR_INVALID;
+    if (stream < 0 || (size_t)stream >= p->streams.size()) return fail(p, QASR_ERR_INVALID, WHO + ": stream " + std::to_string(stream) + " outside the pool");
+    TtsStream& st = p->streams[stream];
+    int rc = QASR_OK;
+    if (st.state == TtsStream::RUNNING) rc = guarded(p, [&] { p->t->impl->pool_finish(stream); });
+    st = TtsStream{};
+    return rc;
+}
 
 int qasr_tts_create(const char* model_dir, const qasr_tts_config* cfg, qasr_tts** out) {
     return create_handle(model_dir, cfg, false, 0, 0, out);

@@ -32,7 +32,9 @@ class CodecQwen3TTS {
     CodecQwen3TTS(int device, const CheckedWeights& w, const CodecGeom& g, const std::vector<bool>& embed_stored, int max_windows,
                   hipStream_t work);
     ~CodecQwen3TTS();
-    void run(const std::vector<CodecWin>& wins, bool clip);                         // any number of windows, max_windows per pass
+    // any number of windows, max_windows per pass.  tail: the windows are decoded for what they keep -- under the knob codec_tail_rows the
+    // vocoder skips the rows only the dropped context needs (the same bits)
+    void run(const std::vector<CodecWin>& wins, bool clip, bool tail = false);
     void quantizer_decode(const int32_t* codes, int B, int T, float* out);          // codes [B][Q][T] -> [B][T][hidden]
     void pre_transformer(const float* x, int B, int T, float* out);                 // [B][T][latent] -> [B][T][latent]
     void unload();
@@ -50,13 +52,14 @@ class CodecQwen3TTS {
     enum Mode { FULL, RVQ, PT };
     void check_loaded() const;
     void ensure(long M1, Mode mode);
-    void pass(const CodecWin* w, int n, Mode mode, bool clip, const float* xin, float* xout);
+    void pass(const CodecWin* w, int n, Mode mode, bool clip, const float* xin, float* xout, bool tail = false);
     void plan(const CodecWin* w, int n, bool with_codes);
     void dev_rvq();
     void dev_pre_transformer();
-    void dev_vocoder(bool clip);
+    void dev_vocoder(bool clip, bool tail);
     template <bool SNAKE, int EPI>
-    void gemm(const Gemm& g, const float* A, long M, int dil, int rate, const Snake* sn, const float* ls, const float* R, float* C, int ldc, int bmod);
+    void gemm(const Gemm& g, const float* A, long M, int dil, int rate, const Snake* sn, const float* ls, const float* R, float* C, int ldc, int bmod,
+              int lead = -1);                                                       // lead >= 0: TailRows with that lead
     const float* W(size_t off) const { return d_w_.as<float>() + off; }
     int device_;
     CodecGeom g_;
@@ -76,9 +79,20 @@ class CodecQwen3TTS {
     // the pass
     long M1_ = 0;
     int n_win_ = 0;
-    DevBuf d_w_, d_codes_, d_fstart_, d_win_, d_emb_, d_q_, d_lat_[2], d_x_, d_h_, d_qkv_, d_att_, d_g_, d_big_[3], d_wave_;
+    DevBuf d_w_, d_codes_, d_fstart_, d_kept_, d_win_, d_emb_, d_q_, d_lat_[2], d_x_, d_h_, d_qkv_, d_att_, d_g_, d_big_[3], d_wave_;
     long cap_small_ = 0, cap_big_ = 0, cap_win_ = 0;
     std::vector<int32_t> h_codes_;
 };
+
+// How many input rows before the first kept one each stage of the vocoder needs so that every kept sample is what the whole window gives:
+// leads[0] the input of decoder.decoder.0, leads[1 .. 4] the inputs of blocks 1 .. 4, leads[5] the input of the output conv, each at its own
+// rate.  From the output backwards: 6 for the k = 7 output conv; a block of stride s whose output needs `out` rows needs
+// ceil((out + 6 (1 + 3 + 9)) / s) + 1 (three k = 7 units of dilation 1 3 9, then the transposed conv's previous-row tap); decoder.decoder.0
+// adds its own 6.  The real rates 8 5 4 3 give 20 14 23 28 29 6.  Pure host.
+void codec_tail_leads(const int rates[4], int leads[6]);
+
+// windows handed over by another handle kind of this library (the TTS stream pool, api_tts.cpp): the checks of qasr_codec_forward on
+// every window (loaded, 1 .. 35 frames, every code inside its codebook), then one run(); status and message as the C ABI (api_codec.cpp)
+int codec_run_windows(qasr_codec* c, const std::vector<CodecWin>& wins, bool clip);
 
 }  // namespace qasr

@@ -25,6 +25,7 @@
 // then a fixed tree; attention sums over d, then over j, in order.  No reduction crosses a window and nothing depends on a window's
 // place, so a window's samples are the same bits alone, in any batch, at any place in it and under any split into passes.
 #include "codec_qwen3tts.h"
+#include "tuning.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -84,6 +85,15 @@ std::vector<CodecSpan> codec_window_positions(long T) {
         offset = end;
     }
     return out;
+}
+
+constexpr int UNIT_DIL[3] = {1, 3, 9};                 // the residual units of a block, k = 7 each
+
+void codec_tail_leads(const int rates[4], int leads[6]) {
+    const int units = 6 * (UNIT_DIL[0] + UNIT_DIL[1] + UNIT_DIL[2]);
+    leads[5] = 6;
+    for (int k = 3; k >= 0; --k) leads[k + 1] = cdiv(leads[k + 2] + units, rates[k]) + 1;
+    leads[0] = leads[1] + 6;
 }
 
 // ---- kernels ------------------------------------------------------------------------------------------------------------------------
@@ -146,13 +156,16 @@ __global__ __launch_bounds__(ROW_THREADS) void codec_attn_kernel(const float* __
     }
 }
 
-// wave[m] = clip(bias + sum_j sum_c snake(x[m - (6 - j)][c]) w[j][c]) (:683-685); x [M][C], one thread per sample
+// wave[m] = clip(bias + sum_j sum_c snake(x[m - (6 - j)][c]) w[j][c]) (:683-685); x [M][C], one thread per sample.  TAIL: only the samples
+// from the window's first kept frame (kept[frame row]) on are computed.
+template <bool TAIL>
 __global__ __launch_bounds__(ROW_THREADS) void codec_out_kernel(const float* __restrict__ x, long M, int C, int rate, const int* __restrict__ fstart,
-                                                                const float* __restrict__ sa, const float* __restrict__ sb,
-                                                                const float* __restrict__ w, const float* __restrict__ b, int clip,
-                                                                float* __restrict__ wave) {
+                                                                const int* __restrict__ kept, const float* __restrict__ sa,
+                                                                const float* __restrict__ sb, const float* __restrict__ w,
+                                                                const float* __restrict__ b, int clip, float* __restrict__ wave) {
     const long m = (long)blockIdx.x * ROW_THREADS + threadIdx.x;
     if (m >= M) return;
+    if (TAIL && m < (long)kept[m / rate] * rate) return;
     const long start = (long)fstart[m / rate] * rate;
     float acc = 0.0f;
     for (int j = 0; j < 7; ++j) {
@@ -271,7 +284,7 @@ void CodecQwen3TTS::unload() {
     QASR_HIP(hipSetDevice(device_));
     QASR_HIP(hipStreamSynchronize(work_));
     for (DevBuf* b : {&d_w_, &d_codes_, &d_fstart_, &d_win_, &d_emb_, &d_q_, &d_lat_[0], &d_lat_[1], &d_x_, &d_h_, &d_qkv_, &d_att_, &d_g_,
-                      &d_big_[0], &d_big_[1], &d_big_[2], &d_wave_})
+                      &d_big_[0], &d_big_[1], &d_big_[2], &d_wave_, &d_kept_})
         b->release();
     cap_small_ = cap_big_ = cap_win_ = 0;
     loaded_ = false;
@@ -290,6 +303,7 @@ void CodecQwen3TTS::ensure(long M1, Mode mode) {
         cap_small_ = 0;
         d_codes_.alloc(M1 * g_.quantizers * sizeof(int));
         d_fstart_.alloc(M1 * sizeof(int));
+        d_kept_.alloc(M1 * sizeof(int));
         d_emb_.alloc(M1 * 2 * g_.codebook_dim * F);
         d_q_.alloc(M1 * g_.hidden * F);
         d_lat_[0].alloc(M1 * g_.latent * F); d_lat_[1].alloc(M1 * g_.latent * F);
@@ -306,13 +320,14 @@ void CodecQwen3TTS::ensure(long M1, Mode mode) {
     }
 }
 
-// uploads the pass's tables: fstart[frame row] = its window's first row, win[w] = (frames, first row), codes [M1][Q]
+// uploads the pass's tables: fstart[frame row] = its window's first row, kept[frame row] = its window's first kept row,
+// win[w] = (frames, first row), codes [M1][Q]
 void CodecQwen3TTS::plan(const CodecWin* w, int n, bool with_codes) {
     QASR_HIP(hipStreamSynchronize(work_));             // the tables are rewritten
     long M1 = 0;
     for (int i = 0; i < n; ++i) M1 += w[i].frames;
     M1_ = M1; n_win_ = n;
-    std::vector<int> fstart((size_t)M1), win((size_t)2 * n);
+    std::vector<int> fstart((size_t)M1), kept((size_t)M1), win((size_t)2 * n);
     const int Q = g_.quantizers;
     if (with_codes) h_codes_.resize((size_t)M1 * Q);
     long off = 0;
@@ -320,6 +335,7 @@ void CodecQwen3TTS::plan(const CodecWin* w, int n, bool with_codes) {
         win[2 * i] = w[i].frames; win[2 * i + 1] = (int)off;
         for (int t = 0; t < w[i].frames; ++t) {
             fstart[off + t] = (int)off;
+            kept[off + t] = (int)off + w[i].context;
             if (with_codes)
                 for (int q = 0; q < Q; ++q) h_codes_[(size_t)(off + t) * Q + q] = w[i].codes[(size_t)q * w[i].ld + w[i].start + t];
         }
@@ -328,13 +344,23 @@ void CodecQwen3TTS::plan(const CodecWin* w, int n, bool with_codes) {
     if (n > cap_win_) { cap_win_ = 0; d_win_.alloc((size_t)2 * n * sizeof(int)); cap_win_ = n; }
     QASR_HIP(hipMemcpy(d_win_.p, win.data(), win.size() * sizeof(int), hipMemcpyHostToDevice));
     QASR_HIP(hipMemcpy(d_fstart_.p, fstart.data(), fstart.size() * sizeof(int), hipMemcpyHostToDevice));
+    QASR_HIP(hipMemcpy(d_kept_.p, kept.data(), kept.size() * sizeof(int), hipMemcpyHostToDevice));
     if (with_codes) QASR_HIP(hipMemcpy(d_codes_.p, h_codes_.data(), h_codes_.size() * sizeof(int), hipMemcpyHostToDevice));
 }
 
 template <bool SNAKE, int EPI>
 void CodecQwen3TTS::gemm(const Gemm& gm, const float* A, long M, int dil, int rate, const Snake* sn, const float* ls, const float* R, float* C,
-                         int ldc, int bmod) {
+                         int ldc, int bmod, int lead) {
     const dim3 grid((unsigned)cdiv(M, CG_T), (unsigned)cdiv(gm.N, CG_T));
+    if constexpr (EPI == E_LIN || (SNAKE && EPI == E_RES)) {           // the vocoder's launches from decoder.decoder.0 on
+        if (lead >= 0) {
+            hipLaunchKernelGGL((codec_gemm_kernel<TailRows, SNAKE, EPI>), grid, dim3(CG_THREADS), 0, work_, A, M, gm.Cin, gm.taps, dil,
+                               TailRows{d_fstart_.as<int>(), d_kept_.as<int>(), rate, lead}, W(gm.wt), gm.K, gm.N,
+                               gm.has_bias ? W(gm.bias) : (const float*)nullptr, bmod, sn ? W(sn->a) : (const float*)nullptr,
+                               sn ? W(sn->b) : (const float*)nullptr, ls, R, C, ldc);
+            return;
+        }
+    }
     hipLaunchKernelGGL((codec_gemm_kernel<WindowRows, SNAKE, EPI>), grid, dim3(CG_THREADS), 0, work_, A, M, gm.Cin, gm.taps, dil,
                        WindowRows{d_fstart_.as<int>(), rate}, W(gm.wt), gm.K, gm.N, gm.has_bias ? W(gm.bias) : (const float*)nullptr, bmod,
                        sn ? W(sn->a) : (const float*)nullptr, sn ? W(sn->b) : (const float*)nullptr, ls, R, C, ldc);
@@ -368,9 +394,13 @@ void CodecQwen3TTS::dev_pre_transformer() {
     QASR_HIP(hipGetLastError());
 }
 
-// d_lat_[1] -> d_wave_; records ev_[2] .. ev_[8]
-void CodecQwen3TTS::dev_vocoder(bool clip) {
+// d_lat_[1] -> d_wave_; records ev_[2] .. ev_[8].  tail: every launch from decoder.decoder.0 on starts each window at the first row a
+// kept sample depends on (codec_tail_leads; inside a block, from its output backwards: unit j adds 6 x its dilation to the lead of the
+// launches before it, and a transposed conv's row covers `stride` output rows).  The two upsampling stages run whole windows.
+void CodecQwen3TTS::dev_vocoder(bool clip, bool tail) {
     const int L = g_.latent;
+    int leads[6];
+    codec_tail_leads(g_.rates, leads);
     float* buf[3] = {d_big_[0].as<float>(), d_big_[1].as<float>(), d_big_[2].as<float>()};
     const float* x = d_lat_[1].as<float>();
     int rate = 1;
@@ -391,32 +421,42 @@ void CodecQwen3TTS::dev_vocoder(bool clip) {
     int cur = 1;
     {
         const int nxt = 0;
-        gemm<false, E_LIN>(dec0_, buf[cur], M1_ * rate, 1, rate, nullptr, nullptr, nullptr, buf[nxt], g_.decoder_dim, g_.decoder_dim);
+        gemm<false, E_LIN>(dec0_, buf[cur], M1_ * rate, 1, rate, nullptr, nullptr, nullptr, buf[nxt], g_.decoder_dim, g_.decoder_dim,
+                           tail ? leads[1] : -1);
         cur = nxt;
     }
     int C = g_.decoder_dim;
     for (int k = 0; k < 4; ++k) {                      // SnakeBeta, transposed conv, three residual units (:221-228)
         const Block& bl = blocks_[k];
         const int nxt = (cur + 1) % 3, tmp = (cur + 2) % 3, co = C / 2;
-        gemm<true, E_LIN>(bl.tconv, buf[cur], M1_ * rate, 1, rate, &bl.s, nullptr, nullptr, buf[nxt], bl.tconv.N, co);
+        int lead[3];                                   // of unit j's two launches: what the units behind it read before the block's output lead
+        lead[2] = leads[k + 2];
+        for (int j = 1; j >= 0; --j) lead[j] = lead[j + 1] + 6 * UNIT_DIL[j + 1];
+        gemm<true, E_LIN>(bl.tconv, buf[cur], M1_ * rate, 1, rate, &bl.s, nullptr, nullptr, buf[nxt], bl.tconv.N, co,
+                          tail ? cdiv(lead[0] + 6 * UNIT_DIL[0], g_.rates[k]) : -1);
         rate *= g_.rates[k];
         const long M = M1_ * rate;
-        const int dil[3] = {1, 3, 9};
         for (int j = 0; j < 3; ++j) {
-            gemm<true, E_LIN>(bl.u[j].c1, buf[nxt], M, dil[j], rate, &bl.u[j].s1, nullptr, nullptr, buf[tmp], co, co);
-            gemm<true, E_RES>(bl.u[j].c2, buf[tmp], M, 1, rate, &bl.u[j].s2, nullptr, buf[nxt], buf[nxt], co, co);
+            gemm<true, E_LIN>(bl.u[j].c1, buf[nxt], M, UNIT_DIL[j], rate, &bl.u[j].s1, nullptr, nullptr, buf[tmp], co, co, tail ? lead[j] : -1);
+            gemm<true, E_RES>(bl.u[j].c2, buf[tmp], M, 1, rate, &bl.u[j].s2, nullptr, buf[nxt], buf[nxt], co, co, tail ? lead[j] : -1);
         }
         cur = nxt; C = co;
         QASR_HIP(hipEventRecord(ev_[4 + k], work_));
     }
     const long M = M1_ * rate;
-    hipLaunchKernelGGL(codec_out_kernel, dim3((unsigned)cdiv(M, ROW_THREADS)), dim3(ROW_THREADS), 0, work_, buf[cur], M, C, rate,
-                       d_fstart_.as<int>(), W(final_snake_.a), W(final_snake_.b), W(final_w_), W(final_b_), clip ? 1 : 0, d_wave_.as<float>());
+    if (tail)
+        hipLaunchKernelGGL(codec_out_kernel<true>, dim3((unsigned)cdiv(M, ROW_THREADS)), dim3(ROW_THREADS), 0, work_, buf[cur], M, C, rate,
+                           d_fstart_.as<int>(), d_kept_.as<int>(), W(final_snake_.a), W(final_snake_.b), W(final_w_), W(final_b_), clip ? 1 : 0,
+                           d_wave_.as<float>());
+    else
+        hipLaunchKernelGGL(codec_out_kernel<false>, dim3((unsigned)cdiv(M, ROW_THREADS)), dim3(ROW_THREADS), 0, work_, buf[cur], M, C, rate,
+                           d_fstart_.as<int>(), d_kept_.as<int>(), W(final_snake_.a), W(final_snake_.b), W(final_w_), W(final_b_), clip ? 1 : 0,
+                           d_wave_.as<float>());
     QASR_HIP(hipEventRecord(ev_[8], work_));
     QASR_HIP(hipGetLastError());
 }
 
-void CodecQwen3TTS::pass(const CodecWin* w, int n, Mode mode, bool clip, const float* xin, float* xout) {
+void CodecQwen3TTS::pass(const CodecWin* w, int n, Mode mode, bool clip, const float* xin, float* xout, bool tail) {
     QASR_HIP(hipSetDevice(device_));
     long M1 = 0;
     for (int i = 0; i < n; ++i) {
@@ -447,7 +487,7 @@ void CodecQwen3TTS::pass(const CodecWin* w, int n, Mode mode, bool clip, const f
         float ms = 0; QASR_HIP(hipEventElapsedTime(&ms, ev_[1], ev_[2])); timing_[1] += ms;
         return;
     }
-    dev_vocoder(clip);
+    dev_vocoder(clip, tail && tuning().codec_tail_rows != 0);
     for (int i = 0, off = 0; i < n; off += w[i].frames, ++i)
         QASR_HIP(hipMemcpyAsync(w[i].out, d_wave_.as<float>() + (size_t)(off + w[i].context) * spf_,
                                 (size_t)(w[i].frames - w[i].context) * spf_ * F, hipMemcpyDeviceToHost, work_));
@@ -461,11 +501,11 @@ void CodecQwen3TTS::pass(const CodecWin* w, int n, Mode mode, bool clip, const f
 }
 
 // ---- entry points -------------------------------------------------------------------------------------------------------------------
-void CodecQwen3TTS::run(const std::vector<CodecWin>& wins, bool clip) {
+void CodecQwen3TTS::run(const std::vector<CodecWin>& wins, bool clip, bool tail) {
     check_loaded();
     for (float& t : timing_) t = 0.0f;
     for (size_t i = 0; i < wins.size(); i += (size_t)max_windows_)
-        pass(wins.data() + i, (int)std::min(wins.size() - i, (size_t)max_windows_), FULL, clip, nullptr, nullptr);
+        pass(wins.data() + i, (int)std::min(wins.size() - i, (size_t)max_windows_), FULL, clip, nullptr, nullptr, tail);
 }
 
 void CodecQwen3TTS::quantizer_decode(const int32_t* codes, int B, int T, float* out) {

@@ -107,15 +107,33 @@ struct RowSpan { long last, first; };
 // first frame row.  Input and output are at the same rate.
 struct WindowRows {
     static constexpr bool BIAS_REPEATS = true;         // a transposed conv's N = s C_out columns share C_out biases: bias[n % bmod]
+    static constexpr bool SKIPS = false;               // every row is computed
     const int* fstart;
     int rate;
     __device__ __forceinline__ RowSpan operator()(long m) const { return {m, (long)fstart[m / rate] * rate}; }
+};
+
+// WindowRows for windows of which only the tail is kept (streamed chunks behind their left context): kept[frame row] = the window's
+// first kept frame row, lead = how many rows at this launch's rate before the first kept one a later launch still reads
+// (codec_tail_leads).  A row before live(m) is dead: nothing kept depends on it, a tile of dead rows is not computed and keeps whatever
+// an earlier pass left there, which a correct lead never reads.  Rows are located as in WindowRows, so a live row is the same bits.
+struct TailRows {
+    static constexpr bool BIAS_REPEATS = true;
+    static constexpr bool SKIPS = true;
+    const int *fstart, *kept;
+    int rate, lead;
+    __device__ __forceinline__ RowSpan operator()(long m) const { return {m, (long)fstart[m / rate] * rate}; }
+    __device__ __forceinline__ long live(long m) const {               // the first live row of m's window, clamped to the window's first row
+        const long f = m / rate, a = (long)kept[f] * rate - lead, b = (long)fstart[f] * rate;
+        return a > b ? a : b;
+    }
 };
 
 // the encoder's rows: ostart / istart are the first rows of the clips at the output / input level, output row t of a clip reads input
 // row t stride of the same clip.  ostart = nullptr: rows are independent (taps = 1).
 struct ClipRows {
     static constexpr bool BIAS_REPEATS = false;        // bias[n]
+    static constexpr bool SKIPS = false;
     const int *ostart, *istart;
     int nclips, stride;
     __device__ __forceinline__ RowSpan operator()(long m) const {
@@ -128,7 +146,7 @@ struct ClipRows {
 
 // C = epilogue(sum_k A(m, k) Wt[k][n]), k = j C_in + c <-> x[rows(m).last - (taps - 1 - j) dil][c], zero before rows(m).first.
 // A [input rows][C_in], Wt [K][N].  bias[n], or bias[n % bmod] where Rows::BIAS_REPEATS (nullptr: none).  E_SWIGLU: columns 2 i,
-// 2 i + 1 are gate i, up i; C [M][N / 2].
+// 2 i + 1 are gate i, up i; C [M][N / 2].  Rows::SKIPS: tiles of dead rows return at once (block-uniform, before any barrier).
 template <class Rows, bool SNAKE, int EPI>
 __global__ __launch_bounds__(CG_THREADS) void codec_gemm_kernel(const float* __restrict__ A, long M, int Cin, int taps, int dil, Rows rows,
                                                                 const float* __restrict__ Wt, int K, int N, const float* __restrict__ bias,
@@ -139,6 +157,10 @@ __global__ __launch_bounds__(CG_THREADS) void codec_gemm_kernel(const float* __r
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const long m0 = (long)blockIdx.x * CG_T;
     const int n0 = blockIdx.y * CG_T;
+    if constexpr (Rows::SKIPS) {                       // a tile wholly before the live rows of its last row's window, and wholly inside that
+        const long ml = (m0 + CG_T < M ? m0 + CG_T : M) - 1;           // window (the end of an earlier window is always live): nothing to do
+        if (ml < rows.live(ml) && m0 >= rows(ml).first) return;
+    }
     RowSpan span[4];                                   // of each A row this thread loads
 #pragma unroll
     for (int r = 0; r < 4; ++r) {

@@ -94,6 +94,14 @@ class TtsTalker {
     int max_ref_text() const { return max_ref_text_; }
     static void check_geometry(const qasr_tts_config& c);      // std::invalid_argument for what the kernels do not serve
     static int icl_context(const qasr_tts_config& c, int max_ref_frames, int max_ref_text);   // positions of an ICL handle; throws over TTS_MAX_CTX
+    // ---- the stream pool's view (api_tts.cpp, qasr_tts_pool_*): a batch row is a slot that a stream joins and
+    // leaves at any frame.  Everything a row owns is per slot; a free slot carries finished = 1, is computed and writes nothing.
+    void pool_begin(const qasr_tts_sampling& s, unsigned long long seed);     // the pool's Knobs, every slot free, table rows 0 1 2
+    void pool_admit(int slot, const TtsRow& r);                                // the slot's state and its prompt but the last position
+    void pool_frames(int B, int n);                                            // n frames of slots 0 .. B - 1, no host read
+    void pool_poll(int B, int* n_frames, int* finished);                       // [B] each, synchronises
+    void pool_finish(int slot);                                                // finished = 1 (max_tokens reached, close)
+    void pool_codes(int slot, int f0, int n, int32_t* out);                    // frames f0 .. f0 + n - 1 of the slot -> out [16][n]
     struct Knobs;                        // device-side per-call values (tts_talker.hip)
 
   private:
@@ -106,8 +114,9 @@ class TtsTalker {
     void load_all(const SafeTensorsDir& st);
     void* dev_upload(const void* src, size_t bytes);
     void prefill(const std::vector<TtsRow>& rows, bool build_only = false);
+    int plan_row(const TtsRow& r, std::vector<int>& tp_ids, int tp_row0, int* pt, int* pc, int* tr, int& nt, float* xv, int* ref) const;
     void packed_prompt(int B, int Pmax);
-    void layer_steps(const Net& n, bf16_t* x, int B, bool talker, int cp_pos, bool kv_only_last);
+    void layer_steps(const Net& n, bf16_t* x, int B, bool talker, int cp_pos, bool kv_only_last, int row0 = 0);
     void issue_frame(int B, bool forced_mode);
     void run_frame(int B);
     void set_knobs(const qasr_tts_sampling& s, unsigned long long seed);

@@ -308,9 +308,11 @@ __global__ __launch_bounds__(256) void tts_next_input_kernel(TtsNextArgs a) {
     const int frame = a.st.frame_of[b], ctx = a.st.ctx_len[b];
     const bool fin = a.st.finished[b] != 0;
     if (tid < TTS_GROUPS) {
-        int c = a.forced ? a.forced[((long)b * TTS_GROUPS + tid) * a.forced_T + frame] : a.codes[((long)b * TTS_GROUPS + tid) * a.stride + frame];
+        int c = 0;                                                      // a finished row computes on, its values are never read; in a stream
+        if (!fin)                                                       // pool its frame index runs on past the code rows: no load there
+            c = a.forced ? a.forced[((long)b * TTS_GROUPS + tid) * a.forced_T + frame] : a.codes[((long)b * TTS_GROUPS + tid) * a.stride + frame];
         const int lim = tid == 0 ? a.codec_vocab : a.cp_vocab;
-        s_c[tid] = (fin || c < 0 || c >= lim) ? 0 : c;                  // a finished row computes on, its values are never read
+        s_c[tid] = (c < 0 || c >= lim) ? 0 : c;
     }
     __syncthreads();
     const int ti = frame < a.st.trail_len[b] ? a.trail[(long)b * a.max_trail + frame] : 0;      // row 0 of tp: tts_pad
@@ -750,8 +752,9 @@ static TtsState state_of(int* base, int B) { return TtsState{base, base + B, bas
 
 // one token per row through every layer of a network, in place on x.  talker: attention over the row's cache at ctx_len[b];
 // else the code predictor's attention at position cp_pos of the frame.  kv_only_last: the last layer stops behind its attention
-// (its K / V are all a later position needs of it).
-void TtsTalker::layer_steps(const Net& n, bf16_t* x, int B, bool talker, int cp_pos, bool kv_only_last) {
+// (its K / V are all a later position needs of it).  row0 (Talker only): x holds the rows of slots row0 .. row0 + B - 1, whose state, RoPE
+// rows and cache blocks are read at their own slots (the pool admits one slot while the others stand still).
+void TtsTalker::layer_steps(const Net& n, bf16_t* x, int B, bool talker, int cp_pos, bool kv_only_last, int row0) {
     const int nq = n.heads * n.hd, nkv = n.kv * n.hd, half = n.hd / 2;
     const int MB = cfg_.max_batch;
     TtsState st = state_of(d_state_, MB);
@@ -762,9 +765,10 @@ void TtsTalker::layer_steps(const Net& n, bf16_t* x, int B, bool talker, int cp_
         decode_gemv_q_launch(DEC_EPI_BF16, a, L.qkv.img, L.ln1, n.eps, d_scratch_, stream_);
         if (talker) {
             const size_t per = (size_t)MB * n.kv * max_ctx_ * n.hd;
-            KVLayout kv{d_k_ + l * per, nullptr, max_ctx_, n.kv, n.hd, d_vf_ + l * per};
-            decode_attention_launch(d_qkv_, st.ctx_len, B, n.heads, n.kv, n.hd, L.qn, L.kn, n.eps, d_rope_rows_,
-                                    d_rope_rows_ + (size_t)MB * half, kv, d_attn_, stream_);
+            const size_t slot0 = (size_t)row0 * n.kv * max_ctx_ * n.hd;      // KVLayout::off(slot, 0, 0)
+            KVLayout kv{d_k_ + l * per + slot0, nullptr, max_ctx_, n.kv, n.hd, d_vf_ + l * per + slot0};
+            decode_attention_launch(d_qkv_, st.ctx_len + row0, B, n.heads, n.kv, n.hd, L.qn, L.kn, n.eps, d_rope_rows_ + (size_t)row0 * half,
+                                    d_rope_rows_ + (size_t)(MB + row0) * half, kv, d_attn_, stream_);
         } else {
             const size_t per = (size_t)MB * n.kv * TTS_GROUPS * n.hd;
             hipLaunchKernelGGL(tts_cp_attn_kernel, dim3(n.kv, B), dim3(64), 0, stream_, (const bf16_t*)d_qkv_, cp_pos, n.heads, n.kv, L.qn, L.kn,
@@ -849,6 +853,42 @@ void TtsTalker::run_frame(int B) {
     QASR_HIP(hipGraphLaunch(it->second, stream_));
 }
 
+// The prompt plan of one row: buildPrefillEmbeddings (Qwen3TTS.swift:1313-1390), for an ICL row buildICLPrefillEmbeddings.  pt / pc
+// [max_prefill_] (preset to -1): the text-side and codec-side entry of every position; tr [max_text]: the trailing text rows, nt of them.
+// A text id is appended to tp_ids and named by its row of the projected text table, tp_row0 + its place in tp_ids (rows 0 1 2 of the
+// table are tts_pad, tts_bos, tts_eos).  xv [hidden], ref [16][max_ref_frames_] (ICL rows).  Returns the prompt length.
+int TtsTalker::plan_row(const TtsRow& r, std::vector<int>& tp_ids, int tp_row0, int* pt, int* pc, int* tr, int& nt, float* xv, int* ref) const {
+    const auto& c = cfg_;
+    int n = 0;
+    nt = 0;
+    auto text_row = [&](int id) { tp_ids.push_back(id); return tp_row0 + (int)tp_ids.size() - 1; };
+    for (int i = 0; i < r.n_instruct; ++i) pt[n++] = text_row(r.instruct[i]);                  // instruct in front
+    for (int i = 0; i < 3; ++i) pt[n++] = text_row(r.text[i]);                                 // role
+    std::vector<int> codec = {c.codec_think, c.codec_think_bos, r.language, c.codec_think_eos};
+    if (r.xvector) { codec.push_back(-2); std::memcpy(xv, r.xvector, (size_t)c.hidden * 4); }
+    if (r.speaker >= 0) codec.push_back(r.speaker);
+    codec.push_back(c.codec_pad);
+    codec.push_back(c.codec_bos);
+    const int L = (int)codec.size();
+    for (int i = 0; i < L - 1; ++i) { pt[n] = i < L - 2 ? 0 : 1; pc[n++] = codec[i]; }        // tts_pad ... tts_bos over the prefix
+    if (r.ref_codes) {
+        // buildICLPrefillEmbeddings (Qwen3TTS+ICL.swift:158-242): the prefix's own codec_bos is dropped; every text id over codec_pad,
+        // tts_eos over codec_pad, tts_pad over codec_bos, tts_pad over every reference frame; no trailing text
+        for (int i = 0; i < r.n_ref_text; ++i) { pt[n] = text_row(r.ref_text[i]); pc[n++] = c.codec_pad; }
+        for (int i = 3; i < r.n_text - 5; ++i) { pt[n] = text_row(r.text[i]); pc[n++] = c.codec_pad; }
+        pt[n] = 2; pc[n++] = c.codec_pad;
+        pt[n] = 0; pc[n++] = c.codec_bos;
+        for (int f = 0; f < r.ref_frames; ++f) { pt[n] = 0; pc[n++] = -3 - f; }
+        for (int g = 0; g < TTS_GROUPS; ++g)
+            std::memcpy(&ref[(size_t)g * max_ref_frames_], r.ref_codes + (size_t)g * r.ref_frames, (size_t)r.ref_frames * 4);
+    } else {
+        pt[n] = text_row(r.text[3]); pc[n++] = codec[L - 1];                                   // first text + codec_bos
+        for (int i = 4; i < r.n_text - 5; ++i) tr[nt++] = text_row(r.text[i]);
+        tr[nt++] = 2;                                                                          // tts_eos
+    }
+    return n;
+}
+
 // buildPrefillEmbeddings (Qwen3TTS.swift:1313-1390) for every row, then the prompt positions but the last through the Talker's layers.
 void TtsTalker::prefill(const std::vector<TtsRow>& rows, bool build_only) {
     const auto& c = cfg_;
@@ -864,42 +904,13 @@ void TtsTalker::prefill(const std::vector<TtsRow>& rows, bool build_only) {
     pf_len_.assign(B, 0);
     int Pmax = 0;
     for (int b = 0; b < B; ++b) {
-        const TtsRow& r = rows[b];
-        ridx[b] = r.index;
-        int* pt = &pf_text[(size_t)b * P];
-        int* pc = &pf_codec[(size_t)b * P];
-        int n = 0;
-        auto text_row = [&](int id) { tp_ids.push_back(id); return (int)tp_ids.size() - 1; };
-        for (int i = 0; i < r.n_instruct; ++i) pt[n++] = text_row(r.instruct[i]);                  // instruct in front
-        for (int i = 0; i < 3; ++i) pt[n++] = text_row(r.text[i]);                                 // role
-        std::vector<int> codec = {c.codec_think, c.codec_think_bos, r.language, c.codec_think_eos};
-        if (r.xvector) { codec.push_back(-2); std::memcpy(&xv[(size_t)b * H], r.xvector, (size_t)H * 4); }
-        if (r.speaker >= 0) codec.push_back(r.speaker);
-        codec.push_back(c.codec_pad);
-        codec.push_back(c.codec_bos);
-        const int L = (int)codec.size();
-        for (int i = 0; i < L - 1; ++i) { pt[n] = i < L - 2 ? 0 : 1; pc[n++] = codec[i]; }        // tts_pad ... tts_bos over the prefix
+        ridx[b] = rows[b].index;
         int nt = 0;
-        if (r.ref_codes) {
-            // buildICLPrefillEmbeddings (Qwen3TTS+ICL.swift:158-242): the prefix's own codec_bos is dropped; every text id over codec_pad,
-            // tts_eos over codec_pad, tts_pad over codec_bos, tts_pad over every reference frame; no trailing text
-            for (int i = 0; i < r.n_ref_text; ++i) { pt[n] = text_row(r.ref_text[i]); pc[n++] = c.codec_pad; }
-            for (int i = 3; i < r.n_text - 5; ++i) { pt[n] = text_row(r.text[i]); pc[n++] = c.codec_pad; }
-            pt[n] = 2; pc[n++] = c.codec_pad;
-            pt[n] = 0; pc[n++] = c.codec_bos;
-            for (int f = 0; f < r.ref_frames; ++f) { pt[n] = 0; pc[n++] = -3 - f; }
-            for (int g = 0; g < TTS_GROUPS; ++g)
-                std::memcpy(&ref[((size_t)b * TTS_GROUPS + g) * max_ref_frames_], r.ref_codes + (size_t)g * r.ref_frames, (size_t)r.ref_frames * 4);
-        } else {
-            pt[n] = text_row(r.text[3]); pc[n++] = codec[L - 1];                                   // first text + codec_bos
-            int* tr = &trail[(size_t)b * c.max_text];
-            for (int i = 4; i < r.n_text - 5; ++i) tr[nt++] = text_row(r.text[i]);
-            tr[nt++] = 2;                                                                          // tts_eos
-        }
+        const int n = plan_row(rows[b], tp_ids, 0, &pf_text[(size_t)b * P], &pf_codec[(size_t)b * P], &trail[(size_t)b * c.max_text], nt,
+                               &xv[(size_t)b * H], icl ? &ref[(size_t)b * TTS_GROUPS * max_ref_frames_] : nullptr);
         pf_len_[b] = n;
-        int* s = state.data();
-        s[4 * MB + b] = nt;
-        s[5 * MB + b] = n;
+        state[(size_t)4 * MB + b] = nt;
+        state[(size_t)5 * MB + b] = n;
         Pmax = std::max(Pmax, n);
     }
     for (int b = B; b < MB; ++b) state[(size_t)1 * MB + b] = 1;
@@ -1068,6 +1079,98 @@ void TtsTalker::forced(const std::vector<TtsRow>& rows, const TtsForcedOut& f) {
     QASR_HIP(hipStreamSynchronize(stream_));
     for (auto& fb : forced_buf_) fb.reset();
     d_f_codes_ = nullptr; d_f_tlog_ = d_f_cplog_ = d_f_hid_ = nullptr;
+}
+
+// ================================================================================================
+// The stream pool's view (qasr_tts_pool_*, api_tts.cpp).  What prefill() builds for a whole call is built here for
+// one slot: the slot's rows of the projected text table are rows 3 + slot * per_slot .. of d_tp_ (max_tp_ holds max_batch such blocks),
+// its plan, trailing indices, x-vector, history bits, code rows and six state words are its rows of the call-wide arrays.
+// ================================================================================================
+void TtsTalker::pool_begin(const qasr_tts_sampling& s, unsigned long long seed) {
+    const auto& c = cfg_;
+    const int MB = c.max_batch;
+    QASR_HIP(hipSetDevice(c.device));
+    set_knobs(s, seed);
+    std::vector<int> state((size_t)6 * MB, 0);
+    for (int b = 0; b < MB; ++b) state[(size_t)MB + b] = 1;                 // every slot free
+    const int ids[3] = {c.tts_pad, c.tts_bos, c.tts_eos};
+    QASR_HIP(hipMemcpyAsync(d_state_, state.data(), state.size() * 4, hipMemcpyHostToDevice, stream_));
+    QASR_HIP(hipMemcpyAsync(d_tp_ids_, ids, sizeof(ids), hipMemcpyHostToDevice, stream_));
+    hipLaunchKernelGGL(tts_gather_rows_kernel, dim3(3), dim3(256), 0, stream_, text_emb_, (const int*)d_tp_ids_, c.text_hidden, d_tp_in_);
+    gemv_rows(fc1_.img.raw, d_tp_in_, 3, fc1_.bias, nullptr, d_tp_mid_, c.text_hidden, true, stream_);
+    gemv_rows(fc2_.img.raw, d_tp_mid_, 3, fc2_.bias, nullptr, d_tp_, c.hidden, false, stream_);
+    QASR_HIP(hipGetLastError());
+    QASR_HIP(hipStreamSynchronize(stream_));
+}
+
+void TtsTalker::pool_admit(int slot, const TtsRow& r) {
+    const auto& c = cfg_;
+    const int MB = c.max_batch, H = c.hidden, P = max_prefill_, half = c.head_dim / 2, TH = c.text_hidden;
+    if (slot < 0 || slot >= MB || r.ref_codes) throw std::invalid_argument("talker: pool_admit: slot outside the handle or an ICL row");
+    QASR_HIP(hipSetDevice(c.device));
+    const int tp0 = 3 + slot * (c.max_text + c.max_instruct + max_ref_text_);
+    std::vector<int> tp_ids, pt(P, -1), pc(P, -1), tr(c.max_text, 0);
+    std::vector<float> xv(H, 0.0f);
+    int nt = 0;
+    const int n = plan_row(r, tp_ids, tp0, pt.data(), pc.data(), tr.data(), nt, xv.data(), nullptr);
+    const int ntp = (int)tp_ids.size();
+    const int words[6] = {0, 0, 0, 0, nt, n};                               // ctx_len finished n_frames frame_of trail_len pf_len
+    const long long ridx = r.index;
+    QASR_HIP(hipMemcpyAsync(d_tp_ids_ + tp0, tp_ids.data(), (size_t)ntp * 4, hipMemcpyHostToDevice, stream_));
+    QASR_HIP(hipMemcpyAsync(d_pf_text_ + (size_t)slot * P, pt.data(), (size_t)P * 4, hipMemcpyHostToDevice, stream_));
+    QASR_HIP(hipMemcpyAsync(d_pf_codec_ + (size_t)slot * P, pc.data(), (size_t)P * 4, hipMemcpyHostToDevice, stream_));
+    QASR_HIP(hipMemcpyAsync(d_trail_ + (size_t)slot * c.max_text, tr.data(), (size_t)c.max_text * 4, hipMemcpyHostToDevice, stream_));
+    QASR_HIP(hipMemcpyAsync(d_xvec_ + (size_t)slot * H, xv.data(), (size_t)H * 4, hipMemcpyHostToDevice, stream_));
+    QASR_HIP(hipMemcpyAsync(d_row_index_ + slot, &ridx, 8, hipMemcpyHostToDevice, stream_));
+    for (int w = 0; w < 6; ++w) QASR_HIP(hipMemcpyAsync(d_state_ + (size_t)w * MB + slot, &words[w], 4, hipMemcpyHostToDevice, stream_));
+    QASR_HIP(hipMemsetAsync(d_seen_ + (size_t)slot * c.codec_vocab, 0, (size_t)c.codec_vocab, stream_));
+    QASR_HIP(hipMemsetAsync(d_codes_ + (size_t)slot * TTS_GROUPS * c.max_frames, 0xff, (size_t)TTS_GROUPS * c.max_frames * 4, stream_));
+    hipLaunchKernelGGL(tts_gather_rows_kernel, dim3(ntp), dim3(256), 0, stream_, text_emb_, (const int*)(d_tp_ids_ + tp0), TH,
+                       d_tp_in_ + (size_t)tp0 * TH);
+    gemv_rows(fc1_.img.raw, d_tp_in_ + (size_t)tp0 * TH, ntp, fc1_.bias, nullptr, d_tp_mid_ + (size_t)tp0 * TH, TH, true, stream_);
+    gemv_rows(fc2_.img.raw, d_tp_mid_ + (size_t)tp0 * TH, ntp, fc2_.bias, nullptr, d_tp_ + (size_t)tp0 * H, H, false, stream_);
+    // the one-row view: every pointer at the slot's row, the table (d_tp_) whole since the plan names its rows
+    bf16_t* pf = d_pf_ + (size_t)slot * P * H;
+    hipLaunchKernelGGL(tts_prefill_build_kernel, dim3(P, 1), dim3(256), 0, stream_, (const int*)(d_pf_text_ + (size_t)slot * P),
+                       (const int*)(d_pf_codec_ + (size_t)slot * P), P, (const bf16_t*)d_tp_, codec_emb_, (const float*)(d_xvec_ + (size_t)slot * H),
+                       H, pf, (const int*)nullptr, 0, (const bf16_t* const*)d_cp_emb_);
+    TtsState st = state_of(d_state_ + slot, MB);
+    bf16_t* x = d_x_ + (size_t)slot * H;
+    for (int s = 0; s < n; ++s) {
+        hipLaunchKernelGGL(tts_prefill_feed_kernel, dim3(1), dim3(256), 0, stream_, st, s, n, (const bf16_t*)pf, P, H, x,
+                           (const float*)d_rope_cos_, (const float*)d_rope_sin_, d_rope_rows_ + (size_t)slot * half,
+                           d_rope_rows_ + (size_t)(MB + slot) * half, half);
+        if (s + 1 < n) layer_steps(tk_, x, 1, true, 0, false, slot);       // the last position is the Talker step of the slot's frame 0
+    }
+    QASR_HIP(hipGetLastError());
+    QASR_HIP(hipStreamSynchronize(stream_));                              // the host vectors above go out of scope
+}
+
+void TtsTalker::pool_frames(int B, int n) {
+    QASR_HIP(hipSetDevice(cfg_.device));
+    for (int f = 0; f < n; ++f) run_frame(B);
+}
+
+void TtsTalker::pool_poll(int B, int* n_frames, int* finished) {
+    TtsState st = state_of(d_state_, cfg_.max_batch);
+    QASR_HIP(hipMemcpyAsync(n_frames, st.n_frames, (size_t)B * 4, hipMemcpyDeviceToHost, stream_));
+    QASR_HIP(hipMemcpyAsync(finished, st.finished, (size_t)B * 4, hipMemcpyDeviceToHost, stream_));
+    QASR_HIP(hipStreamSynchronize(stream_));
+}
+
+void TtsTalker::pool_finish(int slot) {
+    const int one = 1;
+    QASR_HIP(hipMemcpyAsync(state_of(d_state_, cfg_.max_batch).finished + slot, &one, 4, hipMemcpyHostToDevice, stream_));
+    QASR_HIP(hipStreamSynchronize(stream_));
+}
+
+void TtsTalker::pool_codes(int slot, int f0, int n, int32_t* out) {
+    const int F = cfg_.max_frames;
+    if (n <= 0) return;
+    if (f0 < 0 || f0 + n > F) throw std::invalid_argument("talker: pool_codes: frames outside the slot's rows");
+    QASR_HIP(hipMemcpy2DAsync(out, (size_t)n * 4, d_codes_ + (size_t)slot * TTS_GROUPS * F + f0, (size_t)F * 4, (size_t)n * 4, TTS_GROUPS,
+                              hipMemcpyDeviceToHost, stream_));
+    QASR_HIP(hipStreamSynchronize(stream_));
 }
 
 }  // namespace qasr

@@ -94,6 +94,15 @@ class QasrTtsIcl(C.Structure):
                 ("ref_codes", C.POINTER(C.POINTER(C.c_int32))), ("ref_frames", C.POINTER(C.c_int32))]
 
 
+class QasrTtsStreamConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("first_chunk_frames", "chunk_frames", "decoder_left_context")]
+
+
+class QasrTtsChunk(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("stream", "frame_index", "n_frames", "is_final")] + \
+               [("samples", C.POINTER(C.c_float)), ("n_samples", C.c_size_t), ("codes", C.POINTER(C.c_int32))]
+
+
 SC_TRANSCRIBE_FN = C.CFUNCTYPE(ScTranscriptionResult, C.c_void_p, C.POINTER(C.c_float), C.c_size_t, C.c_int)
 SC_RATE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p)
 
@@ -325,6 +334,8 @@ SIGNATURES = {
     "qasr_codec_hidden_size": (C.c_int, [_E]),
     "qasr_codec_latent_dim": (C.c_int, [_E]),
     "qasr_codec_forward": (C.c_int, [_E, _I, C.c_size_t, C.c_size_t, C.c_int, _F]),
+    "qasr_codec_forward_tail": (C.c_int, [_E, _I, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, _F]),
+    "qasr_codec_tail_leads": (C.c_int, [_I, _I]),
     "qasr_codec_window_positions": (C.c_int64, [C.c_size_t, _I, _I, _I, C.c_size_t]),
     "qasr_codec_decode": (C.c_int, [_E, _I, C.c_size_t, _F]),
     "qasr_codec_decode_batch": (C.c_int, [_E, _P(_I), _P(C.c_size_t), C.c_size_t, _P(_F)]),
@@ -385,6 +396,16 @@ SIGNATURES = {
     "qasr_tts_icl_prompt": (C.c_int, [_E, _P(QasrTtsRequest), _P(QasrTtsIcl), _F, _I]),
     "qasr_tts_clone": (C.c_int, [_E, _E, _E, _E, _P(QasrTtsRequest), _P(_I), _I, _P(_F), _P(C.c_size_t), _P(QasrTtsSampling), C.c_uint64,
                                  _P(_F), _P(C.c_size_t), _I, _I]),
+    "qasr_tts_default_stream_config": (None, [C.c_int, _P(QasrTtsStreamConfig)]),
+    "qasr_tts_pool_create": (C.c_int, [_E, _E, _P(QasrTtsSampling), C.c_uint64, _P(_E)]),
+    "qasr_tts_pool_open": (C.c_int, [_E, _P(QasrTtsRequest), _P(QasrTtsStreamConfig), _I]),
+    "qasr_tts_pool_step": (C.c_int, [_E, _P(QasrTtsChunk), C.c_size_t, _P(C.c_size_t)]),
+    "qasr_tts_pool_timing": (C.c_int, [_E, _F]),
+    "qasr_tts_pool_close": (C.c_int, [_E, C.c_int32]),
+    "qasr_tts_pool_live": (C.c_int, [_E]),
+    "qasr_tts_pool_destroy": (None, [_E]),
+    "qasr_tts_pool_last_error": (C.c_char_p, [_E]),
+    "qasr_tts_stream_chunks": (C.c_int64, [C.c_int32, C.c_int, _P(QasrTtsStreamConfig), _I, _I, _I, C.c_size_t]),
     "qasr_transducer_default_config": (C.c_int, [C.c_char_p, _P(QasrTransducerConfig)]),
     "qasr_tdt_greedy_decode": (C.c_int, [_P(QasrTransducerConfig), _P(QasrTransducerCallbacks), C.c_int32, _I, _F, C.c_int32, _F]),
     "qasr_rnnt_greedy_decode": (C.c_int, [_P(QasrTransducerConfig), _P(QasrTransducerCallbacks), C.c_int32, C.c_int32, _I, _F, C.c_int32, _I]),

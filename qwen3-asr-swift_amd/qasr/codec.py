@@ -38,6 +38,16 @@ def window_positions(T: int) -> List[Tuple[int, int, int]]:
     return [(int(s[i]), int(c[i]), int(e[i])) for i in range(n)]
 
 
+def tail_leads(upsample_rates=(8, 5, 4, 3)) -> List[int]:
+    """Input rows before the first kept one that decoder.decoder.0, blocks 1..4 and the output conv need (qasr_codec_tail_leads; pure CPU)."""
+    r = (C.c_int32 * 4)(*[int(v) for v in upsample_rates])
+    out = (C.c_int32 * 6)()
+    rc = _lib.load(strict=True).qasr_codec_tail_leads(r, out)
+    if rc != 0:
+        raise QasrError(f"qasr error {rc}: tail_leads({tuple(upsample_rates)})")
+    return [int(v) for v in out]
+
+
 class SpeechTokenizerDecoder:
     """SpeechTokenizerDecoder on the device."""
     sample_rate = SAMPLE_RATE
@@ -114,6 +124,17 @@ class SpeechTokenizerDecoder:
         B, _, T = a.shape
         out = np.zeros((B, SAMPLES_PER_FRAME * T), dtype=np.float32)
         self._check(self.lib.qasr_codec_forward(self.h, _iptr(a), B, T, 1 if clip else 0, _fptr(out)))
+        return out[0] if single else out
+
+    def forward_tail(self, codes, context: int, clip: bool = True) -> np.ndarray:
+        """forward()[..., 1920 * context:], bit for bit, without the vocoder rows only the dropped context needs (qasr_codec_forward_tail)."""
+        single = np.ndim(codes) == 2
+        a = self._codes(codes, 3)
+        B, _, T = a.shape
+        if not 0 <= int(context) < T:
+            raise QasrError("qasr error 1: the context must be shorter than the window")
+        out = np.zeros((B, SAMPLES_PER_FRAME * (T - int(context))), dtype=np.float32)
+        self._check(self.lib.qasr_codec_forward_tail(self.h, _iptr(a), B, T, int(context), 1 if clip else 0, _fptr(out)))
         return out[0] if single else out
 
     def decode(self, codes) -> np.ndarray:

@@ -3,9 +3,11 @@
 Reference: Sources/Qwen3TTS/Qwen3TTS.swift (Qwen3TTSModel.synthesize, synthesizeBatch, synthesizeWithVoiceClone in x-vector mode),
 Qwen3TTS+ICL.swift (synthesizeWithVoiceCloneICL), Talker.swift, CodePredictor.swift, Sampling.swift, Configuration.swift.  Text -> ids stays with the caller: the wrapper builds the chat
 template of prepareTextTokens / prepareInstructTokens around ids it is given.  Codes are int32 [16, n_frames] per row at 12.5 Hz; with a
-SpeechTokenizerDecoder (qasr.codec) they become 24 kHz float32 audio.  No CPU fallback.
+SpeechTokenizerDecoder (qasr.codec) they become 24 kHz float32 audio, in one piece or streamed in chunks (TtsStreamPool,
+synthesize_stream).  No CPU fallback.
 """
 import ctypes as C
+import weakref
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
@@ -54,6 +56,47 @@ class SamplingConfig:
     def c_struct(self) -> _lib.QasrTtsSampling:
         return _lib.QasrTtsSampling(float(self.temperature), int(self.top_k), float(self.top_p), float(self.repetition_penalty),
                                     int(self.max_tokens), float(self.eos_logit_bias))
+
+
+@dataclass
+class StreamingConfig:
+    """StreamingConfig (Qwen3TTS.swift): frames of the first chunk, of every later one, and of the codec's left context per chunk."""
+    first_chunk_frames: int = 3
+    chunk_frames: int = 25
+    decoder_left_context: int = 10
+
+    @classmethod
+    def default(cls) -> "StreamingConfig":
+        return cls()
+
+    @classmethod
+    def low_latency(cls) -> "StreamingConfig":
+        return cls(1, 15, 10)
+
+    def c_struct(self) -> _lib.QasrTtsStreamConfig:
+        return _lib.QasrTtsStreamConfig(int(self.first_chunk_frames), int(self.chunk_frames), int(self.decoder_left_context))
+
+
+@dataclass
+class AudioChunk:
+    """AudioChunk: float32 samples [1920 * n_frames] at 24 kHz from frame `frame_index` on; `codes` int32 [16, n_frames] of the chunk and
+    `stream` (the pool's name of the stream) beside the reference's fields."""
+    samples: np.ndarray
+    frame_index: int
+    is_final: bool
+    codes: Optional[np.ndarray] = None
+    stream: int = 0
+
+
+def stream_chunks(n_frames: int, ended_by_eos: bool, config: Optional[StreamingConfig] = None) -> List[tuple]:
+    """The (frame_index, n_frames, is_final) chunks a stream of n_frames frames is cut into (qasr_tts_stream_chunks; pure CPU)."""
+    sc = (config or StreamingConfig()).c_struct()
+    cap = int(n_frames) + 2
+    a, b, c = ((C.c_int32 * cap)() for _ in range(3))
+    n = _lib.load(strict=True).qasr_tts_stream_chunks(int(n_frames), int(bool(ended_by_eos)), C.byref(sc), a, b, c, cap)
+    if n < 0:
+        raise QasrError(f"qasr error {-n}: stream_chunks({n_frames}, {ended_by_eos}, {config})")
+    return [(int(a[i]), int(b[i]), bool(c[i])) for i in range(n)]
 
 
 def prepare_text_tokens(text_ids: Sequence[int]) -> List[int]:
@@ -150,11 +193,81 @@ class _Icl:
         self.icl = _lib.QasrTtsIcl(self.tp, self.tl, self.cp, self.cf)
 
 
+class TtsStreamPool:
+    """Up to max_batch concurrent streams over one Talker and one codec (qasr_tts_pool_*): open() queues a stream, step() runs all of
+    them to the next due chunk.  While the pool is open the model's one-shot calls are refused; close_pool() gives the model back."""
+
+    def __init__(self, model: "Qwen3TTSModel", codec, sampling: Optional[SamplingConfig] = None, seed: int = 0):
+        self.lib, self.model, self.codec, self.h = model.lib, model, codec, None
+        s = (sampling or SamplingConfig()).c_struct()
+        h = C.c_void_p()
+        model._check(self.lib.qasr_tts_pool_create(model.h, getattr(codec, "h", codec), C.byref(s), int(seed), C.byref(h)))
+        self.h = h
+        model._pool = weakref.ref(self)                                     # Qwen3TTSModel.close() destroys a pool it still has
+        self._chunks = (_lib.QasrTtsChunk * model.cfg.max_batch)()
+
+    def _check(self, rc):
+        if rc != 0:
+            raise QasrError(f"qasr error {rc}: {self.lib.qasr_tts_pool_last_error(self.h).decode()}")
+
+    def open(self, text, language, config: Optional[StreamingConfig] = None, speaker=None, xvector=None, instruct=None, row_index: int = 0,
+             _request=None) -> int:
+        """One templated id list (prepare_text_tokens) -> the stream's name, valid until its final chunk or close()."""
+        rq = _request or self.model._request([text], [language], None if speaker is None else [speaker], None if xvector is None else [xvector],
+                                             None if instruct is None else [instruct], [row_index])
+        sc = (config or StreamingConfig()).c_struct()
+        stream = C.c_int32(-1)
+        self._check(self.lib.qasr_tts_pool_open(self.h, C.byref(rq.rq), C.byref(sc), C.byref(stream)))
+        return int(stream.value)
+
+    def step(self) -> List[AudioChunk]:
+        """Runs every live stream to the next due chunk; [] only when no stream is live.  The chunks are copies."""
+        n = C.c_size_t(0)
+        self._check(self.lib.qasr_tts_pool_step(self.h, self._chunks, len(self._chunks), C.byref(n)))
+        out = []
+        for c in self._chunks[:n.value]:
+            f = int(c.n_frames)
+            samples = np.ctypeslib.as_array(c.samples, (int(c.n_samples),)).copy() if f else np.zeros(0, dtype=np.float32)
+            codes = np.ctypeslib.as_array(c.codes, (NUM_CODE_GROUPS, f)).copy() if f else np.zeros((NUM_CODE_GROUPS, 0), dtype=np.int32)
+            out.append(AudioChunk(samples, int(c.frame_index), bool(c.is_final), codes, int(c.stream)))
+        return out
+
+    def timing(self) -> dict:
+        """Host milliseconds of the last step: admission, frames (with the polls and the code reads), codec."""
+        ms = (C.c_float * 3)()
+        self._check(self.lib.qasr_tts_pool_timing(self.h, ms))
+        return dict(zip(("admission", "frames", "codec"), (float(v) for v in ms)))
+
+    def close(self, stream: int):
+        """Cancels a stream; its slot is free at once."""
+        self._check(self.lib.qasr_tts_pool_close(self.h, int(stream)))
+
+    @property
+    def live(self) -> int:
+        return int(self.lib.qasr_tts_pool_live(self.h))
+
+    def close_pool(self):
+        if self.h:
+            if self.model.h:                                                # never behind the handle it borrows
+                self.lib.qasr_tts_pool_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close_pool()
+
+    def __del__(self):
+        self.close_pool()
+
+
 class Qwen3TTSModel:
     """Qwen3TTSModel on the device: ids in, codes (and with a codec, audio) out."""
 
     def __init__(self, handle, cfg):
         self.lib, self.h, self.cfg = _lib.load(strict=True), handle, cfg
+        self._pool = None
 
     @classmethod
     def from_pretrained(cls, model_dir, cfg=None, max_ref_frames=None, max_ref_text=None, **over):
@@ -175,6 +288,9 @@ class Qwen3TTSModel:
         return cls(h, cfg)
 
     def close(self):
+        pool = self._pool() if self._pool is not None else None
+        if pool is not None:
+            pool.close_pool()                                               # the pool borrows the handle: it goes first
         if self.h:
             self.lib.qasr_tts_free(self.h)
             self.h = None
@@ -358,6 +474,14 @@ class Qwen3TTSModel:
         """synthesize: one templated id list -> float32 audio at 24 kHz."""
         return self.synthesize_batch(codec, [text], [language], sampling, seed, None if speaker is None else [speaker], None,
                                      None if instruct is None else [instruct])[0]
+
+    def synthesize_stream(self, codec, text, language, sampling: Optional[SamplingConfig] = None, streaming: Optional[StreamingConfig] = None,
+                          seed: int = 0, speaker=None, xvector=None, instruct=None, row_index: int = 0):
+        """synthesizeStream: a generator of AudioChunk over a pool of one stream; the last chunk has is_final set."""
+        with TtsStreamPool(self, codec, sampling, seed) as pool:
+            pool.open(text, language, streaming, speaker, xvector, instruct, row_index)
+            while pool.live:
+                yield from pool.step()
 
     def synthesize_with_voice_clone(self, codec, text, language, xvector, sampling: Optional[SamplingConfig] = None, seed: int = 0):
         """synthesizeWithVoiceClone in x-vector mode: xvector [hidden] from qasr.tts_speaker.SpeakerEncoder.embed."""
