@@ -296,6 +296,42 @@ int qasr_attn_case_probe(qasr_engine* e, int op, const qasr_attn_case* g, uint16
                          const int32_t* cu, const int32_t* slot_of_clip, const int32_t* pos, const int32_t* slot, const uint16_t* qn_w,
                          const uint16_t* kn_w, uint16_t* kcache, uint16_t* vfrag, const uint16_t* vt, uint16_t* qr, uint16_t* out);
 
+/* Diagnostic: the encoder-side kernels that are not the GEMM, one launch of the product's own entry (csrc/enc_kernels.h, csrc/ctc_kernels.h)
+ * on host data; needs no weights.  Nothing is restated.  `in` and `out` hold in_extra / out_extra ROWS beyond what the launch is told about
+ * (the caller fills them with NaN patterns / a sentinel); `out` is uploaded before the launch and downloaded after it, so an untouched byte
+ * comes back as it went in.  pf = f32 parameters, pw = bf16 parameters, idx / off = the launch's int32 / int64 index arrays.
+ *   MHA, WINDOW     in bf16 [rows + in_extra][3 * heads * hd] (q | k | v), idx = cu [n_clips + 1]; out bf16 [rows + out_extra][heads * hd].
+ *                   mha_attention_launch(max_len) under the mha_form knob / window_attention_launch.
+ *   LN_BF16, LN_GELU_BF16, LN_GELU_F32   in f32 [rows + in_extra][D], pf = gamma [D] | beta [D]; out bf16 / bf16 / f32 [rows + out_extra][D].
+ *   CONV0           in = pcm f32 [n_in], off = pcm_off [n_clips], idx = frame_off [n_clips] | n_out [n_clips], pf = stats [2 n_clips] |
+ *                   w [D][10] | bias [D] | ln_g [D] | ln_b [D], max_len = max_out; out bf16 [rows + out_extra][D] (D = channels).
+ *   WAVE_STATS      in = pcm f32 [n_in], off = pcm_off [rows], idx = n_samples [rows]; out f32 [rows + out_extra][2].
+ *   CONV1           in = mel f32 [n_in], idx = ChunkMeta records, 9 int32 per image (clip, t0, clen, w0, w1, w2, w3, tok_off, n_tok),
+ *                   rows = images, pf = bias [D], pw = w bf16 [D][9]; out bf16 [rows + out_extra][H1][W1][D].
+ *   ARGMAX          in f32 [(rows + in_extra) * ld], n = D; out int32 [rows + out_extra] ids, then ONE int32 error word.
+ *   CAST            in f32 [rows + in_extra] ELEMENTS; out bf16 [rows + out_extra].
+ *   CONV_ROWS       idx = in_off | out_off | n_out [n_clips each], rows = total_out, stride, D = C; out int64 [rows + out_extra].
+ *   FRAME_INFO      idx = frame_off | n_frames [n_clips each], rows = total; out int32 [rows + out_extra][2].
+ * Refused with QASR_ERR_INVALID before anything is launched: a cu that does not start at 0 / increase / end at rows, max_len below a clip,
+ * head_dim other than 32 / 64, mha_form 1 / 2 at head_dim 32 (the launcher would run form 0 there: the probe runs only the form that was
+ * asked for), a WINDOW clip above 128 rows, D % 4 != 0 or D > 2048 for the norms, more than 1024 CONV0 channels, CONV1 channels that are no
+ * multiple of 8, a ChunkMeta that reads outside mel, a CAST count that is no multiple of 4, a pcm offset or frame range outside its array.
+ * tests/test_gpu_enc_cases.py. */
+enum { QASR_ENC_MHA = 0, QASR_ENC_WINDOW, QASR_ENC_LN_BF16, QASR_ENC_LN_GELU_BF16, QASR_ENC_LN_GELU_F32, QASR_ENC_CONV0, QASR_ENC_WAVE_STATS,
+       QASR_ENC_CONV1, QASR_ENC_ARGMAX, QASR_ENC_CAST, QASR_ENC_CONV_ROWS, QASR_ENC_FRAME_INFO };
+typedef struct qasr_enc_case {
+    int32_t rows, n_clips;            /* rows the launch is told about; clips / windows */
+    int32_t in_extra, out_extra;      /* rows allocated beyond `rows` in `in` / `out` */
+    int32_t heads, hd, max_len;       /* attention; CONV0: max_out */
+    int32_t D, ld;                    /* width | channels | argmax n; ARGMAX row pitch */
+    int32_t n_in;                     /* elements of pcm / mel */
+    int32_t n_mels, mel_stride, H1, W1;   /* CONV1 */
+    int32_t stride;                   /* CONV_ROWS */
+    float eps;
+} qasr_enc_case;
+int qasr_enc_case_probe(qasr_engine* e, int op, const qasr_enc_case* g, const void* in, const int32_t* idx, const int64_t* off,
+                        const float* pf, const uint16_t* pw, void* out);
+
 /* ---- utterance-batch data parallelism inside one process ----------------------------------------------------------------------
  * Replaces the sequential file loop of `speech transcribe-batch` (Sources/AudioCLILib/TranscribeBatchCommand.swift:82-93) for a caller
  * that owns several GPUs: one engine (= one HIP device + one stream, weights replicated) and one host thread per listed device; clips

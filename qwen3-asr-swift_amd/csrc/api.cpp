@@ -2,6 +2,7 @@
 #include "api_guard.h"
 #include "engine.h"
 #include "ctc_engine.h"
+#include "tuning.h"
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -115,6 +116,79 @@ static const char* attn_case_refusal(int op, const qasr_attn_case& g, const uint
             if (slot[p] != slot_of_clip[c] || pos[p] != p - cu[c]) return "attn case: pos / slot contradict cu";
     }
     if (cu[g.n_clips] != g.n_pos) return "attn case: cu must end at n_pos";
+    return nullptr;
+}
+
+// qasr_enc_case_probe: why the arguments are refused, or null.  Everything a launch would index with is checked here, on the host.
+static const char* enc_case_refusal(int op, const qasr_enc_case& g, const void* in, const int32_t* idx, const int64_t* off, const float* pf,
+                                    const uint16_t* pw) {
+    if (op < QASR_ENC_MHA || op > QASR_ENC_FRAME_INFO) return "enc case: unknown operation";
+    if (g.rows < 0 || g.rows > (1 << 22) || g.in_extra < 0 || g.in_extra > 4096 || g.out_extra < 0 || g.out_extra > 4096)
+        return "enc case: rows in [0, 2^22], in_extra / out_extra in [0, 4096]";
+    const bool attn = op == QASR_ENC_MHA || op == QASR_ENC_WINDOW;
+    const bool norm = op == QASR_ENC_LN_BF16 || op == QASR_ENC_LN_GELU_BF16 || op == QASR_ENC_LN_GELU_F32;
+    const bool clips = attn || op == QASR_ENC_CONV0 || op == QASR_ENC_CONV_ROWS || op == QASR_ENC_FRAME_INFO;
+    if (clips && (g.n_clips <= 0 || g.n_clips > 4096 || !idx)) return "enc case: n_clips in [1, 4096] and the index array";
+    if (op != QASR_ENC_CONV_ROWS && op != QASR_ENC_FRAME_INFO && !in) return "enc case: the input array is missing";
+    if (attn) {
+        if (g.hd != 32 && g.hd != 64) return "enc case: head_dim must be 32 or 64";
+        if (g.heads <= 0 || g.heads > 64) return "enc case: heads in [1, 64]";
+        if (op == QASR_ENC_MHA && g.hd == 32 && qasr::tuning().mha_form != 0)
+            return "enc case: head_dim 32 has the 16x16x32 form only: set mha_form 0 (the launcher would run it whatever the knob says)";
+        if (idx[0] != 0) return "enc case: cu must start at 0";
+        for (int c = 0; c < g.n_clips; ++c) {
+            if (idx[c + 1] <= idx[c]) return "enc case: cu must increase";
+            if (idx[c + 1] > g.rows) return "enc case: cu runs past rows";
+            if (op == QASR_ENC_MHA && idx[c + 1] - idx[c] > g.max_len) return "enc case: max_len is smaller than a clip";
+            if (op == QASR_ENC_WINDOW && idx[c + 1] - idx[c] > 128) return "enc case: a window is longer than 128 rows";
+        }
+        if (idx[g.n_clips] != g.rows) return "enc case: cu must end at rows";
+        if (op == QASR_ENC_MHA && (g.max_len <= 0 || g.max_len > (1 << 20))) return "enc case: max_len in [1, 2^20]";
+    }
+    if (norm) {
+        if (g.D <= 0 || g.D % 4 || g.D > 2048) return "enc case: the norms take a width that is a multiple of 4 up to 2048";
+        if (!pf || !(g.eps > 0.0f) || !(g.eps < 1.0f)) return "enc case: the norms need gamma | beta and eps in (0, 1)";
+    }
+    if (op == QASR_ENC_CONV0 || op == QASR_ENC_WAVE_STATS) {
+        const int B = op == QASR_ENC_CONV0 ? g.n_clips : g.rows;
+        if (g.n_in <= 0 || !off || !idx || !(g.eps > 0.0f) || !(g.eps < 1.0f)) return "enc case: pcm, pcm_off, the lengths and eps in (0, 1)";
+        if (B > 4096) return "enc case: at most 4096 clips";
+        for (int b = 0; b < B; ++b) {
+            // CONV0 reads the 5 n_out + 5 samples of its frames (kernel 10, stride 5); WAVE_STATS its n samples
+            const long n = op == QASR_ENC_CONV0 ? 5L * idx[g.n_clips + b] + 5 : idx[b];
+            const long cnt = op == QASR_ENC_CONV0 ? idx[g.n_clips + b] : idx[b];
+            if (cnt < 0) return "enc case: a negative length";
+            if (off[b] < 0 || off[b] > g.n_in || (cnt > 0 && off[b] + n > g.n_in)) return "enc case: a pcm offset or range lies outside the pcm array";
+        }
+    }
+    if (op == QASR_ENC_CONV0) {
+        if (g.D <= 0 || g.D > 1024) return "enc case: conv0 takes 1 to 1024 channels";
+        if (!pf || g.max_len <= 0) return "enc case: conv0 needs its parameters and max_out > 0";
+        for (int b = 0; b < g.n_clips; ++b) {
+            const long f0 = idx[b], nf = idx[g.n_clips + b];
+            if (nf > g.max_len) return "enc case: max_out is smaller than a clip's frames";
+            if (f0 < 0 || f0 + nf > g.rows) return "enc case: a clip's frames lie outside the output rows";
+        }
+    }
+    if (op == QASR_ENC_CONV1) {
+        if (g.D <= 0 || g.D % 8 || g.D > 1024) return "enc case: conv1 takes a channel count that is a multiple of 8 up to 1024";
+        if (!pf || !pw || !idx || g.rows <= 0) return "enc case: conv1 needs bias, weights and chunk records";
+        if (g.n_mels <= 0 || g.n_mels > 256 || g.mel_stride <= 0 || g.H1 <= 0 || g.H1 > 256 || g.W1 <= 0 || g.W1 > 256 || g.n_in <= 0)
+            return "enc case: conv1 geometry (n_mels, H1, W1 in [1, 256], mel_stride, n_in > 0)";
+        if ((3L * (2 * g.W1 + 2) + 10L * g.D) * 4 > 64 * 1024) return "enc case: conv1 shared memory above 64 KiB";
+        if ((double)g.rows * g.H1 * g.W1 * g.D > 64.0 * 1024 * 1024) return "enc case: conv1 output above 64 Mi elements";
+        for (int i = 0; i < g.rows; ++i) {
+            const long clip = idx[9 * i], t0 = idx[9 * i + 1], clen = idx[9 * i + 2];
+            if (clip < 0 || t0 < 0 || clen < 0 || clip > 4096) return "enc case: a chunk record is negative";
+            const long cols = clen < 2L * g.W1 + 1 ? clen : 2L * g.W1 + 1;      // columns iw < min(clen, 2 W1 + 1) are read
+            if (t0 + cols > g.mel_stride || ((clip + 1) * g.n_mels - 1) * g.mel_stride + t0 + cols > g.n_in)
+                return "enc case: a chunk record reads outside the mel array";
+        }
+    }
+    if (op == QASR_ENC_ARGMAX && (g.D <= 0 || g.ld < g.D || (double)g.ld * (g.rows + g.in_extra) > 64.0 * 1024 * 1024))
+        return "enc case: argmax needs n > 0, ld >= n and at most 64 Mi elements";
+    if (op == QASR_ENC_CAST && g.rows % 4) return "enc case: the cast takes an element count that is a multiple of 4";
+    if (op == QASR_ENC_CONV_ROWS && (g.stride <= 0 || g.D <= 0)) return "enc case: conv rows need stride and C > 0";
     return nullptr;
 }
 
@@ -287,6 +361,13 @@ int qasr_attn_case_probe(qasr_engine* e, int op, const qasr_attn_case* g, uint16
     if (!e || !g || !qkv || !qn_w || !kn_w || !kcache || !vfrag || !out) return QASR_ERR_INVALID;
     if (const char* why = attn_case_refusal(op, *g, x, W, cu, slot_of_clip, pos, slot, vt, qr)) return fail(e, QASR_ERR_INVALID, why);
     return on_device(e, [&] { e->impl->attn_case_probe(op, *g, qkv, x, W, cu, slot_of_clip, pos, slot, qn_w, kn_w, kcache, vfrag, vt, qr, out); });
+}
+
+int qasr_enc_case_probe(qasr_engine* e, int op, const qasr_enc_case* g, const void* in, const int32_t* idx, const int64_t* off, const float* pf,
+                        const uint16_t* pw, void* out) {
+    if (!e || !g || !out) return QASR_ERR_INVALID;
+    if (const char* why = enc_case_refusal(op, *g, in, idx, off, pf, pw)) return fail(e, QASR_ERR_INVALID, why);
+    return on_device(e, [&] { e->impl->enc_case_probe(op, *g, in, idx, off, pf, pw, out); });
 }
 
 int qasr_transcribe_batch(qasr_engine* e, const float* const* pcm, const size_t* n, size_t B, int sample_rate,

@@ -127,7 +127,8 @@ struct EpiPosConv {
 
 // Full (unmasked) multi-head self-attention over packed clips: qkv bf16 [frames][3D] (q | k | v), clip c = rows
 // [cu[c], cu[c+1]); out bf16 [frames][D].  Online softmax over 64-key tiles, P rounded to bf16 for the P V product
-// (SDPA.multiHead with mask nil, MLXCommon/SDPA.swift:18-37).  head_dim 64 (every Omnilingual variant) or 16 (tests).
+// (SDPA.multiHead with mask nil, MLXCommon/SDPA.swift:18-37).  head_dim 64 (every Omnilingual variant; the form
+// follows the mha_form knob) or 32 (the 16x16x32 form only).
 void mha_attention_launch(const bf16_t* qkv, const int* cu, int n_clips, int max_len, int heads, int head_dim, bf16_t* out,
                           hipStream_t s);
 

@@ -1,5 +1,5 @@
-// enc_kernels.h -- audio-encoder kernels other than the GEMM: conv2d1 (C_in = 1), LayerNorm,
-// block-diagonal window attention.  Reference: Sources/Qwen3ASR/AudioEncoder.swift:362-511.
+// enc_kernels.h -- audio-encoder kernels other than the GEMM: conv2d1 (C_in = 1), block-diagonal window attention (the LayerNorm is
+// layernorm_f32p_launch of ctc_kernels.h).  Reference: Sources/Qwen3ASR/AudioEncoder.swift:362-511.
 #pragma once
 #include "common.h"
 #include "gemm.h"
@@ -23,13 +23,10 @@ void conv1_launch(const float* mel, int mel_stride, int n_mels, const ChunkMeta*
                   const bf16_t* w /*[C][3][3][1]*/, const float* bias, bf16_t* out, int H1, int W1, int C,
                   hipStream_t s);
 
-// ---- LayerNorm over the last dim: x f32 [T][D] -> y bf16 [T][D] (eps, affine bf16 params)
-void layernorm_launch(const float* x, const bf16_t* gamma, const bf16_t* beta, bf16_t* y, int T, int D, float eps,
-                      hipStream_t s);
-
 // ---- window attention: qkv bf16 [T][3D] (q | k | v), windows given by cu_seqlens; out bf16 [T][D].
 // softmax(q k^T / sqrt(hd)) v inside each window (== the additive -1e9 block mask of :337-357).
-// P is rounded to bf16 before the PV product (MFMA operands).  Window length <= 128.
+// P is rounded to bf16 before the PV product (MFMA operands).  Window length <= 128: keys from 128 upward would be IGNORED, the caller
+// refuses longer windows (Engine::run_encoder).
 void window_attention_launch(const bf16_t* qkv, const int* cu_seqlens, int n_windows, int heads, int head_dim,
                              bf16_t* out, hipStream_t s);
 

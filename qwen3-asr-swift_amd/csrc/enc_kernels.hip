@@ -1,4 +1,4 @@
-// enc_kernels.hip -- conv2d1, LayerNorm, window attention (see enc_kernels.h).
+// enc_kernels.hip -- conv2d1, window attention (see enc_kernels.h).
 #include "enc_kernels.h"
 
 namespace qasr {
@@ -76,59 +76,6 @@ void conv1_launch(const float* mel, int mel_stride, int n_mels, const ChunkMeta*
     size_t sh = (3 * (2 * W1 + 2) + 10 * C) * sizeof(float);
     hipLaunchKernelGGL(conv1_kernel, dim3(H1, n_img), dim3(256), sh, s, mel, mel_stride, n_mels, chunks, w, bias, out,
                        H1, W1, C);
-}
-
-// ------------------------------------------------------------------------------------------------
-// LayerNorm: one wavefront per row, two-pass in registers (D <= 64 * 4 * LN_MAXV).
-// ------------------------------------------------------------------------------------------------
-constexpr int LN_MAXV = 5;   // float4 per lane: D <= 1280
-
-__global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const bf16_t* __restrict__ gamma,
-                                                        const bf16_t* __restrict__ beta, bf16_t* __restrict__ y, int T,
-                                                        int D, float eps) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= T) return;
-    const int nv = D / 4;
-    const float4* xr = reinterpret_cast<const float4*>(x + (long)row * D);
-    float4 v[LN_MAXV];
-    float sum = 0.0f;
-#pragma unroll
-    for (int i = 0; i < LN_MAXV; ++i) {
-        int idx = lane + 64 * i;
-        v[i] = idx < nv ? xr[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
-        sum += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-    }
-    const float mean = wave_sum(sum) / (float)D;
-    float sq = 0.0f;
-#pragma unroll
-    for (int i = 0; i < LN_MAXV; ++i) {
-        int idx = lane + 64 * i;
-        if (idx < nv) {
-            float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
-            sq += (a * a + b * b) + (c * c + d * d);
-        }
-    }
-    const float rstd = rsqrtf(wave_sum(sq) / (float)D + eps);
-#pragma unroll
-    for (int i = 0; i < LN_MAXV; ++i) {
-        int idx = lane + 64 * i;
-        if (idx < nv) {
-            float4 g = load_bf16x4(gamma + idx * 4), b = load_bf16x4(beta + idx * 4);
-            float4 o;
-            o.x = (v[i].x - mean) * rstd * g.x + b.x;
-            o.y = (v[i].y - mean) * rstd * g.y + b.y;
-            o.z = (v[i].z - mean) * rstd * g.z + b.z;
-            o.w = (v[i].w - mean) * rstd * g.w + b.w;
-            *reinterpret_cast<uint2*>(y + (long)row * D + idx * 4) = pack_bf16x4(o);
-        }
-    }
-}
-
-void layernorm_launch(const float* x, const bf16_t* gamma, const bf16_t* beta, bf16_t* y, int T, int D, float eps,
-                      hipStream_t s) {
-    if (T <= 0) return;
-    if (D % 4 != 0 || D > 256 * LN_MAXV) throw std::invalid_argument("layernorm: unsupported width");
-    hipLaunchKernelGGL(layernorm_kernel, dim3(cdiv(T, 4)), dim3(256), 0, s, x, gamma, beta, y, T, D, eps);
 }
 
 // ------------------------------------------------------------------------------------------------

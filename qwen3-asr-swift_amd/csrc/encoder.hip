@@ -230,6 +230,12 @@ void Engine::run_encoder() {
     if (n_tok_ == 0) return;
     const int D = cfg_.enc_d_model, C = cfg_.conv_channels, F = cfg_.enc_ffn, K9 = 9 * C;
     hipStream_t s = stream_;
+    const int hd = D / cfg_.enc_heads;
+    // window_attention_kernel holds a whole window in registers and ignores keys from 128 upward: refuse before anything is launched
+    const bool mha_windows = hd == 64 && tuning().enc_attn != 0;
+    if (!mha_windows && max_win_ > 128)
+        throw std::invalid_argument("encoder: an attention window of " + std::to_string(max_win_) +
+                                    " tokens exceeds the 128 of the window kernel (head_dim 32 or enc_attn = 0)");
     bf16_t *c1 = d_c1_.as<bf16_t>(), *c2 = d_c2_.as<bf16_t>(), *c3 = d_c3_.as<bf16_t>();
     bf16_t *h = d_ench_.as<bf16_t>(), *qkv = d_encqkv_.as<bf16_t>(), *at = d_enca_.as<bf16_t>();
     bf16_t* mid = d_encmid_.as<bf16_t>();
@@ -253,12 +259,11 @@ void Engine::run_encoder() {
         EpiPosF32 e{x, D, d_pe_.as<float>(), d_tok_t_};
         gemm_nt(a, encw_.conv_out, (long)H3_ * C, n_tok_, D, H3_ * C, e, s);
     }
-    const int hd = D / cfg_.enc_heads;
     for (const EncLayerW& L : encw_.layers) {
         layernorm_f32p_launch(x, L.ln1_g, L.ln1_b, h, n_tok_, D, cfg_.ln_eps, 0, s);
         gemm_nt(ADense{h, D, n_tok_, D}, L.wqkv, D, n_tok_, 3 * D, D, EpiBiasActBf16F<0>{qkv, 3L * D, L.bqkv}, s);
         // head_dim 64 (both published sizes): the transposed-score 32x32x16 kernel of the wav2vec2 path, a window = a "clip"
-        if (hd == 64 && tuning().enc_attn != 0) mha_attention_launch(qkv, d_cu_win_, n_win_, max_win_, cfg_.enc_heads, hd, at, s);
+        if (mha_windows) mha_attention_launch(qkv, d_cu_win_, n_win_, max_win_, cfg_.enc_heads, hd, at, s);
         else window_attention_launch(qkv, d_cu_win_, n_win_, cfg_.enc_heads, hd, at, s);
         gemm_nt(ADense{at, D, n_tok_, D}, L.wo, D, n_tok_, D, D, EpiResidF32F{x, D, L.bo}, s);
         layernorm_f32p_launch(x, L.ln2_g, L.ln2_b, h, n_tok_, D, cfg_.ln_eps, 0, s);

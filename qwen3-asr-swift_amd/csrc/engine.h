@@ -116,6 +116,9 @@ public:
     void attn_case_probe(int op, const qasr_attn_case& g, uint16_t* qkv, const uint16_t* x, const uint16_t* W, const int32_t* cu,
                          const int32_t* slot_of_clip, const int32_t* pos, const int32_t* slot, const uint16_t* qn_w, const uint16_t* kn_w,
                          uint16_t* kcache, uint16_t* vfrag, const uint16_t* vt, uint16_t* qr, uint16_t* out);
+    // qasr_enc_case_probe (csrc/enc_cases.hip): one launch of an encoder-side kernel that is not the GEMM, on host data
+    void enc_case_probe(int op, const qasr_enc_case& g, const void* in, const int32_t* idx, const int64_t* off, const float* pf,
+                        const uint16_t* pw, void* out);
     void kernel_probe(int which, int reps, float* avg_ms, double* bytes_per_launch);
     int batch_size() const { return batch_; }
     void decode_structure(int* fused_qa, int* chain, int* launches_per_layer);

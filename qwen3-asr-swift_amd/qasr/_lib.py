@@ -153,6 +153,11 @@ class QasrAttnCase(C.Structure):
                [("eps", C.c_float), ("rope_theta", C.c_float)]
 
 
+class QasrEncCase(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("rows", "n_clips", "in_extra", "out_extra", "heads", "hd", "max_len", "D", "ld", "n_in", "n_mels",
+                                         "mel_stride", "H1", "W1", "stride")] + [("eps", C.c_float)]
+
+
 _P = C.POINTER
 _F = _P(C.c_float)
 _I = _P(C.c_int32)
@@ -193,6 +198,7 @@ SIGNATURES = {
     "qasr_gemm_case_probe": (C.c_int, [_E, C.c_int, C.c_int, _P(QasrGemmCase), _P(C.c_uint16), _P(C.c_uint16), C.c_void_p, _I, _P(C.c_int64),
                                        _F, C.c_void_p]),
     "qasr_attn_case_probe": (C.c_int, [_E, C.c_int, _P(QasrAttnCase)] + [_P(C.c_uint16)] * 3 + [_I] * 4 + [_P(C.c_uint16)] * 7),
+    "qasr_enc_case_probe": (C.c_int, [_E, C.c_int, _P(QasrEncCase), C.c_void_p, _I, _P(C.c_int64), _F, _P(C.c_uint16), C.c_void_p]),
     "qasr_set_shared_device": (C.c_int, [_E, C.c_int]),
     "qasr_decode_structure": (C.c_int, [_E, _P(C.c_int), _P(C.c_int), _P(C.c_int)]),
     "qasr_set_tuning": (C.c_int, [C.c_char_p, C.c_int]),
