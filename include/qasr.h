@@ -937,6 +937,60 @@ int qasr_xvec_embed_mel(qasr_xvec* x, const float* mel, size_t T, float* out);
 /* ms[6]: device time of the last call, HIP events on the work stream: front end, initial conv, blocks 1..3, MFA + pooling + fc */
 int qasr_xvec_timing(const qasr_xvec* x, float* ms);
 
+/* ---- CosyVoice3 HiFT vocoder (csrc/voc_cosyvoice.hip, csrc/api_voc.cpp) ----------------------------------------------------------------
+ * Reference: Sources/CosyVoiceTTS/HiFiGAN.swift.  80-bin mel frames (20 ms each) -> 24 kHz mono PCM, what HiFiGANGenerator.decode(mel:)
+ * computes for CosyVoiceTTS.  What each entry replaces:
+ *   CosyVoiceWeightLoader.loadHiFiGAN (WeightLoading.swift:214-331), local directory           -> qasr_hift_create
+ *   F0Predictor.callAsFunction (HiFiGAN.swift:361-373)                                           -> qasr_hift_f0
+ *   interpolateF0 + SourceModuleHnNSF.callAsFunction (:383-395, :253-289, :323-328)              -> qasr_hift_source
+ *   stft, conv_pre, the three stages, conv_post, istft, clip (:777-857) on a given source       -> qasr_hift_decode_source
+ *   HiFiGANGenerator.decode(mel:) (:755-868)                                                     -> qasr_hift_decode / _decode_batch
+ * A clip of T >= 1 frames gives 480 T source samples, 120 T + 1 STFT frames (n_fft 16, hop 4, periodic Hann, reflect padding 8) and
+ * 480 T + 16 PCM samples: the inverse STFT's centre padding is not trimmed (:566-568).  Snake is x + 1 / (alpha + 1e-9) sin^2(alpha x)
+ * with alpha as stored; the phase channels of conv_post go through sin, the last LeakyReLU has slope 0.01 (:838-849).
+ * Noise.  MLX's random stream cannot be restated; the distribution and the three places noise enters are the reference's, the
+ * generator is this library's: draw c of a clip is splitmix64(seed + (c + 1) 0x9e3779b97f4a7c15) (the counter form of the sampler's
+ * generator); with r the draw, u1 = ((r >> 40) + 1) 2^-24, u2 = ((r >> 16) & 0xFFFFFF) 2^-24, uniform = u2, normal = sqrt(-2 ln u1)
+ * cos(2 pi u2).  Counter h = 0 .. 8: initPhase of harmonic h + 1 = 2 pi uniform; counter 16 + 10 n + h: the unvoiced noise of sample n,
+ * harmonic h + 1; counter 16 + 10 n + 9: the noise added to sample n after the merge.
+ * Precision: f32 throughout; the source's running phase is kept in cycles in f64 and reduced mod 1 before the sine.  A clip's output
+ * is bit-identical alone, in any batch and place, under any split into passes, and run to run; qasr_hift_decode is bit-identical to
+ * the three stage entries chained.  One object, one thread at a time.  Not covered: the LLM, the flow model,
+ * CAM++, the speech tokenizer, chunked / streaming vocoding. */
+typedef struct qasr_hift qasr_hift;
+/* model_dir/hifigan.safetensors: conv_pre, ups.{0..2}, source_downs.{0..2}, conv_post, f0_predictor.condnet.{0,2,4,6,8} (.weight
+ * [out][k][in] as stored, .bias), f0_predictor.classifier and m_source.l_linear (.weight [out][in], .bias), and for resblocks.{0..8}
+ * (3 stage + kernel) and source_resblocks.{0..2}: convs1.{0..2}, convs2.{0..2}, activations1.{0..2}.alpha, activations2.{0..2}.alpha;
+ * F32, F16 or BF16, widened at upload.  The file's beta, up_activations.* and final_activation.* are not read, as in the reference.
+ * Everything is checked before any HIP call: a missing file or key -> QASR_ERR_IO, a wrong shape or dtype -> QASR_ERR_INVALID, the
+ * key named in qasr_hift_last_error(NULL).  max_frames: mel frames one device pass holds (0 = 4096, about 82 s; at most 2^17); every
+ * buffer is sized from it at create: about 160 KB of device memory per frame (five activation buffers of 120 x 64 f32, the source,
+ * its STFT, the PCM) plus 0.1 GB that does not depend on it, so 0.75 GB at the default.  order_with: as for qasr_seg_create. */
+int qasr_hift_create(int device, const char* model_dir, size_t max_frames, qasr_engine* order_with, qasr_hift** out);
+void qasr_hift_destroy(qasr_hift* h);
+const char* qasr_hift_last_error(const qasr_hift* h);               /* h may be NULL: last create() failure */
+int qasr_hift_is_loaded(const qasr_hift* h);
+int qasr_hift_unload(qasr_hift* h);                                 /* later device calls return QASR_ERR_NOT_LOADED */
+size_t qasr_hift_memory_footprint(const qasr_hift* h);              /* bytes as stored of the tensors read, 0 unloaded */
+int qasr_hift_sample_rate(void);                                    /* 24000 */
+size_t qasr_hift_num_samples(size_t T);                             /* 480 T + 16, 0 for 0.  Pure CPU. */
+/* The noise stream on the host, the twin of the device code (the same lines, csrc/voc_cosyvoice.h): for draw counters[i] of the stream
+ * `seed`, uniform[i] = u2 and normal[i] = sqrt(-2 ln u1) cos(2 pi u2) in f32; either output may be NULL.  Pure CPU. */
+int qasr_hift_noise(uint64_t seed, const uint64_t* counters, size_t n, float* uniform, float* normal);
+/* Stage entries.  mel [T][80], f0 [T] (Hz, >= 0), src [480 T], pcm [480 T + 16].  T == 0, T > max_frames or NULL -> QASR_ERR_INVALID;
+ * after qasr_hift_unload every argument gives QASR_ERR_NOT_LOADED. */
+int qasr_hift_f0(qasr_hift* h, const float* mel, size_t T, float* f0);
+int qasr_hift_source(qasr_hift* h, const float* f0, size_t T, uint64_t seed, float* src);
+int qasr_hift_decode_source(qasr_hift* h, const float* mel, size_t T, const float* src, float* pcm);
+/* the whole generator: bit-identical to qasr_hift_decode_source(mel, qasr_hift_source(qasr_hift_f0(mel), seed)) */
+int qasr_hift_decode(qasr_hift* h, const float* mel, size_t T, uint64_t seed, float* pcm);
+/* B clips of any lengths, cut into passes of at most max_frames frames at clip boundaries; pcm[b] [480 T[b] + 16] is bit-identical to
+ * qasr_hift_decode of that clip with seeds[b] */
+int qasr_hift_decode_batch(qasr_hift* h, const float* const* mel, const size_t* T, const uint64_t* seeds, size_t B, float* const* pcm);
+/* ms[7]: device time of the last call, HIP events on the work stream: F0 predictor, source, STFT, conv_pre, stage 0, stage 1, stage 2 +
+ * conv_post + inverse STFT; a stage the entry does not run is 0 */
+int qasr_hift_timing(const qasr_hift* h, float* ms);
+
 /* ---- Qwen3-TTS Talker + code predictor (Sources/Qwen3TTS/Talker.swift, CodePredictor.swift, Sampling.swift, Qwen3TTS.swift) -------------
  * Text ids (the chat template of prepareTextTokens around them), a language id, optionally a speaker token id or an x-vector (qasr_xvec_*)
  * and an instruct prefix -> 16 code streams at 12.5 Hz, which qasr_codec_decode turns into 24 kHz audio.  MLX affine 4 / 8 bit

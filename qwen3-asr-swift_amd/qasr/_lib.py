@@ -380,6 +380,21 @@ SIGNATURES = {
     "qasr_xvec_mel": (C.c_int, [_E, _P(_F), _P(C.c_size_t), C.c_size_t, _P(_F)]),
     "qasr_xvec_embed_mel": (C.c_int, [_E, _F, C.c_size_t, _F]),
     "qasr_xvec_timing": (C.c_int, [_E, _F]),
+    "qasr_hift_create": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t, _E, _P(_E)]),
+    "qasr_hift_destroy": (None, [_E]),
+    "qasr_hift_last_error": (C.c_char_p, [_E]),
+    "qasr_hift_is_loaded": (C.c_int, [_E]),
+    "qasr_hift_unload": (C.c_int, [_E]),
+    "qasr_hift_memory_footprint": (C.c_size_t, [_E]),
+    "qasr_hift_sample_rate": (C.c_int, []),
+    "qasr_hift_num_samples": (C.c_size_t, [C.c_size_t]),
+    "qasr_hift_noise": (C.c_int, [C.c_uint64, _P(C.c_uint64), C.c_size_t, _F, _F]),
+    "qasr_hift_f0": (C.c_int, [_E, _F, C.c_size_t, _F]),
+    "qasr_hift_source": (C.c_int, [_E, _F, C.c_size_t, C.c_uint64, _F]),
+    "qasr_hift_decode_source": (C.c_int, [_E, _F, C.c_size_t, _F, _F]),
+    "qasr_hift_decode": (C.c_int, [_E, _F, C.c_size_t, C.c_uint64, _F]),
+    "qasr_hift_decode_batch": (C.c_int, [_E, _P(_F), _P(C.c_size_t), _P(C.c_uint64), C.c_size_t, _P(_F)]),
+    "qasr_hift_timing": (C.c_int, [_E, _F]),
     "qasr_tts_default_config": (C.c_int, [C.c_char_p, C.c_int, _P(QasrTtsConfig)]),
     "qasr_tts_default_sampling": (None, [C.c_int, _P(QasrTtsSampling)]),
     "qasr_tts_poll_interval": (C.c_int, []),

@@ -255,7 +255,7 @@ def write_silero_safetensors(sd: dict, model_dir: str, dtype: str = "F32", drop=
     return _write_safetensors(sd, model_dir, dtype, drop, reshape)
 
 
-def _write_safetensors(sd: dict, model_dir: str, dtype: str = "F32", drop=(), reshape=None) -> str:
+def _write_safetensors(sd: dict, model_dir: str, dtype: str = "F32", drop=(), reshape=None, filename: str = "model.safetensors") -> str:
     import json
     import os
     os.makedirs(model_dir, exist_ok=True)
@@ -282,7 +282,7 @@ def _write_safetensors(sd: dict, model_dir: str, dtype: str = "F32", drop=(), re
         off += len(raw)
     h = json.dumps(header).encode()
     h += b" " * ((8 - len(h) % 8) % 8)
-    path = os.path.join(model_dir, "model.safetensors")
+    path = os.path.join(model_dir, filename)
     with open(path, "wb") as f:
         f.write(len(h).to_bytes(8, "little"))
         f.write(h)
@@ -757,6 +757,102 @@ def write_tts_speaker_encoder_safetensors(sd: dict, model_dir: str, dtype: str =
     for k, v in (extra.items() if isinstance(extra, dict) else extra):
         d[k] = np.asarray(v, dtype=np.float32)
     _write_safetensors(d, model_dir, dtype, drop, reshape)
+    return model_dir
+
+
+# ---- CosyVoice3 HiFT vocoder (qasr_hift_*) ----------------------------------------------------------------------------------------
+HIFT_CH, HIFT_UP_K, HIFT_DOWN_K, HIFT_SRC_K, HIFT_RES_K = (512, 256, 128, 64), (16, 11, 7), (30, 6, 1), (7, 7, 11), (3, 7, 11)
+
+
+def cosyvoice_hifigan_tensor_shapes(ignored: bool = True) -> dict:
+    """key -> shape of every tensor of hifigan.safetensors (HiFiGAN.swift:656-749, WeightLoading.swift:214-331; conv weights [out, k, in]
+    as the file stores them).  ignored: with the keys the file holds and the reference never loads (every Snake's beta,
+    up_activations.*, final_activation.*)."""
+    s = {}
+
+    def conv(k, out, taps, cin):
+        s[k + ".weight"], s[k + ".bias"] = (out, taps, cin), (out,)
+
+    def resblock(p, C, k):
+        for d in range(3):
+            conv(f"{p}.convs1.{d}", C, k, C)
+            conv(f"{p}.convs2.{d}", C, k, C)
+            for a in ("activations1", "activations2"):
+                s[f"{p}.{a}.{d}.alpha"] = (C,)
+                if ignored:
+                    s[f"{p}.{a}.{d}.beta"] = (C,)
+
+    for i in range(5):
+        conv(f"f0_predictor.condnet.{2 * i}", 512, 4 if i == 0 else 3, 80 if i == 0 else 512)
+    s["f0_predictor.classifier.weight"], s["f0_predictor.classifier.bias"] = (1, 512), (1,)
+    s["m_source.l_linear.weight"], s["m_source.l_linear.bias"] = (1, 9), (1,)
+    conv("conv_pre", 512, 5, 80)
+    for i in range(3):
+        C = HIFT_CH[i + 1]
+        conv(f"ups.{i}", C, HIFT_UP_K[i], HIFT_CH[i])
+        conv(f"source_downs.{i}", C, HIFT_DOWN_K[i], 18)
+        resblock(f"source_resblocks.{i}", C, HIFT_SRC_K[i])
+        for j in range(3):
+            resblock(f"resblocks.{3 * i + j}", C, HIFT_RES_K[j])
+        if ignored:
+            s[f"up_activations.{i}.alpha"], s[f"up_activations.{i}.beta"] = (HIFT_CH[i],), (HIFT_CH[i],)
+    conv("conv_post", 18, 7, 64)
+    if ignored:
+        s["final_activation.alpha"], s["final_activation.beta"] = (64,), (64,)
+    return s
+
+
+def synth_cosyvoice_hifigan_state_dict(seed: int = 0) -> dict:
+    """Seeded HiFT weights {key: float32 array} on the real geometry (21 M parameters).  Every conv is N(0, gain^2 / fan_in): 1.2 in the
+    F0 stack (ELU), 0.55 for the two convs that read the mel (its rms is about 1.8), 1.3 for the upsample convs (LeakyReLU), 0.5 inside
+    the residual blocks so that three of them in a row leave the signal O(1); Snake alphas are log-normal around 1 (0.5 .. 2).  The
+    classifier (deviation about 100 Hz around a bias of 24 Hz, folded by the abs) spreads F0 over roughly 0 .. 400 Hz with about one
+    frame in ten under the 10 Hz voicing threshold, so that every test clip of 8 frames or more holds voiced and unvoiced frames; the merge
+    weights give a voiced source of amplitude about 0.5; conv_post's outputs stay within +-4 and its magnitude half carries a bias
+    of -1.2, so the waveform peaks well above 0.05 and rarely reaches the +-0.99 clamp (tests/test_hift_cpu.py asserts all four).
+    The keys the reference ignores hold 1e3: a loader that read them would not go unnoticed."""
+    rng = np.random.default_rng(44021 + seed)
+    sd = {}
+    for key, shape in cosyvoice_hifigan_tensor_shapes().items():
+        if key.endswith(".beta") or key.startswith("up_activations.") or key.startswith("final_activation."):
+            sd[key] = np.full(shape, 1e3)
+        elif key.endswith(".alpha"):
+            sd[key] = np.exp(0.3 * rng.standard_normal(shape))
+        elif key == "f0_predictor.classifier.weight":
+            sd[key] = 160.0 * rng.standard_normal(shape) / math.sqrt(512)
+        elif key == "f0_predictor.classifier.bias":
+            sd[key] = np.full(shape, 24.0)
+        elif key == "m_source.l_linear.weight":
+            sd[key] = 3.0 * rng.standard_normal(shape)
+        elif key == "conv_post.bias":
+            sd[key] = np.concatenate([np.full(9, -1.2), 0.05 * rng.standard_normal(9)])
+        elif key.endswith(".bias"):
+            sd[key] = 0.05 * rng.standard_normal(shape)
+        else:
+            fan = shape[1] * shape[2]
+            if key.startswith("f0_predictor.condnet.0") or key.startswith("conv_pre"):
+                gain = 0.55
+            elif key.startswith("f0_predictor."):
+                gain = 1.2
+            elif key.startswith("ups."):
+                gain = 1.3
+            elif key.startswith("source_downs."):
+                gain = 1.0
+            elif key.startswith("conv_post"):
+                gain = 0.4
+            else:
+                gain = 0.5
+            sd[key] = gain * rng.standard_normal(shape) / math.sqrt(fan)
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in sd.items()}
+
+
+def write_cosyvoice_hifigan_safetensors(sd: dict, model_dir: str, dtype: str = "F32", drop=(), reshape=None, extra=()) -> str:
+    """Writes `sd` as model_dir/hifigan.safetensors (dtype F32 | F16 | BF16; F64 for the dtype error).  `drop`: keys left out,
+    `reshape`: {key: shape} written with a wrong shape, `extra`: (key, array) pairs added as they are.  Returns model_dir."""
+    d = dict(sd)
+    for k, v in (extra.items() if isinstance(extra, dict) else extra):
+        d[k] = np.asarray(v, dtype=np.float32)
+    _write_safetensors(d, model_dir, dtype, drop, reshape, filename="hifigan.safetensors")
     return model_dir
 
 
