@@ -332,6 +332,59 @@ typedef struct qasr_enc_case {
 int qasr_enc_case_probe(qasr_engine* e, int op, const qasr_enc_case* g, const void* in, const int32_t* idx, const int64_t* off,
                         const float* pf, const uint16_t* pw, void* out);
 
+/* Diagnostic: the kernels that stream the weights of a decode step, by themselves, on host data; needs no weights.  Nothing is restated: the
+ * probe uploads, repacks the weight with the product's packer (pack_mfma_a_launch / quant_pack_launch) unless `generic` is set, calls the
+ * product's launch entry ONCE (csrc/dec_kernels.h, csrc/dec_quant.h, csrc/dec_gemv_wide.h) and downloads.
+ *   GEMV           X bf16 [B + in_extra][K], W bf16 [N][K] row-major, norm_w bf16 [K] or NULL (the fused RMSNorm prologue).  The dispatch of a
+ *                  float checkpoint's decode-step linear: decode_gemv_wide_launch at K = 6144 under the gemv_wide knob, else
+ *                  decode_gemv_fused_launch.  epi BF16 / RESID: out bf16 [B + out_extra][N] (RESID reads it); SWIGLU: out [..][N / 2], weight
+ *                  rows in blocks of 16 gate + 16 up; LOGITS: logits f32 [B + out_extra][N] and the argmax partials.
+ *   GEMVQ          the same on an MLX affine-quantised matrix: W = uint32 [N][K * bits / 32], scales / biases [N][K / 64] bf16 (sb_f32 0) or
+ *                  f32 (1).  decode_gemv_q_launch; epi BF16 / RESID / SWIGLU.
+ *   LMHEAD         lm_head_launch: final RMSNorm (norm_w required) + tied head on W bf16 [N][K] -> logits f32 [B + out_extra][N], partials.
+ *   LMHEADQ        lm_head_q_launch on a quantised table.
+ *   RMSNORM_ROWS   rmsnorm_rows_launch: X [B + in_extra][K], norm_w -> out bf16 [B + out_extra][K].
+ *   FINALIZE       greedy_finalize_launch on given partials part_val / part_idx [B][n_parts] (n_parts is an INPUT here) and a given state.  With
+ *                  R = B + out_extra: state int32 = tokens [R][max_new + 1] | lens [R] | finished [R] | ctx_len [R] | n_active [1] | err [1] |
+ *                  clear [clear_words + 33] (absent at clear_words 0: the word 32 behind the cleared ones is the step sequence word);
+ *                  rope f32 = cos [n_rope][half] | sin [n_rope][half]; rope_rows f32 = cos_rows [R][half] | sin_rows [R][half]; the embedding
+ *                  table W = bf16 [N][K] (bits 0) or a quantised triplet (N = vocab, K = hidden) -> out bf16 [R][K] = the next input rows.
+ *                  state, rope_rows and out are uploaded before and downloaded after the launch: everything it may write comes back.
+ *   EMBED          epi 0: embed_splice_launch / embed_splice_q_launch, state = ids [B] | audio_src [B], X = audio rows bf16 [n_audio][K];
+ *                  epi 1: gather_rows_launch / gather_rows_q_launch, state = row ids [B]; epi 2: quant_dequant_rows_launch of rows
+ *                  [r0, r0 + B).  W as for FINALIZE -> out bf16 [B + out_extra][K].
+ * out, logits and the partials are uploaded before the launch and downloaded after it, so an untouched byte comes back as it went in.
+ * part_val / part_idx hold part_cap elements each; the launch writes [B][n_parts] at their start.  On return g->n_parts = partials per row
+ * (0 without an argmax) and g->route = 1 where a tuned instantiation ran, 0 for the generic kernel (-1: RMSNORM_ROWS, FINALIZE, EMBED).  Knobs: qasr_set_tuning.
+ * Refused with QASR_ERR_INVALID before anything is launched: B outside 1 .. 64, N that is no multiple of the epilogue's row tile (16; SWIGLU
+ * 32), K % 32 != 0 (bf16) or K % 64 != 0 (quantised; % 128 unless generic: the packer's block), K above 8192, a norm above K = 2048, bits
+ * other than 4 / 8, an epilogue the launch does not have (GEMVQ LOGITS), an LM-head B above lm_head_rows, a persistent LM head with fewer
+ * than 8 tiles per workgroup of its grid, part_cap below B * n_parts, a missing array, more than 2^28 weight elements; FINALIZE / EMBED: a
+ * hidden size that is no multiple of 8 (quantised: 64), a row id, audio row or dequantised row range outside its table, lens outside
+ * [0, max_new], a context length whose next position lies outside the rope table, half above 256, n_parts outside [1, 4096], part_cap
+ * below B * n_parts, n_audio outside [0, 65536].  A partial
+ * INDEX outside the vocabulary is not refused: the kernel clamps it and sets err.
+ * tests/test_gpu_dec_cases.py. */
+enum { QASR_DEC_GEMV = 0, QASR_DEC_GEMVQ = 1, QASR_DEC_LMHEAD = 2, QASR_DEC_LMHEADQ = 3, QASR_DEC_RMSNORM_ROWS = 4, QASR_DEC_FINALIZE = 5,
+       QASR_DEC_EMBED = 6 };
+enum { QASR_DEC_EPI_BF16 = 0, QASR_DEC_EPI_RESID = 1, QASR_DEC_EPI_SWIGLU = 2, QASR_DEC_EPI_LOGITS = 3 };
+typedef struct qasr_dec_case {
+    int32_t B, N, K;                  /* batch rows, weight rows, reduction length */
+    int32_t epi;                      /* GEMV / GEMVQ: QASR_DEC_EPI_*; else 0 */
+    int32_t generic;                  /* 1: no packed image is handed to the launch, so its generic kernel runs */
+    int32_t bits, sb_f32;             /* quantised forms */
+    int32_t in_extra, out_extra;      /* rows allocated beyond B in X / in out and logits */
+    int32_t part_cap;                 /* elements of part_val and of part_idx */
+    float eps;
+    int32_t n_parts, route;           /* written by the probe (FINALIZE: n_parts is given) */
+    int32_t max_new, max_tokens, eos, ignore_eos, advance_ctx, clear_words;   /* FINALIZE: GreedyState and the launch's flag */
+    int32_t n_rope, half;             /* FINALIZE: rows and width of the rope tables */
+    int32_t n_audio, r0;              /* EMBED: audio rows in X; first row of epi 2 */
+} qasr_dec_case;
+int qasr_dec_case_probe(qasr_engine* e, int op, qasr_dec_case* g, const uint16_t* X, const void* W, const void* scales, const void* biases,
+                        const uint16_t* norm_w, uint16_t* out, float* logits, float* part_val, int32_t* part_idx, int32_t* state,
+                        const float* rope, float* rope_rows);
+
 /* ---- utterance-batch data parallelism inside one process ----------------------------------------------------------------------
  * Replaces the sequential file loop of `speech transcribe-batch` (Sources/AudioCLILib/TranscribeBatchCommand.swift:82-93) for a caller
  * that owns several GPUs: one engine (= one HIP device + one stream, weights replicated) and one host thread per listed device; clips

@@ -192,6 +192,94 @@ static const char* enc_case_refusal(int op, const qasr_enc_case& g, const void* 
     return nullptr;
 }
 
+// qasr_dec_case_probe: why the arguments are refused, or null.  Everything a launch would index with is checked here, on the host.
+static const char* dec_case_refusal(int op, const qasr_dec_case& g, const uint16_t* X, const void* W, const void* scales, const void* biases,
+                                    const uint16_t* norm_w, const uint16_t* out, const float* logits, const float* part_val,
+                                    const int32_t* part_idx, const int32_t* state, const float* rope, const float* rope_rows) {
+    if (op < QASR_DEC_GEMV || op > QASR_DEC_EMBED) return "dec case: unknown operation";
+    if (op == QASR_DEC_FINALIZE || op == QASR_DEC_EMBED) {
+        if (g.B < 1 || g.B > 64 || g.out_extra < 0 || g.out_extra > 64) return "dec case: B must be in [1, 64], out_extra in [0, 64]";
+        if (!W || !out || !state) return "dec case: the table, out and the int32 array are missing";
+        if (g.N <= 0 || g.K <= 0 || g.K % 8 || g.K > 8192 || (double)g.N * g.K > 268435456.0) return "dec case: table rows > 0, hidden a multiple of 8 up to 8192";
+        if (g.bits != 0) {
+            if (g.bits != 4 && g.bits != 8) return "dec case: bits must be 0 (bf16 table), 4 or 8";
+            if (g.sb_f32 != 0 && g.sb_f32 != 1) return "dec case: sb_f32 must be 0 or 1";
+            if (g.K % 64 || !scales || !biases) return "dec case: a quantised table needs hidden % 64 == 0, scales and biases";
+        }
+        const int R = g.B + g.out_extra;
+        if (op == QASR_DEC_EMBED) {
+            if (g.epi < 0 || g.epi > 2) return "dec case: EMBED epi 0 splice, 1 gather, 2 dequantise rows";
+            if (g.n_audio < 0 || g.n_audio > 65536) return "dec case: n_audio in [0, 65536]";
+            if (g.epi == 2) {
+                if (!g.bits) return "dec case: dequantised rows need a quantised table";
+                return g.r0 < 0 || (long)g.r0 + g.B > g.N ? "dec case: the dequantised rows lie outside the table" : nullptr;
+            }
+            for (int p = 0; p < g.B; ++p) {
+                const int a = g.epi == 0 ? state[g.B + p] : -1;
+                if (a >= 0 && (!X || a >= g.n_audio)) return "dec case: an audio row outside the audio rows";
+                if (a < 0 && (state[p] < 0 || state[p] >= g.N)) return "dec case: a row id outside the table";
+            }
+            return nullptr;
+        }
+        if (!part_val || !part_idx || !rope || !rope_rows) return "dec case: partials and rope arrays are missing";
+        if (g.n_parts < 1 || g.n_parts > 4096) return "dec case: n_parts in [1, 4096]";
+        if ((long)g.part_cap < (long)g.B * g.n_parts) return "dec case: part_cap is below B * n_parts";
+        if (g.max_new < 1 || g.max_new > 4096 || g.clear_words < 0 || g.clear_words > 4096) return "dec case: max_new in [1, 4096], clear_words in [0, 4096]";
+        if (g.half < 1 || g.half > 256 || g.n_rope < 1 || g.n_rope > 65536) return "dec case: half in [1, 256], n_rope in [1, 65536]";
+        if (g.advance_ctx != 0 && g.advance_ctx != 1) return "dec case: advance_ctx must be 0 or 1";
+        const int32_t* lens = state + (long)R * (g.max_new + 1);
+        for (int b = 0; b < g.B; ++b) {
+            if (lens[b] < 0 || lens[b] > g.max_new) return "dec case: a row's length outside [0, max_new]";
+            const long next = (long)lens[2 * R + b] + g.advance_ctx;
+            if (lens[2 * R + b] < 0 || next >= g.n_rope) return "dec case: a row's next position lies outside the rope table";
+        }
+        return nullptr;
+    }
+    const bool quant = op == QASR_DEC_GEMVQ || op == QASR_DEC_LMHEADQ, head = op == QASR_DEC_LMHEAD || op == QASR_DEC_LMHEADQ;
+    const bool gemv = op == QASR_DEC_GEMV || op == QASR_DEC_GEMVQ;
+    if (g.B < 1 || g.B > 64) return "dec case: B must be in [1, 64]";
+    if (g.in_extra < 0 || g.in_extra > 64 || g.out_extra < 0 || g.out_extra > 64) return "dec case: in_extra / out_extra in [0, 64]";
+    if (!X) return "dec case: the activation rows are missing";
+    if (g.K <= 0 || g.K > 8192) return "dec case: K in [1, 8192]";
+    if (!(g.eps > 0.0f) || !(g.eps < 1.0f)) return "dec case: eps in (0, 1)";
+    if (op == QASR_DEC_RMSNORM_ROWS) {
+        if (g.K % 8 || g.K > 2048) return "dec case: rmsnorm rows take a width that is a multiple of 8 up to 2048";
+        if (!norm_w || !out) return "dec case: rmsnorm rows need the weight and out";
+        if (g.epi != 0) return "dec case: rmsnorm rows have no epilogue";
+        return nullptr;
+    }
+    if (!W) return "dec case: the weight is missing";
+    if (g.generic != 0 && g.generic != 1) return "dec case: generic must be 0 or 1";
+    if (g.N <= 0 || (double)g.N * g.K > 268435456.0) return "dec case: N > 0 and at most 2^28 weight elements";
+    if (quant) {
+        if (g.bits != 4 && g.bits != 8) return "dec case: bits must be 4 or 8";
+        if (g.sb_f32 != 0 && g.sb_f32 != 1) return "dec case: sb_f32 must be 0 or 1";
+        if (g.K % 64) return "dec case: a quantised K must be a multiple of the group size 64";
+        if (!g.generic && g.K % 128) return "dec case: the packed quantised image needs K % 128 == 0 (set generic)";
+        if (!scales || !biases) return "dec case: scales / biases are missing";
+    } else if (g.K % 32) return "dec case: K must be a multiple of 32";
+    if (norm_w && (g.K % 8 || g.K > 2048)) return "dec case: the norm takes K up to 2048";
+    const int epi = head ? QASR_DEC_EPI_LOGITS : g.epi;
+    if (gemv && (g.epi < QASR_DEC_EPI_BF16 || g.epi > QASR_DEC_EPI_LOGITS)) return "dec case: unknown epilogue";
+    if (head && g.epi != 0) return "dec case: the LM heads have no epilogue choice";
+    if (op == QASR_DEC_GEMVQ && epi == QASR_DEC_EPI_LOGITS) return "dec case: the quantised linear has no LOGITS epilogue (LMHEADQ is the head)";
+    if (g.N % (epi == QASR_DEC_EPI_SWIGLU ? 32 : 16)) return "dec case: N must be a multiple of the epilogue's row tile (16; SWIGLU 32)";
+    if (epi != QASR_DEC_EPI_LOGITS) return out ? nullptr : "dec case: out is missing";
+    if (!logits || !part_val || !part_idx) return "dec case: logits and the partial arrays are missing";
+    int parts;
+    if (head) {
+        if (!norm_w) return "dec case: the LM heads need the final norm's weight";
+        const int rows = quant ? qasr::lm_head_q_rows(g.N, g.K, g.bits) : qasr::lm_head_rows(g.N, g.K);
+        parts = quant ? qasr::lm_head_q_parts(g.N, g.K, g.bits) : qasr::lm_head_parts(g.N, g.K);
+        const bool persistent = !g.generic && rows < (1 << 30);
+        if (persistent && g.B > rows) return "dec case: more batch rows than one LM-head launch holds at this hidden size";
+        if (persistent && g.N / 16 < 8 * parts) return "dec case: the persistent LM head needs a tile for every wave of its grid";
+        if (!persistent) parts = quant ? 1 : qasr::decode_gemv_blocks(qasr::DEC_EPI_LOGITS, g.N);
+    } else parts = qasr::decode_gemv_blocks(qasr::DEC_EPI_LOGITS, g.N);
+    if (g.part_cap < 0 || (long)g.part_cap < (long)g.B * parts) return "dec case: part_cap is below B * partials per row";
+    return nullptr;
+}
+
 extern "C" {
 
 int qasr_default_config(const char* preset, qasr_config* c) {
@@ -368,6 +456,15 @@ int qasr_enc_case_probe(qasr_engine* e, int op, const qasr_enc_case* g, const vo
     if (!e || !g || !out) return QASR_ERR_INVALID;
     if (const char* why = enc_case_refusal(op, *g, in, idx, off, pf, pw)) return fail(e, QASR_ERR_INVALID, why);
     return on_device(e, [&] { e->impl->enc_case_probe(op, *g, in, idx, off, pf, pw, out); });
+}
+
+int qasr_dec_case_probe(qasr_engine* e, int op, qasr_dec_case* g, const uint16_t* X, const void* W, const void* scales, const void* biases,
+                        const uint16_t* norm_w, uint16_t* out, float* logits, float* part_val, int32_t* part_idx, int32_t* state,
+                        const float* rope, float* rope_rows) {
+    if (!e || !g) return QASR_ERR_INVALID;
+    if (const char* why = dec_case_refusal(op, *g, X, W, scales, biases, norm_w, out, logits, part_val, part_idx, state, rope, rope_rows))
+        return fail(e, QASR_ERR_INVALID, why);
+    return on_device(e, [&] { e->impl->dec_case_probe(op, *g, X, W, scales, biases, norm_w, out, logits, part_val, part_idx, state, rope, rope_rows); });
 }
 
 int qasr_transcribe_batch(qasr_engine* e, const float* const* pcm, const size_t* n, size_t B, int sample_rate,

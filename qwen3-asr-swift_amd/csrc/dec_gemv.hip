@@ -472,6 +472,9 @@ static bool gemv2_k(const DecGemv2Args& a2, hipStream_t s) {
 // Falls back to [rmsnorm_rows +] the generic kernel for shapes without a tuned instantiation.
 static thread_local unsigned long long* g_gemv_dbg = nullptr;      // per host thread: engines of several devices step concurrently (qasr_dp_*)
 void decode_gemv_set_debug(unsigned long long* dbg) { g_gemv_dbg = dbg; }
+static thread_local int g_gemv_route = -1;
+void decode_gemv_note_route(int tuned) { g_gemv_route = tuned; }
+int decode_gemv_last_route() { return g_gemv_route; }
 int decode_gemv_fused_launch(DecEpi epi, const DecGemvArgs& a, const bf16_t* norm_w, float eps, bf16_t* norm_scratch,
                              hipStream_t s) {
     if (a.B <= 0) return 0;
@@ -488,6 +491,7 @@ int decode_gemv_fused_launch(DecEpi epi, const DecGemvArgs& a, const bf16_t* nor
             else if (epi == DEC_EPI_BF16) ok = gemv2_k<DEC_PRO_COPY, DEC_EPI_BF16, 1>(a2, s);
         }
     }
+    decode_gemv_note_route(ok ? 1 : 0);
     if (ok) return a.N / (16 * nt);
     DecGemvArgs g = a;
     if (norm_w) {

@@ -8,5 +8,7 @@ namespace qasr {
 bool decode_gemv_wide_supported(DecEpi epi, const DecGemvArgs& a);
 // out = epi(X . W^T), same contract as decode_gemv_fused_launch without a norm; returns the number of column tiles
 int decode_gemv_wide_launch(DecEpi epi, const DecGemvArgs& a, hipStream_t s);
+// a decode-step linear on fragment-major bf16 weights: the wide kernel where it applies (knob gemv_wide, no norm), else decode_gemv_fused_launch
+int decode_gemv_dense_launch(DecEpi epi, const DecGemvArgs& a, const bf16_t* norm_w, float eps, bf16_t* norm_scratch, hipStream_t s);
 
 }  // namespace qasr

@@ -9,6 +9,7 @@
 // Accumulation order per output: wave w adds its k-steps in ascending order (phase 0 first), then wave 0 + 1 + ... + 7.
 #include "dec_gemv_wide.h"
 #include "dec_epilogue.h"
+#include "tuning.h"
 
 namespace qasr {
 
@@ -108,7 +109,14 @@ int decode_gemv_wide_launch(DecEpi epi, const DecGemvArgs& a, hipStream_t s) {
     if (!decode_gemv_wide_supported(epi, a)) throw std::invalid_argument("decode_gemv_wide: unsupported shape");
     if (epi == DEC_EPI_RESID) gemv_wide_go<12, 2, DEC_EPI_RESID>(a, s);     // 2 phases x 3072 columns
     else gemv_wide_go<12, 2, DEC_EPI_BF16>(a, s);
+    decode_gemv_note_route(1);
     return a.N / 16;
+}
+
+// a decode-step linear of a float checkpoint (Engine::decode_gemv and qasr_dec_case_probe go through it)
+int decode_gemv_dense_launch(DecEpi epi, const DecGemvArgs& a, const bf16_t* norm_w, float eps, bf16_t* norm_scratch, hipStream_t s) {
+    if (!norm_w && tuning().gemv_wide && decode_gemv_wide_supported(epi, a)) return decode_gemv_wide_launch(epi, a, s);   // K = 6144 (1.7B)
+    return decode_gemv_fused_launch(epi, a, norm_w, norm_w ? eps : 0.f, norm_w ? norm_scratch : nullptr, s);
 }
 
 }  // namespace qasr

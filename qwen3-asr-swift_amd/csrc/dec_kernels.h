@@ -87,6 +87,10 @@ void argmax_rows_launch(const bf16_t* x, long ld, int rows, int n, int* out, hip
 void decode_gemv_set_debug(unsigned long long* dbg);
 int decode_gemv_fused_launch(DecEpi epi, const DecGemvArgs& a, const bf16_t* norm_w, float eps, bf16_t* norm_scratch,
                              hipStream_t s);
+// diagnostic: what the calling thread's last decode-step linear or LM-head launch (bf16 or quantised) ran: 1 a tuned instantiation,
+// 0 the generic kernel.  The launchers note it; qasr_dec_case_probe reports it so that a test shape cannot fall to the generic kernel silently
+void decode_gemv_note_route(int tuned);
+int decode_gemv_last_route();
 
 // Final RMSNorm + tied LM head + argmax partials (persistent kernel where the shape allows, else the fused
 // GEMV).  lm_head_parts = partials per row the launch will produce (fixed per (N, K)); partial layout

@@ -500,6 +500,7 @@ void decode_gemv_q_launch(DecEpi epi, const DecGemvArgs& a, const QuantImg& w, c
         if (w.bits == 4) ok = w.sb_f32 ? gemvq_epi<4, true>(epi, norm_w != nullptr, a2, s) : gemvq_epi<4, false>(epi, norm_w != nullptr, a2, s);
         else if (w.bits == 8) ok = w.sb_f32 ? gemvq_epi<8, true>(epi, norm_w != nullptr, a2, s) : gemvq_epi<8, false>(epi, norm_w != nullptr, a2, s);
     }
+    decode_gemv_note_route(ok ? 1 : 0);
     if (ok) return;
     DecGemvArgs g = a;
     if (norm_w) {
@@ -888,10 +889,12 @@ int lm_head_q_launch(const QuantImg& w, const bf16_t* X, const bf16_t* norm_w, f
         if (w.bits == 4) { if (w.sb_f32) QASR_LMQ(4, true); else QASR_LMQ(4, false); }
         else { if (w.sb_f32) QASR_LMQ(8, true); else QASR_LMQ(8, false); }
 #undef QASR_LMQ
+        decode_gemv_note_route(1);
         return LMQ_GRID;
     }
     // generic: needs a logits buffer (the engine always passes one on this path)
     if (!logits) throw std::invalid_argument("quantised LM head (generic path) needs the logits buffer");
+    decode_gemv_note_route(0);
     DecGemvArgs g{};
     g.X = X; g.B = B; g.N = N; g.K = K; g.logits = logits;
     rmsnorm_rows_launch(X, norm_w, norm_scratch, B, K, eps, s);

@@ -584,8 +584,7 @@ GreedyState Engine::greedy_rows(int r0) const {
 // float checkpoint: fragment-major bf16 images; quantised checkpoint: packed 4 / 8-bit images (dec_quant.h)
 void Engine::decode_gemv(DecEpi epi, const DecGemvArgs& a, const QuantImg& qi, const bf16_t* norm_w, bf16_t* h, hipStream_t s) {
     if (decw_.quant) decode_gemv_q_launch(epi, a, qi, norm_w, cfg_.rms_eps, h, s);
-    else if (!norm_w && tuning().gemv_wide && decode_gemv_wide_supported(epi, a)) decode_gemv_wide_launch(epi, a, s);   // K = 6144 (1.7B)
-    else decode_gemv_fused_launch(epi, a, norm_w, norm_w ? cfg_.rms_eps : 0.f, norm_w ? h : nullptr, s);
+    else decode_gemv_dense_launch(epi, a, norm_w, cfg_.rms_eps, h, s);
 }
 
 int Engine::step_chain(int r0, int nr) const {

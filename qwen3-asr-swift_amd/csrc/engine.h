@@ -119,6 +119,12 @@ public:
     // qasr_enc_case_probe (csrc/enc_cases.hip): one launch of an encoder-side kernel that is not the GEMM, on host data
     void enc_case_probe(int op, const qasr_enc_case& g, const void* in, const int32_t* idx, const int64_t* off, const float* pf,
                         const uint16_t* pw, void* out);
+    // qasr_dec_case_probe (csrc/dec_cases.hip): one decode-step linear (bf16 / quantised), LM head or rmsnorm_rows launch on host data
+    void dec_case_probe(int op, qasr_dec_case& g, const uint16_t* X, const void* W, const void* scales, const void* biases,
+                        const uint16_t* norm_w, uint16_t* out, float* logits, float* part_val, int32_t* part_idx, int32_t* state, const float* rope,
+                        float* rope_rows);
+    void dec_case_tail(int op, qasr_dec_case& g, const uint16_t* X, const void* W, const void* scales, const void* biases, uint16_t* out,
+                       const float* part_val, const int32_t* part_idx, int32_t* state, const float* rope, float* rope_rows);
     void kernel_probe(int which, int reps, float* avg_ms, double* bytes_per_launch);
     int batch_size() const { return batch_; }
     void decode_structure(int* fused_qa, int* chain, int* launches_per_layer);

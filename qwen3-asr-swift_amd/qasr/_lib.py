@@ -158,6 +158,12 @@ class QasrEncCase(C.Structure):
                                          "mel_stride", "H1", "W1", "stride")] + [("eps", C.c_float)]
 
 
+class QasrDecCase(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "N", "K", "epi", "generic", "bits", "sb_f32", "in_extra", "out_extra", "part_cap")] + \
+               [("eps", C.c_float)] + [(n, C.c_int32) for n in ("n_parts", "route", "max_new", "max_tokens", "eos", "ignore_eos", "advance_ctx",
+                                                                "clear_words", "n_rope", "half", "n_audio", "r0")]
+
+
 _P = C.POINTER
 _F = _P(C.c_float)
 _I = _P(C.c_int32)
@@ -199,6 +205,7 @@ SIGNATURES = {
                                        _F, C.c_void_p]),
     "qasr_attn_case_probe": (C.c_int, [_E, C.c_int, _P(QasrAttnCase)] + [_P(C.c_uint16)] * 3 + [_I] * 4 + [_P(C.c_uint16)] * 7),
     "qasr_enc_case_probe": (C.c_int, [_E, C.c_int, _P(QasrEncCase), C.c_void_p, _I, _P(C.c_int64), _F, _P(C.c_uint16), C.c_void_p]),
+    "qasr_dec_case_probe": (C.c_int, [_E, C.c_int, _P(QasrDecCase), _P(C.c_uint16)] + [C.c_void_p] * 3 + [_P(C.c_uint16)] * 2 + [_F, _F, _I, _I, _F, _F]),
     "qasr_set_shared_device": (C.c_int, [_E, C.c_int]),
     "qasr_decode_structure": (C.c_int, [_E, _P(C.c_int), _P(C.c_int), _P(C.c_int)]),
     "qasr_set_tuning": (C.c_int, [C.c_char_p, C.c_int]),
