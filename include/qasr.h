@@ -1262,6 +1262,70 @@ int qasr_stream_chunker_pop(qasr_stream_chunker* c, float* chunk);       /* 1: c
 int qasr_stream_chunker_flush(qasr_stream_chunker* c, float* chunk);     /* finalize: 1: the zero-padded remainder; 0: buffer was empty */
 size_t qasr_stream_chunker_buffered(const qasr_stream_chunker* c);
 
+/* ---- CosyVoice3 flow-matching mel decoder (csrc/flow_cosyvoice.hip, csrc/api_flow.cpp) --------------------------------------------------
+ * Reference: Sources/CosyVoiceTTS/FlowMatching.swift, DiT.swift.  Speech tokens at 25 Hz (prompt tokens then new tokens), optionally a
+ * prompt mel and a 192-d speaker vector -> an 80-bin mel at 50 Hz, the input of qasr_hift_decode.  What each entry replaces:
+ *   CosyVoiceWeightLoader.loadFlow / loadDiT (WeightLoading.swift:126-212), local directory       -> qasr_flow_create
+ *   inputEmbedding, PreLookaheadLayer, RepeatInterleaveUpsampler (FlowMatching.swift:204-227, :315-321, :23-33) -> qasr_flow_mu
+ *   the L2 norm and spk_embed_affine_layer (FlowMatching.swift:332-336)                            -> qasr_flow_spks
+ *   DiT.callAsFunction (DiT.swift:430-473) on one branch as given                                  -> qasr_flow_velocity
+ *   ConditionalFlowMatching.forward (FlowMatching.swift:127-196) from a given x0                   -> qasr_flow_solve
+ *   CosyVoiceFlowModel.callAsFunction (FlowMatching.swift:293-376)                                 -> qasr_flow_generate / _generate_batch
+ * DiT: dim 1024, 16 heads x 64, ff 2048, any depth (22 as published); time embedding = sinusoid (half 128, angles 1000 t f, [sin | cos],
+ * DiT.swift:22-32) -> Linear -> SiLU -> Linear; rows [x | cond | mu | spks] -> proj -> h + conv_pos_embed(h) (two grouped causal convs
+ * k = 31 with Mish, DiT.swift:283-322); per block AdaLN chunks shift / scale / gate (attention) then shift / scale / gate (MLP)
+ * (DiT.swift:88-101), RoPE on features 0 .. 63 of the 1024-wide q and k only, i.e. head 0 (DiT.swift:161-171), GELU-tanh; norm_out's
+ * chunks are scale then shift (DiT.swift:121-125); proj_out is a float Linear.  Solver: t_i = 1 - cos(i / n pi / 2) in Float, both CFG
+ * branches per step on the same x and t, v = (1 + 0.7) v_c - 0.7 v_u, x += (t_{i+1} - t_i) v (FlowMatching.swift:141-189).
+ * Noise: x0 is this library's counter stream, not MLX's: element (frame t, bin m) of a clip = temperature * the `normal` of draw
+ * 80 t + m of the clip's seed (qasr_hift_noise).
+ * Precision: x, the residual stream, modulation, LayerNorm statistics and the solver are f32; GEMM operands are bf16, accumulation f32;
+ * MLX 4 / 8 bit Linears are dequantised once at load, except the time MLP and the AdaLN linears, which stay packed (DESIGN.md section
+ * 22).  A clip's result is bit-identical alone, in any batch and place, under any split into passes, and run to run.  One object, one
+ * thread at a time.  Not covered: the LLM, CAM++, the speech tokenizer, FlowMelExtractor, chunked / streaming flow, float checkpoints. */
+typedef struct qasr_flow qasr_flow;
+/* model_dir/flow.safetensors with the reference's keys (WeightLoading.swift:126-212).  Depth = the number of
+ * decoder.transformer_blocks.N present; bits (4 or 8) at group 64 from the weight / scales shapes; every other dimension is checked:
+ * a missing file or key -> QASR_ERR_IO, a wrong shape or dtype or an unexpected key -> QASR_ERR_INVALID, the key named in
+ * qasr_flow_last_error(NULL); all before any HIP call.  max_frames: mel frames (sum over clips) one device pass holds, 0 = 4096, at
+ * most 2^15; about 33 KB of device memory per frame.  order_with: as for qasr_seg_create. */
+int qasr_flow_create(int device, const char* model_dir, size_t max_frames, qasr_engine* order_with, qasr_flow** out);
+void qasr_flow_destroy(qasr_flow* h);
+const char* qasr_flow_last_error(const qasr_flow* h);               /* h may be NULL: last create() or check_clip failure */
+int qasr_flow_is_loaded(const qasr_flow* h);
+int qasr_flow_unload(qasr_flow* h);                                 /* later device calls return QASR_ERR_NOT_LOADED */
+size_t qasr_flow_memory_footprint(const qasr_flow* h);              /* bytes as stored of the tensors read, 0 unloaded */
+int qasr_flow_depth(const qasr_flow* h);
+size_t qasr_flow_mel_frames(size_t n_tokens);                       /* 2 n (tokenMelRatio, Configuration.swift:74).  Pure CPU. */
+/* t[n_steps + 1], the solver's time steps (FlowMatching.swift:141-144); n_steps in 1 .. 64.  Pure CPU. */
+int qasr_flow_schedule(int n_steps, float* t);
+/* what qasr_flow_generate checks of a clip before any device work: n >= 1, every id in [0, vocab) (refused, not clamped),
+ * prompt_frames == 2 n_prompt and <= 2 (n + n_prompt) <= max_frames (0 = 4096).  Pure CPU. */
+int qasr_flow_check_clip(const int32_t* tokens, size_t n, const int32_t* prompt_tokens, size_t n_prompt, size_t prompt_frames, int vocab,
+                         size_t max_frames);
+/* Stage entries; rows are frames: x, mu, cond, v, z, mel [T][80], spks [80]; spks and cond may be NULL (zeros, DiT.swift:357-362, :443-447) */
+int qasr_flow_mu(qasr_flow* h, const int32_t* tokens, size_t n, float* mu /* [2 n][80] */);
+int qasr_flow_spks(qasr_flow* h, const float* emb192 /* NULL: 80 zeros */, float* spks80);
+int qasr_flow_velocity(qasr_flow* h, const float* x, const float* mu, const float* spks, const float* cond, size_t T, float t, float* v);
+/* n_steps Euler steps from z (0 = 10, at most 64); v_out NULL or [2][T][80]: the last step's conditioned, then unconditioned velocity.
+ * Bit-identical to a loop over qasr_flow_velocity (conditioned; then mu zero, spks and cond NULL) with the Euler line in f32. */
+int qasr_flow_solve(qasr_flow* h, const float* mu, const float* spks, const float* cond, size_t T, const float* z, int n_steps, float* v_out,
+                    float* mel);
+/* The whole model.  prompt_tokens / prompt_feat [80][prompt_frames] / spk_emb [192] may be NULL; z_out NULL or, like mel,
+ * [80][2 (n + n_prompt)] as the reference returns it (the caller slices off the first prompt_frames columns).  Bit-identical to
+ * qasr_flow_solve on z_out with qasr_flow_mu / qasr_flow_spks and cond = the prompt mel followed by zeros. */
+int qasr_flow_generate(qasr_flow* h, const int32_t* tokens, size_t n, const int32_t* prompt_tokens, size_t n_prompt, const float* prompt_feat,
+                       size_t prompt_frames, const float* spk_emb, int n_steps, float temperature, uint64_t seed, float* z_out, float* mel);
+/* B clips of any lengths in passes of at most max_frames frames cut at clip boundaries; one clip above max_frames -> QASR_ERR_INVALID.
+ * The per-clip arrays prompt_tokens, n_prompt, prompt_feat, prompt_frames, spk_emb and z_out may be NULL, and so may their entries. */
+int qasr_flow_generate_batch(qasr_flow* h, const int32_t* const* tokens, const size_t* n, const int32_t* const* prompt_tokens,
+                             const size_t* n_prompt, const float* const* prompt_feat, const size_t* prompt_frames,
+                             const float* const* spk_emb, int n_steps, float temperature, const uint64_t* seeds, size_t B,
+                             float* const* z_out, float* const* mel);
+/* ms[5]: device time of the solver passes of the last call, HIP events on the work stream: modulation table (0 when the cached table
+ * of this n_steps was reused), input_embed, blocks, norm_out + proj_out, Euler */
+int qasr_flow_timing(const qasr_flow* h, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -451,6 +451,24 @@ SIGNATURES = {
     "qasr_stream_chunker_pop": (C.c_int, [_E, _F]),
     "qasr_stream_chunker_flush": (C.c_int, [_E, _F]),
     "qasr_stream_chunker_buffered": (C.c_size_t, [_E]),
+    "qasr_flow_create": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t, _E, _P(_E)]),
+    "qasr_flow_destroy": (None, [_E]),
+    "qasr_flow_last_error": (C.c_char_p, [_E]),
+    "qasr_flow_is_loaded": (C.c_int, [_E]),
+    "qasr_flow_unload": (C.c_int, [_E]),
+    "qasr_flow_memory_footprint": (C.c_size_t, [_E]),
+    "qasr_flow_depth": (C.c_int, [_E]),
+    "qasr_flow_mel_frames": (C.c_size_t, [C.c_size_t]),
+    "qasr_flow_schedule": (C.c_int, [C.c_int, _F]),
+    "qasr_flow_check_clip": (C.c_int, [_I, C.c_size_t, _I, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t]),
+    "qasr_flow_mu": (C.c_int, [_E, _I, C.c_size_t, _F]),
+    "qasr_flow_spks": (C.c_int, [_E, _F, _F]),
+    "qasr_flow_velocity": (C.c_int, [_E, _F, _F, _F, _F, C.c_size_t, C.c_float, _F]),
+    "qasr_flow_solve": (C.c_int, [_E, _F, _F, _F, C.c_size_t, _F, C.c_int, _F, _F]),
+    "qasr_flow_generate": (C.c_int, [_E, _I, C.c_size_t, _I, C.c_size_t, _F, C.c_size_t, _F, C.c_int, C.c_float, C.c_uint64, _F, _F]),
+    "qasr_flow_generate_batch": (C.c_int, [_E, _P(_I), _P(C.c_size_t), _P(_I), _P(C.c_size_t), _P(_F), _P(C.c_size_t), _P(_F), C.c_int, C.c_float,
+                                           _P(C.c_uint64), C.c_size_t, _P(_F), _P(_F)]),
+    "qasr_flow_timing": (C.c_int, [_E, _F]),
 }
 
 _lib = None

@@ -980,3 +980,107 @@ def write_tts_talker_safetensors(sd: dict, model_dir: str, drop=(), extra=(), sc
         for raw in blobs:
             fh.write(raw)
     return model_dir
+
+
+# ---- CosyVoice3 flow-matching mel decoder (Sources/CosyVoiceTTS/FlowMatching.swift, DiT.swift; keys: WeightLoading.swift:126-212) ----
+FLOW_DIM, FLOW_FF, FLOW_MEL, FLOW_SPK, FLOW_VOCAB = 1024, 2048, 80, 192, 6561
+
+
+def cosyvoice_flow_tensor_shapes(depth: int = 22, vocab: int = FLOW_VOCAB) -> dict:
+    """key -> (shape, quantised) of flow.safetensors before quantisation; a quantised `X.weight` [N, K] is stored as X.weight (packed
+    uint32), X.scales, X.biases [N, K / 64], beside X.bias [N]."""
+    d = "decoder."
+    s = {"input_embedding.weight": ((vocab, FLOW_MEL), False),
+         "spk_embed_affine_layer.weight": ((FLOW_MEL, FLOW_SPK), False), "spk_embed_affine_layer.bias": ((FLOW_MEL,), False),
+         "pre_lookahead_layer.conv1.weight": ((FLOW_DIM, 4, FLOW_MEL), False), "pre_lookahead_layer.conv1.bias": ((FLOW_DIM,), False),
+         "pre_lookahead_layer.conv2.weight": ((FLOW_MEL, 3, FLOW_DIM), False), "pre_lookahead_layer.conv2.bias": ((FLOW_MEL,), False),
+         d + "input_embed.conv_pos_embed.conv1.0.weight": ((FLOW_DIM, 31, 64), False), d + "input_embed.conv_pos_embed.conv1.0.bias": ((FLOW_DIM,), False),
+         d + "input_embed.conv_pos_embed.conv2.0.weight": ((FLOW_DIM, 31, 64), False), d + "input_embed.conv_pos_embed.conv2.0.bias": ((FLOW_DIM,), False),
+         d + "proj_out.weight": ((FLOW_MEL, FLOW_DIM), False), d + "proj_out.bias": ((FLOW_MEL,), False)}
+    q = [(d + "time_embed.time_mlp.0", FLOW_DIM, 256), (d + "time_embed.time_mlp.2", FLOW_DIM, FLOW_DIM), (d + "input_embed.proj", FLOW_DIM, 4 * FLOW_MEL),
+         (d + "norm_out.linear", 2 * FLOW_DIM, FLOW_DIM)]
+    for i in range(depth):
+        b = d + f"transformer_blocks.{i}."
+        q += [(b + "attn_norm.linear", 6 * FLOW_DIM, FLOW_DIM), (b + "attn.to_q", FLOW_DIM, FLOW_DIM), (b + "attn.to_k", FLOW_DIM, FLOW_DIM),
+              (b + "attn.to_v", FLOW_DIM, FLOW_DIM), (b + "attn.to_out.0", FLOW_DIM, FLOW_DIM), (b + "ff.ff.0.0", FLOW_FF, FLOW_DIM),
+              (b + "ff.ff.2", FLOW_DIM, FLOW_FF)]
+    for stem, n, k in q:
+        s[stem + ".weight"] = ((n, k), True)
+        s[stem + ".bias"] = ((n,), False)
+    return s
+
+
+def synth_cosyvoice_flow_state_dict(seed: int = 0, depth: int = 22, bits: int = 4, vocab: int = FLOW_VOCAB) -> dict:
+    """Seeded flow-decoder weights in the checkpoint's form: every QuantizedLinear quantised with quantize_linear (bf16 scales), the rest
+    float32.  Matrices are N(0, g / fan_in).  The AdaLN linears give scale and shift of about 0.3 and gates of 0.4 +- 0.15 with a random
+    sign (their bias carries the 0.4), so that every gate is of order 0.1 to 1 and depth blocks move the residual stream without
+    letting its RMS leave the decade it starts in (tests/test_flow_cpu.py checks both)."""
+    rng = torch.Generator().manual_seed(515151 + seed)
+    sd = {}
+    for key, (shape, quant) in cosyvoice_flow_tensor_shapes(depth, vocab).items():
+        if key.endswith(".bias"):
+            w = 0.05 * torch.randn(shape, generator=rng)
+            if "attn_norm.linear" in key:                   # chunks 2 and 5 are the gates
+                sign = torch.where(torch.rand((2, FLOW_DIM), generator=rng) < 0.5, -1.0, 1.0)
+                w[2 * FLOW_DIM:3 * FLOW_DIM] += 0.4 * sign[0]
+                w[5 * FLOW_DIM:6 * FLOW_DIM] += 0.4 * sign[1]
+        elif key == "input_embedding.weight":
+            w = 0.5 * torch.randn(shape, generator=rng)
+        elif len(shape) == 3:
+            w = torch.randn(shape, generator=rng) * math.sqrt(2.0 / (shape[1] * shape[2]))
+        else:
+            gain = 0.6 if ("attn_norm" in key or "norm_out" in key) else 2.0 if "time_mlp" in key else 10.0 if key.startswith("spk_embed") else 1.0
+            w = torch.randn(shape, generator=rng) * (gain / math.sqrt(shape[1]))
+        if quant:
+            stem = key[:-len(".weight")]
+            sd[key], sd[stem + ".scales"], sd[stem + ".biases"] = quantize_linear(w.to(torch.bfloat16), bits)
+        else:
+            sd[key] = w
+    return sd
+
+
+def write_cosyvoice_flow_safetensors(sd: dict, model_dir: str, drop=(), reshape=None, extra=(), scales_dtype: str = "BF16") -> str:
+    """Writes `sd` as model_dir/flow.safetensors: int32 tensors as U32, scales / biases as `scales_dtype`, the rest F32.  `drop`: keys left
+    out; `reshape`: key -> shape the tensor is resized to; `extra`: (key, float array) pairs added as F32.  Returns model_dir."""
+    import json
+    import os
+    os.makedirs(model_dir, exist_ok=True)
+    header, blobs, off = {}, [], 0
+
+    def add(key, dtype, shape, raw):
+        nonlocal off
+        header[key] = {"dtype": dtype, "shape": list(shape), "data_offsets": [off, off + len(raw)]}
+        blobs.append(raw)
+        off += len(raw)
+
+    for key in sorted(sd):
+        if key in drop:
+            continue
+        v = sd[key]
+        if v.dtype == torch.int32:
+            a = v.contiguous().numpy().astype("<i4")
+            if reshape and key in reshape:
+                a = np.resize(a, reshape[key])
+            add(key, "U32", a.shape, a.tobytes())
+            continue
+        f = v.to(torch.float32).contiguous().numpy()
+        if reshape and key in reshape:
+            f = np.resize(f, reshape[key])
+        if key.endswith((".scales", ".biases")) and scales_dtype == "BF16":
+            u = f.astype("<f4").view("<u4")
+            add(key, "BF16", f.shape, ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype("<u2").tobytes())
+        elif key.endswith((".scales", ".biases")) and scales_dtype == "F16":
+            add(key, "F16", f.shape, f.astype("<f2").tobytes())
+        else:
+            add(key, "F32", f.shape, f.astype("<f4").tobytes())
+    for k, v in (extra.items() if isinstance(extra, dict) else extra):
+        a = np.asarray(v, dtype=np.float32)
+        add(k, "F32", a.shape, a.astype("<f4").tobytes())
+    h = json.dumps(header).encode()
+    h += b" " * ((8 - len(h) % 8) % 8)
+    with open(os.path.join(model_dir, "flow.safetensors"), "wb") as fh:
+        fh.write(len(h).to_bytes(8, "little"))
+        fh.write(h)
+        for raw in blobs:
+            fh.write(raw)
+    return model_dir
