@@ -1326,6 +1326,96 @@ int qasr_flow_generate_batch(qasr_flow* h, const int32_t* const* tokens, const s
  * of this n_steps was reused), input_embed, blocks, norm_out + proj_out, Euler */
 int qasr_flow_timing(const qasr_flow* h, float* ms);
 
+/* ---- CosyVoice3 speech-token LLM (csrc/llm_cosyvoice.hip, csrc/cvlm_sampler.cpp, csrc/api_cvlm.cpp) ------------------------------------
+ * Reference: Sources/CosyVoiceTTS/LLM.swift, Configuration.swift:5-41,124-133, WeightLoading.swift:18-110, CosyVoiceTTS.swift:194-322.
+ * Text ids (the caller's tokenizer; instruction + <|endofprompt|> + content) and optionally the prompt speech tokens of a reference clip
+ * -> speech tokens at 25 Hz, which qasr_flow_generate turns into a mel and qasr_hift_decode into 24 kHz audio.  What each entry replaces:
+ *   CosyVoiceWeightLoader.loadLLM (WeightLoading.swift:35-110), llm.safetensors of a local directory   -> qasr_cvlm_create
+ *   CosyVoiceLLM.generate (LLM.swift:479-560) for B rows                                              -> qasr_cvlm_generate
+ *   forwardStep on given tokens (:425-468)                                                            -> qasr_cvlm_forced
+ *   sampleToken (:56-123)                                                                             -> qasr_cvlm_sample / _sample_host
+ *   CosyVoiceTTSModel.synthesize behind the tokenizer (CosyVoiceTTS.swift:236-322)                     -> qasr_cvlm_synthesize
+ * A Qwen2.5-0.5B shaped decoder (hidden 896, 24 layers, 14 heads over 2 kv heads, head_dim 64, no q/k norm, a Linear bias on q, k, v,
+ * RoPE theta 1e6 split-half, SwiGLU 4864), float text and speech embeddings, a quantised speech head.  MLX affine 4 / 8 bit checkpoints
+ * only.  The prefix of a row is [speech_emb(sos), text_emb(ids), speech_emb(task_id), speech_emb(prompt tokens)]; position prefix - 1
+ * yields token 0; the stop set is speech_tokens + {0, 1, 2}; a stop token ends the row and is not stored.  Random numbers are the
+ * library's counter stream keyed by (seed, row_index, step, draw), not MLX's.  Rows of a call are independent: a row's tokens and forced
+ * logits are the same bits alone, in any batch, at any slot, under any max_batch and under either prompt chunking (tuning knob
+ * cvlm_prompt_chunk: 64 | 1).  One object, one thread at a time.  HBM: the packed weights plus the KV cache, 2 x layers x kv_heads x 64
+ * x 2 bytes = 12,288 bytes per position and row; positions = 2 + max_text + max_prompt_tokens + max_tokens rounded up to 64.
+ * Not covered: the text tokenizer, CAM++, the speech tokenizer, float checkpoints, a streaming pool. */
+typedef struct qasr_cvlm qasr_cvlm;
+typedef struct qasr_cvlm_config {
+    int32_t hidden, layers, heads, kv_heads, head_dim, inter;          /* 896 24 14 2 64 4864 */
+    int32_t text_vocab, speech_tokens, speech_extra;                   /* 151936 6561 200: sos = 6561, eos = 6562, task_id = 6563 */
+    float rms_eps, rope_theta;                                         /* 1e-6 1e6 */
+    int32_t bits, group_size;                                          /* 4 | 8, 64 */
+    int32_t device;
+    int32_t max_batch;                                                 /* rows of one call, 1 .. 64 (default 8) */
+    int32_t max_text, max_prompt_tokens, max_tokens;                   /* per row (defaults 512, 0, 1000) */
+} qasr_cvlm_config;
+typedef struct qasr_cvlm_sampling {         /* CosyVoiceSamplingConfig (Configuration.swift:124-133); maxTokenTextRatio is never read there: no field */
+    int32_t top_k;                          /* 25; <= 0 or >= vocabulary: off */
+    float top_p;                            /* 0.8; >= 1: off */
+    int32_t win_size;                       /* 10; 0: no repetition-aware resample; at most 64 */
+    float tau_r;                            /* 0.1 */
+    float min_ratio;                        /* 2.0: min_len = Int(Float(content_len) * min_ratio) */
+} qasr_cvlm_sampling;
+typedef struct qasr_cvlm_request {
+    size_t B;
+    const int32_t* const* text; const int32_t* text_len;        /* [B]: at least 1 id */
+    const int32_t* const* prompt; const int32_t* prompt_len;    /* [B] or NULL; NULL entry or 0: none; ids in [0, speech_tokens) */
+    const int32_t* content_len;                                 /* [B] or NULL; < 0: the text length */
+    const int32_t* max_tokens;                                  /* [B] or NULL; <= 0: the handle's */
+    const int64_t* row_index;                                   /* [B] or NULL (0 .. B-1): keys the row's random stream */
+} qasr_cvlm_request;
+int qasr_cvlm_default_config(int bits, qasr_cvlm_config* out);
+void qasr_cvlm_default_sampling(qasr_cvlm_sampling* out);
+/* reads model_dir/llm.safetensors.  Every key, shape and dtype is checked on the host before any HIP call: a missing file or key ->
+ * QASR_ERR_IO; a wrong shape or dtype, a float checkpoint, a key the reference does not name (layers.N.self_attn.q_norm / k_norm.weight,
+ * which its loader names and never loads, are ignored) -> QASR_ERR_INVALID; so is a geometry the kernels do not serve: head_dim != 64,
+ * hidden != heads x 64, heads % kv_heads != 0, heads / kv_heads > 16, hidden or inter not a multiple of 128, group_size != 64, a
+ * vocabulary over 8192, inter over 10240 (4 bit) | 5120 (8 bit) -- there is no fallback kernel.  The key is named in
+ * qasr_cvlm_last_error(NULL).  qasr_cvlm_check runs the host checks alone: no device is touched, no handle is made. */
+int qasr_cvlm_create(const char* model_dir, const qasr_cvlm_config* cfg, qasr_cvlm** out);
+int qasr_cvlm_check(const char* model_dir, const qasr_cvlm_config* cfg);
+void qasr_cvlm_free(qasr_cvlm* h);
+const char* qasr_cvlm_last_error(const qasr_cvlm* h);              /* h may be NULL: last create() / check() failure */
+size_t qasr_cvlm_memory_footprint(const qasr_cvlm* h);             /* parameter bytes as stored */
+size_t qasr_cvlm_device_bytes(const qasr_cvlm* h);                 /* every device allocation of the handle */
+int qasr_cvlm_poll_interval(void);                                 /* steps between two host reads of the finished flags (8) */
+int qasr_cvlm_context(const qasr_cvlm_config* cfg);                /* positions of a row's cache, or -status.  Pure CPU. */
+/* the prefix of one row as the prompt pass reads it: a text id as it is, a speech id as -1 - id; out [2 + text_len + prompt_len].
+ * Returns the prefix length or -status.  Pure CPU. */
+int qasr_cvlm_plan_prefix(const qasr_cvlm_config* cfg, const int32_t* text, int32_t text_len, const int32_t* prompt, int32_t prompt_len,
+                          int32_t* out);
+/* tokens [B][max_tokens] int32 (the handle's max_tokens; entries past n_tokens[b] are -1), n_tokens [B].  B > max_batch, a text or prompt
+ * or max_tokens over the handle's -> QASR_ERR_CAPACITY; an id outside its vocabulary (refused, not clamped), an empty text, a NULL buffer,
+ * win_size over 64 -> QASR_ERR_INVALID.  Every refusal names the row. */
+int qasr_cvlm_generate(qasr_cvlm* h, const qasr_cvlm_request* rq, const qasr_cvlm_sampling* s, uint64_t seed, int32_t* tokens, int32_t* n_tokens);
+/* teacher-forced pass: tokens [B][T], T <= max_tokens, ids in [0, vocabulary) -> logits [B][T][V] f32 (V = speech_tokens + speech_extra),
+ * hidden [B][T][hidden] (post-norm, bf16 values); logits[f] is read at position prefix - 1 + f after feeding tokens 0 .. f - 1.  Either
+ * output may be NULL. */
+int qasr_cvlm_forced(qasr_cvlm* h, const qasr_cvlm_request* rq, const int32_t* tokens, size_t T, float* logits, float* hidden);
+/* the device sampler alone on the caller's logits [B][V]: history[b] [n_history[b]] (n_history <= max_tokens), step[b] keys the random
+ * stream and step 0 masks the stops, below_min[b] != 0 masks them too; row_index NULL: 0 .. B-1.  out [B]. */
+int qasr_cvlm_sample(qasr_cvlm* h, const float* logits, const int32_t* const* history, const int32_t* n_history, const int32_t* step,
+                     const int32_t* below_min, size_t B, const qasr_cvlm_sampling* s, uint64_t seed, const int64_t* row_index, int32_t* out);
+/* the host twin of the device sampler on one row.  cfg NULL: the default geometry.  Returns the token or -status.  Pure CPU. */
+int qasr_cvlm_sample_host(const qasr_cvlm_config* cfg, const float* logits, const int32_t* history, int32_t n_history, int32_t step,
+                          int below_min, const qasr_cvlm_sampling* s, uint64_t seed, int64_t row_index);
+/* one linear of the loaded handle alone, as the step runs it: kind 0 q|k|v (input_layernorm prologue, bias; y [B][(heads + 2 kv) x 64]),
+ * 1 o (y = resid + o(x), [B][hidden]), 2 gate|up (post_attention_layernorm prologue, SwiGLU; y [B][inter]), 3 down (y = resid + down(x)),
+ * 4 head (final norm prologue; y [B][V] f32; layer ignored).  x [B][K], resid [B][N]: f32 holding bf16 values.  1 <= B <= 64. */
+int qasr_cvlm_linear_probe(qasr_cvlm* h, int32_t layer, int32_t kind, const float* x, const float* resid, size_t B, float* y);
+/* generate, then per row qasr_flow_generate_batch (the row's prompt tokens, prompt_feat[b] [80][prompt_frames[b]] and spk_emb[b] [192],
+ * any NULL; 10 steps, temperature 1, flow and vocoder seed = seed + row_index[b]) and qasr_hift_decode_batch on the full mel; the first
+ * 480 x prompt_frames[b] samples are dropped afterwards (CosyVoiceTTS.swift:276-322).  pcm[b] holds qasr_hift_num_samples(2 x max_tokens)
+ * floats, n_samples[b] of them are written; a row with no tokens returns 0 samples.  tokens / n_tokens as qasr_cvlm_generate, may be NULL. */
+int qasr_cvlm_synthesize(qasr_cvlm* h, qasr_flow* flow, qasr_hift* hift, const qasr_cvlm_request* rq, const qasr_cvlm_sampling* s,
+                         uint64_t seed, const float* const* spk_emb, const float* const* prompt_feat, const size_t* prompt_frames,
+                         float* const* pcm, size_t* n_samples, int32_t* tokens, int32_t* n_tokens);
+
 #ifdef __cplusplus
 }
 #endif

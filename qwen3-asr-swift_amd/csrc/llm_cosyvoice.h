@@ -1,0 +1,128 @@
+// llm_cosyvoice.h -- the CosyVoice3 speech-token LLM on the device (kernels and host object in llm_cosyvoice.hip, host sampler twin in
+// cvlm_sampler.cpp, C ABI in api_cvlm.cpp): text ids (+ prompt speech tokens) -> speech tokens at 25 Hz, the input of qasr_flow_*.
+//
+// Reference: Sources/CosyVoiceTTS/LLM.swift (sampleToken :12-123, CosyVoiceAttention :131-216, CosyVoiceBlock :219-262, buildInputSequence
+// :387-417, generate :479-560), Configuration.swift:5-41,124-133, WeightLoading.swift:18-110 (keys of llm.safetensors).  A Qwen2.5-0.5B
+// shaped decoder: head_dim 64, no q/k norm, a Linear bias on q, k and v, separate text and speech embeddings, a quantised speech head.
+// MLX affine 4 / 8 bit Linears stay packed (the images of dec_quant.h); bf16 activations between ops, f32 accumulation, f32 norms,
+// softmax and logits.  Every kernel of the step is in llm_cosyvoice.hip; nothing is shared with the Engine or the Talker beyond the
+// image builder (quant_pack_launch), the RoPE tables and the counter random stream of tts_talker.h.  DESIGN.md section 23.
+#pragma once
+#include "dec_quant.h"
+#include "safetensors.h"
+#include "tts_talker.h"      // tts_stream_key, tts_uniform
+#include "qasr.h"
+#include <map>
+#include <memory>
+#include <set>
+#include <string>
+#include <vector>
+
+namespace qasr {
+
+constexpr int CVLM_POLL = 8;             // steps between two host reads of the finished flags
+constexpr int CVLM_MAX_VOCAB = 8192;     // logits of one sampler workgroup (four LDS arrays of this many words)
+constexpr int CVLM_MAX_WIN = 64;         // history window of the repetition-aware resample (LDS)
+constexpr int CVLM_ATT_CHUNK = 64;       // keys of one wave in one round of the attention sweep
+constexpr int CVLM_ATT_ROUND = 256;      // keys of one round (4 waves): the online-softmax merge happens once per round, in key order
+constexpr int CVLM_PASS_ROWS = 64;       // rows of one launch sequence: batch rows of a step, packed (slot, position) pairs of a prompt pass
+constexpr int CVLM_MAX_CTX = 32768;      // positions of a row
+constexpr int CVLM_GEMV_PHASE = 1024;    // activation columns of the GEMV's LDS image
+constexpr int CVLM_GEMV_MAXB = 10;       // k-blocks one wave may own: K <= 8 * 10 * 128 (4 bit) | 8 * 10 * 64 (8 bit)
+constexpr int CVLM_STOPS = 3;            // speech_tokens + 0 .. 2 end a row (Configuration.swift:33-35)
+
+// ---- the sampler, stated once for the device kernel and the host twin (cvlm_sampler.cpp) ------------------------------------------
+struct CvlmSampleParams {
+    int top_k; float top_p; int win_size; float tau_r;
+    int V, speech_tokens;                // suppress [speech_tokens, V) except the stops speech_tokens + 0 .. 2
+    unsigned long long seed;
+};
+// repetitions of the pick in the window that trigger the resample (LLM.swift:106-108)
+__host__ __device__ inline int cvlm_ras_threshold(int win_size, float tau_r) {
+    const int t = (int)((float)win_size * tau_r);
+    return t > 1 ? t : 1;
+}
+// sampleToken on one row of f32 logits; history [n_history] are the row's tokens so far, step keys the random stream, mask_stops is
+// "below min_len or token 0".  Pure host code.
+int cvlm_sample_host(const float* logits, const CvlmSampleParams& p, const int32_t* history, int n_history, int step, bool mask_stops,
+                     long long row);
+
+struct CvlmRow {                         // one row of a request, checked by the C ABI
+    const int32_t* text; int n_text;
+    const int32_t* prompt; int n_prompt; // prompt speech tokens, may be null / 0
+    int content_len;                     // ids of `text` that are content (min_len = Int(Float(content_len) * min_ratio))
+    int max_tokens;                      // 1 .. the handle's
+    long long index;                     // the caller's row index (random stream)
+};
+
+enum CvlmLinear { CVLM_LIN_QKV = 0, CVLM_LIN_O = 1, CVLM_LIN_GATE_UP = 2, CVLM_LIN_DOWN = 3, CVLM_LIN_HEAD = 4 };
+
+class CosyLlm {
+  public:
+    // every key, shape and dtype is checked on the host before any HIP call (WeightLoadError); host_only: stop there (no device is touched)
+    CosyLlm(const qasr_cvlm_config& cfg, const SafeTensorsDir& st, bool host_only = false);
+    ~CosyLlm();
+    const qasr_cvlm_config& config() const { return cfg_; }
+    int vocab() const { return cfg_.speech_tokens + cfg_.speech_extra; }
+    size_t footprint() const { return param_bytes_; }
+    size_t device_bytes() const { return device_bytes_; }
+    static void check_geometry(const qasr_cvlm_config& c);      // std::invalid_argument for what the kernels do not serve
+    static int context(const qasr_cvlm_config& c);              // positions of a row's cache
+    // the prefix of a row as the prompt pass reads it: text ids as they are, speech ids as -1 - id (buildInputSequence)
+    static std::vector<int> plan_prefix(const qasr_cvlm_config& c, const CvlmRow& r);
+    // tokens [B][max_tokens] (the handle's; -1 past a row's count), n_tokens [B]
+    void generate(const std::vector<CvlmRow>& rows, const qasr_cvlm_sampling& s, unsigned long long seed, int32_t* tokens, int32_t* n_tokens);
+    // teacher-forced: tokens [B][T] -> logits [B][T][V], hidden [B][T][hidden] (post-norm), either may be null
+    void forced(const std::vector<CvlmRow>& rows, const int32_t* tokens, int T, float* logits, float* hidden);
+    // the device sampler alone: logits [B][V], history[b] [n_history[b]]
+    void sample(int B, const float* logits, const int32_t* const* history, const int32_t* n_history, const int32_t* step,
+                const int32_t* below_min, const qasr_cvlm_sampling& s, unsigned long long seed, const int64_t* row_index, int32_t* out);
+    // one linear of the handle alone: x [B][K] (bf16 values), resid [B][N] for o / down, y [B][N] (gate_up: [B][inter])
+    void linear_probe(int layer, int kind, int B, const float* x, const float* resid, float* y);
+    static void linear_shape(const qasr_cvlm_config& c, int kind, int& K, int& N_out);
+    struct State;                        // per-row device state (llm_cosyvoice.hip)
+
+  private:
+    struct QLin { QuantImg img; const float* bias = nullptr; int N = 0, K = 0; };
+    struct Layer { QLin qkv, o, gu, down; const bf16_t *ln1 = nullptr, *ln2 = nullptr; };
+    QLin load_qlin(const SafeTensorsDir& st, const std::vector<std::string>& stems, int K, bool bias, int interleave, int pad_to = 0);
+    const bf16_t* load_bf16(const SafeTensorsDir& st, const std::string& key, std::vector<int64_t> shape);
+    void load_all(const SafeTensorsDir& st);
+    void* dev_upload(const void* src, size_t bytes);
+    void gemv(int epi, const QLin& w, const bf16_t* X, int B, const bf16_t* norm_w, bf16_t* out, float* logits);
+    void layers(int rows, const int* slot, const int* pos, bool last_kv_only);
+    void prefill(const std::vector<CvlmRow>& rows, const qasr_cvlm_sampling* s, int forced_T);
+    void issue_step(int B, bool forced_mode);
+    void run_step(int B);
+    void set_knobs(const qasr_cvlm_sampling& s, unsigned long long seed);
+    void drop_graphs();
+    State state() const;
+
+    qasr_cvlm_config cfg_;
+    bool dry_ = false;
+    std::set<std::string> seen_keys_;
+    hipStream_t stream_ = nullptr;
+    size_t param_bytes_ = 0, device_bytes_ = 0;
+    std::vector<std::unique_ptr<DevBuf>> bufs_;
+    std::vector<Layer> layers_;
+    QLin head_;
+    const bf16_t *text_emb_ = nullptr, *speech_emb_ = nullptr, *norm_ = nullptr;
+    int max_ctx_ = 0, max_prefix_ = 0;
+    float *d_cos_ = nullptr, *d_sin_ = nullptr;
+    bf16_t *d_k_ = nullptr, *d_v_ = nullptr;
+    bf16_t *d_x_ = nullptr, *d_hn_ = nullptr, *d_qkv_ = nullptr, *d_qr_ = nullptr, *d_attn_ = nullptr, *d_act_ = nullptr, *d_res_ = nullptr;
+    float* d_logits_ = nullptr;
+    int *d_state_ = nullptr, *d_tokens_ = nullptr, *d_pick_ = nullptr, *d_prefix_ = nullptr, *d_pairs_ = nullptr, *d_iota_ = nullptr,
+        *d_probe_ = nullptr;
+    long long* d_row_index_ = nullptr;
+    CvlmSampleParams* d_knobs_ = nullptr;
+    float *d_f_log_ = nullptr, *d_f_hid_ = nullptr;             // forced-pass outputs (sized per call)
+    int* d_f_tok_ = nullptr;
+    int forced_T_ = 0;
+    std::unique_ptr<DevBuf> forced_buf_[3];
+    std::map<int, hipGraphExec_t> graphs_;                      // the step's launch sequence per batch size
+    std::set<int> warmed_;
+    unsigned graph_epoch_ = 0;
+};
+
+}  // namespace qasr

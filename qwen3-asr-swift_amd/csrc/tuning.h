@@ -45,6 +45,7 @@ struct Tuning {
     int pp_fuse_qk = 1;      // prompt pass: q/k RMSNorm + RoPE + cache write in the q|k|v projection's epilogue (head-tile GEMM, gemm.h MODE 2) | 0 separate launch
     int qknr_wide = 1;       // q/k norm + RoPE of the prompt pass: 16-byte accesses
     int tts_packed_prompt = 1;   // Qwen3-TTS ICL prompt: 1 one packed pass over every prompt position (TtsTalker::packed_prompt) | 0 one decode step per position
+    int cvlm_prompt_chunk = 64;  // CosyVoice3 LLM prompt pass: 64 packed (slot, position) pairs per pass | 1 one position of every row per pass; the same bits
     int codec_tail_rows = 1; // Qwen3-TTS codec, windows decoded for their tail (qasr_codec_forward_tail, streamed chunks): 1 the vocoder skips the rows only
                              // the dropped context needs (TailRows) | 0 whole windows; the same bits either way
     int conv_ktile = 1;      // implicit-GEMM convolutions (C >= 64): tap decomposition once per staged K-tile on the scalar unit (AConv3x3s2W) | 0 per chunk

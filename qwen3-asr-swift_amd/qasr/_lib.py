@@ -89,6 +89,23 @@ class QasrTtsRequest(C.Structure):
                 ("instruct_len", C.POINTER(C.c_int32)), ("row_index", C.POINTER(C.c_int64))]
 
 
+class QasrCvlmConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("hidden", "layers", "heads", "kv_heads", "head_dim", "inter", "text_vocab", "speech_tokens",
+                                         "speech_extra")] + \
+               [(n, C.c_float) for n in ("rms_eps", "rope_theta")] + \
+               [(n, C.c_int32) for n in ("bits", "group_size", "device", "max_batch", "max_text", "max_prompt_tokens", "max_tokens")]
+
+
+class QasrCvlmSampling(C.Structure):
+    _fields_ = [("top_k", C.c_int32), ("top_p", C.c_float), ("win_size", C.c_int32), ("tau_r", C.c_float), ("min_ratio", C.c_float)]
+
+
+class QasrCvlmRequest(C.Structure):
+    _fields_ = [("B", C.c_size_t), ("text", C.POINTER(C.POINTER(C.c_int32))), ("text_len", C.POINTER(C.c_int32)),
+                ("prompt", C.POINTER(C.POINTER(C.c_int32))), ("prompt_len", C.POINTER(C.c_int32)),
+                ("content_len", C.POINTER(C.c_int32)), ("max_tokens", C.POINTER(C.c_int32)), ("row_index", C.POINTER(C.c_int64))]
+
+
 class QasrTtsIcl(C.Structure):
     _fields_ = [("ref_text", C.POINTER(C.POINTER(C.c_int32))), ("ref_text_len", C.POINTER(C.c_int32)),
                 ("ref_codes", C.POINTER(C.POINTER(C.c_int32))), ("ref_frames", C.POINTER(C.c_int32))]
@@ -469,6 +486,25 @@ SIGNATURES = {
     "qasr_flow_generate_batch": (C.c_int, [_E, _P(_I), _P(C.c_size_t), _P(_I), _P(C.c_size_t), _P(_F), _P(C.c_size_t), _P(_F), C.c_int, C.c_float,
                                            _P(C.c_uint64), C.c_size_t, _P(_F), _P(_F)]),
     "qasr_flow_timing": (C.c_int, [_E, _F]),
+    "qasr_cvlm_default_config": (C.c_int, [C.c_int, _P(QasrCvlmConfig)]),
+    "qasr_cvlm_default_sampling": (None, [_P(QasrCvlmSampling)]),
+    "qasr_cvlm_create": (C.c_int, [C.c_char_p, _P(QasrCvlmConfig), _P(_E)]),
+    "qasr_cvlm_check": (C.c_int, [C.c_char_p, _P(QasrCvlmConfig)]),
+    "qasr_cvlm_free": (None, [_E]),
+    "qasr_cvlm_last_error": (C.c_char_p, [_E]),
+    "qasr_cvlm_memory_footprint": (C.c_size_t, [_E]),
+    "qasr_cvlm_device_bytes": (C.c_size_t, [_E]),
+    "qasr_cvlm_poll_interval": (C.c_int, []),
+    "qasr_cvlm_context": (C.c_int, [_P(QasrCvlmConfig)]),
+    "qasr_cvlm_plan_prefix": (C.c_int, [_P(QasrCvlmConfig), _I, C.c_int32, _I, C.c_int32, _I]),
+    "qasr_cvlm_generate": (C.c_int, [_E, _P(QasrCvlmRequest), _P(QasrCvlmSampling), C.c_uint64, _I, _I]),
+    "qasr_cvlm_forced": (C.c_int, [_E, _P(QasrCvlmRequest), _I, C.c_size_t, _F, _F]),
+    "qasr_cvlm_sample": (C.c_int, [_E, _F, _P(_I), _I, _I, _I, C.c_size_t, _P(QasrCvlmSampling), C.c_uint64, _P(C.c_int64), _I]),
+    "qasr_cvlm_sample_host": (C.c_int, [_P(QasrCvlmConfig), _F, _I, C.c_int32, C.c_int32, C.c_int, _P(QasrCvlmSampling), C.c_uint64,
+                                        C.c_int64]),
+    "qasr_cvlm_linear_probe": (C.c_int, [_E, C.c_int32, C.c_int32, _F, _F, C.c_size_t, _F]),
+    "qasr_cvlm_synthesize": (C.c_int, [_E, _E, _E, _P(QasrCvlmRequest), _P(QasrCvlmSampling), C.c_uint64, _P(_F), _P(_F), _P(C.c_size_t),
+                                       _P(_F), _P(C.c_size_t), _I, _I]),
 }
 
 _lib = None

@@ -1084,3 +1084,75 @@ def write_cosyvoice_flow_safetensors(sd: dict, model_dir: str, drop=(), reshape=
         for raw in blobs:
             fh.write(raw)
     return model_dir
+
+
+# ---- CosyVoice3 speech-token LLM (Sources/CosyVoiceTTS/LLM.swift; keys: WeightLoading.swift:18-110) --------------------------------
+CVLM_REAL = dict(hidden=896, layers=24, heads=14, kv_heads=2, head_dim=64, inter=4864, text_vocab=151936, speech_tokens=6561,
+                 speech_extra=200, bits=4)
+
+
+def cosyvoice_llm_tensor_shapes(geometry=None) -> dict:
+    """key -> (shape, quantised?) of every tensor of llm.safetensors the loader reads, in the reference's key names.  A quantised
+    [out, in] Linear is stored as the triplet weight | scales | biases; `.bias` keys (q, k, v) are float."""
+    g = dict(CVLM_REAL, **(geometry or {}))
+    H, hd, V = g["hidden"], g["head_dim"], g["speech_tokens"] + g["speech_extra"]
+    s = {"text_embedding.weight": ((g["text_vocab"], H), False), "speech_embedding.weight": ((V, H), False)}
+    for l in range(g["layers"]):
+        q = f"layers.{l}."
+        for name, n in (("q_proj", g["heads"] * hd), ("k_proj", g["kv_heads"] * hd), ("v_proj", g["kv_heads"] * hd)):
+            s[q + f"self_attn.{name}.weight"] = ((n, H), True)
+            s[q + f"self_attn.{name}.bias"] = ((n,), False)
+        s[q + "self_attn.o_proj.weight"] = ((H, g["heads"] * hd), True)
+        s[q + "input_layernorm.weight"] = ((H,), False)
+        s[q + "post_attention_layernorm.weight"] = ((H,), False)
+        s[q + "mlp.gate_proj.weight"] = ((g["inter"], H), True)
+        s[q + "mlp.up_proj.weight"] = ((g["inter"], H), True)
+        s[q + "mlp.down_proj.weight"] = ((H, g["inter"]), True)
+    s["norm.weight"] = ((H,), False)
+    s["speech_head.weight"] = ((V, H), True)
+    return s
+
+
+def synth_cosyvoice_llm_state_dict(geometry=None, seed: int = 0, quantized: bool = True) -> dict:
+    """Seeded LLM weights in the checkpoint's form: float tensors bf16, every Linear quantised with quantize_linear at
+    geometry["bits"] (quantized=False keeps them bf16: the float checkpoint the loader refuses).  Matrices are N(0, 1 / fan_in); the
+    head's rows carry a log-normal gain, which gives the logits a heavy tail (a clear first maximum, as a trained model has); norms
+    1 + 0.1 N, embeddings 0.5 N, biases 0.05 N."""
+    g = dict(CVLM_REAL, **(geometry or {}))
+    rng = torch.Generator().manual_seed(636363 + seed)
+    sd = {}
+    for key, (shape, quant) in cosyvoice_llm_tensor_shapes(g).items():
+        if key.endswith(".bias"):
+            w = 0.05 * torch.randn(shape, generator=rng)
+        elif "norm" in key:
+            w = 1.0 + 0.1 * torch.randn(shape, generator=rng)
+        elif "embedding" in key:
+            w = 0.5 * torch.randn(shape, generator=rng)
+        else:
+            w = torch.randn(shape, generator=rng) / math.sqrt(shape[1])
+            if "head" in key:
+                w = 2.0 * w * torch.exp(torch.randn((shape[0], 1), generator=rng))
+        w = w.to(torch.bfloat16)
+        if quant and quantized:
+            stem = key[:-len(".weight")]
+            sd[key], sd[stem + ".scales"], sd[stem + ".biases"] = quantize_linear(w, g["bits"])
+        else:
+            sd[key] = w
+    return sd
+
+
+def write_cosyvoice_llm_safetensors(sd: dict, model_dir: str, drop=(), extra=(), scales_dtype: str = "BF16", reshape=None) -> str:
+    """Writes `sd` (synth_cosyvoice_llm_state_dict) as model_dir/llm.safetensors in the Talker writer's dtypes.  `drop`: keys left out;
+    `extra`: (key, float array) pairs added as F32; `reshape`: key -> shape the tensor is resized to.  Returns model_dir."""
+    import os
+    import tempfile
+    if reshape:
+        sd = dict(sd)
+        for k, shp in reshape.items():
+            v = sd[k]
+            sd[k] = torch.from_numpy(np.resize(v.to(torch.float32).numpy() if v.dtype != torch.int32 else v.numpy(), shp)).to(v.dtype)
+    with tempfile.TemporaryDirectory() as tmp:
+        write_tts_talker_safetensors(sd, tmp, drop=drop, extra=extra, scales_dtype=scales_dtype)
+        os.makedirs(model_dir, exist_ok=True)
+        os.replace(os.path.join(tmp, "model.safetensors"), os.path.join(model_dir, "llm.safetensors"))
+    return model_dir
