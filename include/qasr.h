@@ -1416,6 +1416,63 @@ int qasr_cvlm_synthesize(qasr_cvlm* h, qasr_flow* flow, qasr_hift* hift, const q
                          uint64_t seed, const float* const* spk_emb, const float* const* prompt_feat, const size_t* prompt_frames,
                          float* const* pcm, size_t* n_samples, int32_t* tokens, int32_t* n_tokens);
 
+/* ---- CosyVoice3 speech tokenizer and voice profiles (csrc/s3tok_cosyvoice.hip, csrc/api_s3tok.cpp) ---------------------------------------
+ * Reference: Sources/CosyVoiceTTS/SpeechTokenizer.swift, WhisperMelExtractor.swift, FlowMelExtractor.swift, VoiceCloning.swift:69-158,
+ * :329-345, WeightLoading.swift:350-398.  A reference clip -> the prompt speech tokens (25 Hz, [0, 6561)) and the prompt mel ([80][frames],
+ * 50 Hz) that qasr_cvlm_synthesize / qasr_flow_generate take for zero-shot cloning.  The CAM++ speaker vector stays a caller input.
+ * What each entry replaces:
+ *   CosyVoiceWeightLoader.loadSpeechTokenizer (WeightLoading.swift:350-398), speech_tokenizer.safetensors -> qasr_s3tok_create
+ *   resample (VoiceCloning.swift:329-345)                                                                -> qasr_s3tok_resample
+ *   WhisperMelExtractor.extract (WhisperMelExtractor.swift:132-225)                                      -> qasr_s3tok_whisper_mel
+ *   FlowMelExtractor.extract (FlowMelExtractor.swift:142-229)                                            -> qasr_s3tok_flow_mel
+ *   AudioEncoderV3.callAsFunction (SpeechTokenizer.swift:279-288)                                        -> qasr_s3tok_hidden
+ *   FSQCodebook.encode up to project_down (:77), and from tanh on (:78-93)                              -> qasr_s3tok_project, qasr_s3tok_fsq_host
+ *   SpeechTokenizerModel.encode on the Whisper mel of a clip (:312-315)                                  -> qasr_s3tok_encode / _encode_batch
+ *   extractVoiceProfile (VoiceCloning.swift:69-158) without camppSpeaker                                 -> qasr_s3tok_profile / _profile_batch
+ * One deviation: the reference hands tokens and prompt mel over with whatever lengths they have; qasr_flow_generate takes a prompt mel of
+ * exactly 2 frames per prompt token, so the profile entries cut both to L = min(tokens, frames / 2) as upstream CosyVoice's zero-shot front
+ * end does, and report the uncut lengths.  The stage entries return uncut results.  A clip gives the same bits alone, at any place of a
+ * batch and under any max_tokens.  One handle, one thread at a time. */
+typedef struct qasr_s3tok qasr_s3tok;
+/* model_dir holds speech_tokenizer.safetensors (F32 / F16 / BF16).  A missing file or key is QASR_ERR_IO; a wrong shape or dtype, an unknown
+ * key (a bias on `key` is one) or an argument out of range is QASR_ERR_INVALID, the message names the key: qasr_s3tok_last_error(NULL);
+ * all before any HIP call.  max_tokens: hidden rows (tokens, summed over clips) one device pass holds, 0 = 768 (30 s), at most 2^14. */
+int qasr_s3tok_create(int device, const char* model_dir, size_t max_tokens, qasr_engine* order_with, qasr_s3tok** out);
+void qasr_s3tok_destroy(qasr_s3tok* h);
+const char* qasr_s3tok_last_error(const qasr_s3tok* h);             /* h may be NULL: last create() failure */
+int qasr_s3tok_is_loaded(const qasr_s3tok* h);
+int qasr_s3tok_unload(qasr_s3tok* h);                               /* later device calls return QASR_ERR_NOT_LOADED */
+size_t qasr_s3tok_memory_footprint(const qasr_s3tok* h);            /* bytes as stored of the tensors read, 0 unloaded */
+int qasr_s3tok_depth(const qasr_s3tok* h);
+size_t qasr_s3tok_max_tokens(const qasr_s3tok* h);
+/* Pure CPU.  Whisper mel frames of n samples at 16 kHz: n / 160 (the last frame is dropped); tokens of T mel frames: two k 3, stride 2,
+ * pad 1 convs; flow mel frames of n samples at 24 kHz: n / 480 for n >= 480, else 0; the resampler's output length floor(n dst / src);
+ * the profile's common length min(tokens, frames / 2). */
+size_t qasr_s3tok_whisper_frames(size_t n_samples_16k);
+size_t qasr_s3tok_tokens(size_t mel_frames);
+size_t qasr_s3tok_flow_frames(size_t n_samples_24k);
+size_t qasr_s3tok_resampled_length(size_t n, int src_rate, int dst_rate);
+size_t qasr_s3tok_profile_cut(size_t n_tokens, size_t frames);
+/* The reference's linear resampler on the host, bit for bit; out holds qasr_s3tok_resampled_length values. */
+int qasr_s3tok_resample(const float* x, size_t n, int src_rate, int dst_rate, float* out);
+/* projections [rows][8] -> codes: tanh, x Float(0.999), round half to even, + 1, sum digit[k] 3^k.  Pure CPU, the twin of the device's lines. */
+int qasr_s3tok_fsq_host(const float* proj, size_t rows, int32_t* codes);
+int qasr_s3tok_whisper_mel(qasr_s3tok* h, const float* pcm16k, size_t n, float* mel /* [128][n / 160] */);
+int qasr_s3tok_flow_mel(qasr_s3tok* h, const float* pcm24k, size_t n, float* mel /* [80][n / 480] */);
+int qasr_s3tok_hidden(qasr_s3tok* h, const float* mel /* [128][T] */, size_t T, float* hidden /* [tokens][1280], after the last block */);
+int qasr_s3tok_project(qasr_s3tok* h, const float* mel /* [128][T] */, size_t T, float* proj /* [tokens][8], before tanh */);
+int qasr_s3tok_encode(qasr_s3tok* h, const float* pcm16k, size_t n, int32_t* codes /* [tokens of n / 160 frames] */);
+/* ragged clips packed back to back, in passes of at most max_tokens rows; a clip alone over max_tokens is refused */
+int qasr_s3tok_encode_batch(qasr_s3tok* h, const float* const* pcm16k, const size_t* n, size_t B, int32_t* const* codes);
+/* tokens holds the uncut token count, prompt_feat 80 x the uncut frame count (both from the length functions on the resampled lengths);
+ * written: tokens[0 .. L), prompt_feat as [80][2 L].  n_tokens = L, prompt_frames = 2 L; uncut_* may be NULL.  L = 0 is QASR_ERR_INVALID. */
+int qasr_s3tok_profile(qasr_s3tok* h, const float* pcm, size_t n, int sample_rate, int32_t* tokens, size_t* n_tokens, float* prompt_feat,
+                       size_t* prompt_frames, size_t* uncut_tokens, size_t* uncut_frames);
+int qasr_s3tok_profile_batch(qasr_s3tok* h, const float* const* pcm, const size_t* n, const int* sample_rate, size_t B, int32_t* const* tokens,
+                             size_t* n_tokens, float* const* prompt_feat, size_t* prompt_frames, size_t* uncut_tokens, size_t* uncut_frames);
+/* ms[4] of the last encode / hidden / project / profile call, summed over passes: mel, stems, blocks, FSQ */
+int qasr_s3tok_timing(const qasr_s3tok* h, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

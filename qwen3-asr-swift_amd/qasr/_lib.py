@@ -505,6 +505,31 @@ SIGNATURES = {
     "qasr_cvlm_linear_probe": (C.c_int, [_E, C.c_int32, C.c_int32, _F, _F, C.c_size_t, _F]),
     "qasr_cvlm_synthesize": (C.c_int, [_E, _E, _E, _P(QasrCvlmRequest), _P(QasrCvlmSampling), C.c_uint64, _P(_F), _P(_F), _P(C.c_size_t),
                                        _P(_F), _P(C.c_size_t), _I, _I]),
+    "qasr_s3tok_create": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t, _E, _P(_E)]),
+    "qasr_s3tok_destroy": (None, [_E]),
+    "qasr_s3tok_last_error": (C.c_char_p, [_E]),
+    "qasr_s3tok_is_loaded": (C.c_int, [_E]),
+    "qasr_s3tok_unload": (C.c_int, [_E]),
+    "qasr_s3tok_memory_footprint": (C.c_size_t, [_E]),
+    "qasr_s3tok_depth": (C.c_int, [_E]),
+    "qasr_s3tok_max_tokens": (C.c_size_t, [_E]),
+    "qasr_s3tok_whisper_frames": (C.c_size_t, [C.c_size_t]),
+    "qasr_s3tok_tokens": (C.c_size_t, [C.c_size_t]),
+    "qasr_s3tok_flow_frames": (C.c_size_t, [C.c_size_t]),
+    "qasr_s3tok_resampled_length": (C.c_size_t, [C.c_size_t, C.c_int, C.c_int]),
+    "qasr_s3tok_profile_cut": (C.c_size_t, [C.c_size_t, C.c_size_t]),
+    "qasr_s3tok_resample": (C.c_int, [_F, C.c_size_t, C.c_int, C.c_int, _F]),
+    "qasr_s3tok_fsq_host": (C.c_int, [_F, C.c_size_t, _I]),
+    "qasr_s3tok_whisper_mel": (C.c_int, [_E, _F, C.c_size_t, _F]),
+    "qasr_s3tok_flow_mel": (C.c_int, [_E, _F, C.c_size_t, _F]),
+    "qasr_s3tok_hidden": (C.c_int, [_E, _F, C.c_size_t, _F]),
+    "qasr_s3tok_project": (C.c_int, [_E, _F, C.c_size_t, _F]),
+    "qasr_s3tok_encode": (C.c_int, [_E, _F, C.c_size_t, _I]),
+    "qasr_s3tok_encode_batch": (C.c_int, [_E, _P(_F), _P(C.c_size_t), C.c_size_t, _P(_I)]),
+    "qasr_s3tok_profile": (C.c_int, [_E, _F, C.c_size_t, C.c_int, _I, _P(C.c_size_t), _F, _P(C.c_size_t), _P(C.c_size_t), _P(C.c_size_t)]),
+    "qasr_s3tok_profile_batch": (C.c_int, [_E, _P(_F), _P(C.c_size_t), _P(C.c_int), C.c_size_t, _P(_I), _P(C.c_size_t), _P(_F), _P(C.c_size_t),
+                                           _P(C.c_size_t), _P(C.c_size_t)]),
+    "qasr_s3tok_timing": (C.c_int, [_E, _F]),
 }
 
 _lib = None

@@ -48,6 +48,19 @@ class CosySamplingConfig:
         return _lib.QasrCvlmSampling(int(self.top_k), float(self.top_p), int(self.win_size), float(self.tau_r), float(self.min_ratio))
 
 
+@dataclass
+class VoiceProfile:
+    """CosyVoiceVoiceProfile (VoiceCloning.swift:152-157) as qasr.s3tok.SpeechTokenizer.profile returns it: tokens [L] int32 at 25 Hz and
+    prompt_feat [80, 2 L], cut to the common length; spk_emb [192] (CAM++, the caller's) and the reference clip's transcript ids are
+    optional.  uncut_tokens / uncut_frames: what the tokenizer and the mel extractor gave before the cut."""
+    tokens: np.ndarray
+    prompt_feat: np.ndarray
+    spk_emb: Optional[np.ndarray] = None
+    prompt_text_ids: Optional[List[int]] = None
+    uncut_tokens: int = 0
+    uncut_frames: int = 0
+
+
 def _ivec(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
 
@@ -237,3 +250,17 @@ class CosyVoiceTTS:
             ns, _iptr(tok), _iptr(n)))
         wav = [pcm[b][:ns[b]].copy() for b in range(B)]
         return (wav, [tok[b, :n[b]].copy() for b in range(B)]) if return_tokens else wav
+
+    def synthesize_with_profile(self, content_ids, profile: VoiceProfile, instruction_ids=(), max_tokens=None,
+                                sampling: Optional[CosySamplingConfig] = None, seed: int = 0, return_tokens=False,
+                                end_of_prompt: int = END_OF_PROMPT):
+        """One row of content ids in the voice of `profile` (VoiceCloning.swift:169-): synthesize() with the profile's tokens, prompt mel
+        and speaker vector.  With the clip's transcript the text is clone_text(transcript, content), else frame_text(instruction, content);
+        end_of_prompt: the id of <|endofprompt|>, for a model with a reduced text vocabulary."""
+        content = [int(i) for i in content_ids]
+        head = profile.prompt_text_ids if profile.prompt_text_ids else instruction_ids
+        text = [int(i) for i in head] + [int(end_of_prompt)] + content
+        r = self.synthesize([text], content_len=[len(content)], prompts=[profile.tokens], prompt_feat=[profile.prompt_feat],
+                            spk_emb=[profile.spk_emb], max_tokens=None if max_tokens is None else [max_tokens], sampling=sampling, seed=seed,
+                            return_tokens=return_tokens)
+        return (r[0][0], r[1][0]) if return_tokens else r[0]

@@ -1086,6 +1086,113 @@ def write_cosyvoice_flow_safetensors(sd: dict, model_dir: str, drop=(), reshape=
     return model_dir
 
 
+# ---- CosyVoice3 speech tokenizer, S3-Tokenizer-v3 (Sources/CosyVoiceTTS/SpeechTokenizer.swift; keys: WeightLoading.swift:350-398) ----
+S3TOK_DIM, S3TOK_HEADS, S3TOK_FF, S3TOK_MELS, S3TOK_FSQ, S3TOK_FSMN_K = 1280, 20, 5120, 128, 8, 31
+S3TOK_REAL2 = dict(depth=2)                # the model's widths (the engine knows no others), 2 blocks
+S3TOK_REAL12 = dict(depth=12)
+
+
+def cosyvoice_s3tok_tensor_shapes(geometry=None) -> dict:
+    """key -> shape of speech_tokenizer.safetensors; `key` carries no bias."""
+    depth = dict(S3TOK_REAL12, **(geometry or {}))["depth"]
+    D = S3TOK_DIM
+    s = {"encoder.conv1.weight": (D, 3, S3TOK_MELS), "encoder.conv1.bias": (D,), "encoder.conv2.weight": (D, 3, D), "encoder.conv2.bias": (D,)}
+    for i in range(depth):
+        b = f"encoder.blocks.{i}."
+        for n in ("query", "key", "value", "out"):
+            s[b + f"attn.{n}.weight"] = (D, D)
+            if n != "key":
+                s[b + f"attn.{n}.bias"] = (D,)
+        s[b + "attn.fsmn_block.weight"] = (D, S3TOK_FSMN_K, 1)
+        for n in ("attn_ln", "mlp_ln"):
+            s[b + n + ".weight"], s[b + n + ".bias"] = (D,), (D,)
+        s[b + "mlp.0.weight"], s[b + "mlp.0.bias"] = (S3TOK_FF, D), (S3TOK_FF,)
+        s[b + "mlp.2.weight"], s[b + "mlp.2.bias"] = (D, S3TOK_FF), (D,)
+    s["quantizer._codebook.project_down.weight"], s["quantizer._codebook.project_down.bias"] = (S3TOK_FSQ, D), (S3TOK_FSQ,)
+    return s
+
+
+def synth_s3tok_mel(seed: int, frames: int) -> np.ndarray:
+    """A seeded [128, frames] stand-in for a Whisper-style log-mel: N(0, 0.6^2), the range (x + 4) / 4 gives speech."""
+    return (0.6 * np.random.default_rng(880000 + seed).standard_normal((S3TOK_MELS, frames))).astype(np.float32)
+
+
+def _s3tok_hidden_f32(sd: dict, mel: np.ndarray, depth: int) -> torch.Tensor:
+    """The encoder in torch float32 on one mel, for the calibration of project_down only (the tests' oracle is tests/s3tok_oracle.py)."""
+    F = torch.nn.functional
+    t = lambda k: torch.from_numpy(sd[k])
+    h = torch.from_numpy(mel)[None]
+    for c in ("encoder.conv1", "encoder.conv2"):
+        h = F.gelu(F.conv1d(h, t(c + ".weight").permute(0, 2, 1), t(c + ".bias"), stride=2, padding=1))
+    h = h[0].T
+    T, D, H = h.shape[0], S3TOK_DIM, S3TOK_HEADS
+    ang = torch.arange(T, dtype=torch.float32)[:, None] * (10000.0 ** (-torch.arange(32, dtype=torch.float32) / 32.0))[None]
+    cs, sn = torch.cos(ang)[:, None], torch.sin(ang)[:, None]
+
+    def rope(x):
+        a, b = x.view(T, H, 64)[..., :32], x.view(T, H, 64)[..., 32:]
+        return torch.cat([a * cs - b * sn, b * cs + a * sn], -1)
+
+    for i in range(depth):
+        p = f"encoder.blocks.{i}."
+        x = F.layer_norm(h, (D,), t(p + "attn_ln.weight"), t(p + "attn_ln.bias"), 1e-5)
+        q, k = rope(x @ t(p + "attn.query.weight").T + t(p + "attn.query.bias")), rope(x @ t(p + "attn.key.weight").T)
+        v = x @ t(p + "attn.value.weight").T + t(p + "attn.value.bias")
+        mem = F.conv1d(v.T[None], t(p + "attn.fsmn_block.weight").permute(0, 2, 1), None, padding=15, groups=D)[0].T + v
+        a = torch.softmax(torch.einsum("thd,shd->hts", q, k) / 8.0, -1)
+        o = torch.einsum("hts,shd->thd", a, v.view(T, H, 64)).reshape(T, D)
+        h = h + o @ t(p + "attn.out.weight").T + t(p + "attn.out.bias") + mem
+        x = F.layer_norm(h, (D,), t(p + "mlp_ln.weight"), t(p + "mlp_ln.bias"), 1e-5)
+        h = h + F.gelu(x @ t(p + "mlp.0.weight").T + t(p + "mlp.0.bias")) @ t(p + "mlp.2.weight").T + t(p + "mlp.2.bias")
+    return h
+
+
+def synth_cosyvoice_s3tok_state_dict(seed: int = 0, geometry=None, bf16_values: bool = False) -> dict:
+    """Seeded speech-tokenizer weights {key: float32 array} with the loader's key names.  Matrices and convs are N(0, g / fan_in) (g = 2 in
+    front of a GELU), the FSMN taps N(0, 0.5 / 31), LayerNorm weights 1 +- 0.1, biases +- 0.05.  project_down is scaled, and its bias set,
+    so that the eight projections of synth_s3tok_mel(0, 256) have zero mean and unit standard deviation: tanh then puts roughly 0.29 / 0.42
+    / 0.29 of the digits on the three FSQ levels.  bf16_values: every tensor rounded to bf16 values (a file written as BF16 then holds
+    exactly what the oracle reads)."""
+    depth = dict(S3TOK_REAL12, **(geometry or {}))["depth"]
+    rng = np.random.default_rng(660033 + seed)
+    sd = {}
+    for key, shape in cosyvoice_s3tok_tensor_shapes(dict(depth=depth)).items():
+        if "_ln.weight" in key:
+            w = 1.0 + 0.1 * rng.standard_normal(shape, dtype=np.float32)
+        elif key.endswith(".bias"):
+            w = 0.05 * rng.standard_normal(shape, dtype=np.float32)
+        elif "fsmn_block" in key:
+            w = rng.standard_normal(shape, dtype=np.float32) * math.sqrt(0.5 / S3TOK_FSMN_K)
+        elif len(shape) == 3:
+            w = rng.standard_normal(shape, dtype=np.float32) * math.sqrt(2.0 / (shape[1] * shape[2]))
+        else:
+            gain = 2.0 if "mlp.0" in key else 0.5 if ("mlp.2" in key or "attn.out" in key) else 1.0
+            w = rng.standard_normal(shape, dtype=np.float32) * math.sqrt(gain / shape[1])
+        sd[key] = np.ascontiguousarray(w, dtype=np.float32)
+    if bf16_values:
+        sd = {k: torch.from_numpy(v).to(torch.bfloat16).to(torch.float32).numpy() for k, v in sd.items()}
+    with torch.no_grad():
+        h = _s3tok_hidden_f32(sd, synth_s3tok_mel(0, 256), depth).numpy().astype(np.float64)
+    wk, bk = "quantizer._codebook.project_down.weight", "quantizer._codebook.project_down.bias"
+    y = h @ sd[wk].astype(np.float64).T
+    sd[wk] = (sd[wk] / y.std(0)[:, None]).astype(np.float32)
+    sd[bk] = (-(y.mean(0) / y.std(0))).astype(np.float32)
+    if bf16_values:
+        for k in (wk, bk):
+            sd[k] = torch.from_numpy(sd[k]).to(torch.bfloat16).to(torch.float32).numpy()
+    return sd
+
+
+def write_cosyvoice_s3tok_safetensors(sd: dict, model_dir: str, dtype: str = "F32", drop=(), reshape=None, extra=()) -> str:
+    """Writes `sd` as model_dir/speech_tokenizer.safetensors (dtype F32 | F16 | BF16; F64 for the dtype error).  `drop`: keys left out,
+    `reshape`: {key: shape} written with a wrong shape, `extra`: (key, array) pairs added as they are.  Returns model_dir."""
+    d = dict(sd)
+    for k, v in (extra.items() if isinstance(extra, dict) else extra):
+        d[k] = np.asarray(v, dtype=np.float32)
+    _write_safetensors(d, model_dir, dtype, drop, reshape, filename="speech_tokenizer.safetensors")
+    return model_dir
+
+
 # ---- CosyVoice3 speech-token LLM (Sources/CosyVoiceTTS/LLM.swift; keys: WeightLoading.swift:18-110) --------------------------------
 CVLM_REAL = dict(hidden=896, layers=24, heads=14, kv_heads=2, head_dim=64, inter=4864, text_vocab=151936, speech_tokens=6561,
                  speech_extra=200, bits=4)
