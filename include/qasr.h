@@ -1044,6 +1044,67 @@ int qasr_hift_decode_batch(qasr_hift* h, const float* const* mel, const size_t* 
  * conv_post + inverse STFT; a stage the entry does not run is 0 */
 int qasr_hift_timing(const qasr_hift* h, float* ms);
 
+/* ---- VoxCPM2 AudioVAE (csrc/vae_voxcpm.hip, csrc/api_avae.cpp) ---------------------------------------------------------------------------
+ * Reference: Sources/VoxCPM2TTS/AudioVAE.swift.  16 kHz mono PCM -> latent frames [F][latent_dim] at 25 frames per second (hop 640), and
+ * latent frames -> 48 kHz PCM, 1920 samples per frame.  What each entry replaces:
+ *   AudioVAEConfig.init(from:) (Configuration.swift:171-186), AudioVAE.sanitize (AudioVAE.swift:646-686) and the loaders of
+ *   VoxCPM2TTS.swift:450-511, :743-850, local directory                                          -> qasr_avae_create
+ *   AudioVAE.preprocess + CausalEncoder.callAsFunction (:636-644, :456-460)                      -> qasr_avae_encode / _encode_batch
+ *   AudioVAE.decode / CausalDecoder.callAsFunction (:630-634, :536-561)                          -> qasr_avae_decode / _decode_batch
+ *   CausalEncoder.conv_in / blocks[k - 1], CausalDecoder.conv_in / blocks[k - 1]                 -> qasr_avae_enc_stage / _dec_stage
+ *   snake_out, conv_out, tanh (:558-560)                                                         -> qasr_avae_dec_output
+ * Every conv is causal: zeros go in front of the already-Snaked input only, so decode(z[:k]) is the first 1920 k samples of decode(z).
+ * Snake is x + 1 / (alpha + 1e-9) sin^2(alpha x) with alpha as stored.  A clip of n samples is padded with zero samples to a whole
+ * frame (real rows: conv_in has a bias) and gives ceil(n / hop) frames.  sr_cond picks the row of the decoder's scale / bias tables:
+ * the number of sr_bin_boundaries it has reached; 0 means out_sample_rate.
+ * Precision: f32 throughout, as the reference runs this model.  A clip's output is bit-identical alone, in any batch and place, under
+ * any split into passes, and run to run.  The tuning knob vae_fuse_c picks, per width, between two forms of a residual unit that sum in
+ * different orders; both are held to the same bounds.  One object, one thread at a time.  Not covered: the
+ * VoxCPM2 LM, feature encoder, DiT and FSQ, streaming decode, resampling (input other than sample_rate is the caller's to convert), the
+ * noise block, bf16 operands. */
+typedef struct qasr_avae qasr_avae;
+/* model_dir/config.json's audio_vae_config is optional, every field of it defaults as in the reference.  The tensors are looked up in all
+ * *.safetensors of the directory under audio_vae.{encoder,decoder}.* or the bare encoder.* / decoder.*; a conv's .weight may be stored as
+ * a .weight_g [out][1][1] / .weight_v pair, fused to g v / (|v| + 1e-9) (formed in f64, rounded once); fc_logvar is not read; a
+ * 64-wide sr_cond_layers table may be [n][8][8] or [n][64].  F32, F16 or BF16, widened at upload.  Everything is checked before any HIP
+ * call, the field or tensor named in qasr_avae_last_error(NULL): use_noise_block true, depthwise false, a cond_type other than
+ * scale_bias / scale_bias_init, rates or widths outside the ranges held, a wrong shape or dtype -> QASR_ERR_INVALID; a missing tensor
+ * (every decoder block needs its sr_cond_layers entry: the reference would keep a random table) -> QASR_ERR_IO.
+ * max_frames: latent frames one device pass holds (0 = 1024, 41 s; at most 2^14); the buffers are sized from it at create: three
+ * activation buffers of 81,920 f32 per frame at the default geometry plus PCM and latents, about 1 MB per frame.  order_with: as for
+ * qasr_seg_create. */
+int qasr_avae_create(int device, const char* model_dir, size_t max_frames, qasr_engine* order_with, qasr_avae** out);
+void qasr_avae_destroy(qasr_avae* h);
+const char* qasr_avae_last_error(const qasr_avae* h);               /* h may be NULL: last create() failure */
+int qasr_avae_is_loaded(const qasr_avae* h);
+int qasr_avae_unload(qasr_avae* h);                                 /* later device calls return QASR_ERR_NOT_LOADED */
+size_t qasr_avae_memory_footprint(const qasr_avae* h);              /* bytes as stored of the tensors read, 0 unloaded */
+int qasr_avae_latent_dim(const qasr_avae* h);                       /* 64 */
+int qasr_avae_in_sample_rate(const qasr_avae* h);                   /* 16000 */
+int qasr_avae_out_sample_rate(const qasr_avae* h);                  /* 48000 */
+int qasr_avae_hop(const qasr_avae* h);                              /* 640: the product of encoder_rates */
+int qasr_avae_samples_per_frame(const qasr_avae* h);                /* 1920: the product of decoder_rates */
+size_t qasr_avae_num_frames(const qasr_avae* h, size_t n);          /* ceil(n / hop); h NULL: the default hop 640.  Pure CPU. */
+int qasr_avae_num_blocks(const qasr_avae* h, int decoder);          /* encoder (0) or decoder (1) blocks: stages run 0 .. this */
+/* rows per latent frame and width of stage k's output (k = 0: after conv_in, k >= 1: after block k - 1); k out of range -> QASR_ERR_INVALID */
+int qasr_avae_stage_shape(const qasr_avae* h, int decoder, int k, int* rows_per_frame, int* width);
+/* pcm [n] at in_sample_rate -> z [ceil(n / hop)][latent_dim].  n == 0, more frames than max_frames or NULL -> QASR_ERR_INVALID */
+int qasr_avae_encode(qasr_avae* h, const float* pcm, size_t n, float* z);
+/* z [T][latent_dim] -> pcm [samples_per_frame T].  T == 0, T > max_frames, sr_cond < 0 or NULL -> QASR_ERR_INVALID */
+int qasr_avae_decode(qasr_avae* h, const float* z, size_t T, int sr_cond, float* pcm);
+/* B clips of any lengths, cut into passes of at most max_frames frames at clip boundaries; each output is bit-identical to the single entry */
+int qasr_avae_encode_batch(qasr_avae* h, const float* const* pcm, const size_t* n, size_t B, float* const* z);
+int qasr_avae_decode_batch(qasr_avae* h, const float* const* z, const size_t* T, size_t B, int sr_cond, float* const* pcm);
+/* Stage entries: out [frames x rows_per_frame][width] of qasr_avae_stage_shape, the rows as the reference holds them at that point
+ * (a decoder stage before the next block's scale / bias and Snake) */
+int qasr_avae_enc_stage(qasr_avae* h, const float* pcm, size_t n, int k, float* out);
+int qasr_avae_dec_stage(qasr_avae* h, const float* z, size_t T, int sr_cond, int k, float* out);
+/* rows [samples_per_frame T][width of the last decoder stage] as qasr_avae_dec_stage returns them -> pcm; chained they are qasr_avae_decode's bits */
+int qasr_avae_dec_output(qasr_avae* h, const float* rows, size_t T, float* pcm);
+/* ms[20]: device time of the last call, HIP events on the work stream.  ms[0] encoder conv_in, ms[1 ..] its blocks, then fc_mu;
+ * ms[10] decoder conv_in, ms[11 ..] its blocks, then conv_out + tanh; a stage the entry does not run is 0 */
+int qasr_avae_timing(const qasr_avae* h, float* ms);
+
 /* ---- Qwen3-TTS Talker + code predictor (Sources/Qwen3TTS/Talker.swift, CodePredictor.swift, Sampling.swift, Qwen3TTS.swift) -------------
  * Text ids (the chat template of prepareTextTokens around them), a language id, optionally a speaker token id or an x-vector (qasr_xvec_*)
  * and an instruct prefix -> 16 code streams at 12.5 Hz, which qasr_codec_decode turns into 24 kHz audio.  MLX affine 4 / 8 bit

@@ -1,6 +1,7 @@
 // codec_shared.h -- what the two directions of the Qwen3-TTS speech tokenizer (codec_qwen3tts.hip, codec_enc_qwen3tts.hip) have in
 // common: the geometry, the f32 tile GEMM with its SnakeBeta load and its epilogues, RMSNorm, the depthwise conv + LayerNorm, and the
 // packing of the weights both read (host functions in codec_shared.cpp).  xvec_qwen3tts.hip takes Builder and clip_of from here.
+// vae_voxcpm.hip (the VoxCPM2 AudioVAE) takes Builder, WindowRows and the tile, with its one epilogue of that model's own, E_RESMAP.
 //
 // The two models differ in how a pass lays utterances out in rows, so a kernel that reads across rows takes a row locator (WindowRows,
 // ClipRows): for an output row it names the input row under the conv's last tap and the first input row the row may read.  Everything
@@ -69,7 +70,7 @@ size_t codec_pack_rope(Builder& b, long n);
 
 // ---- kernels ------------------------------------------------------------------------------------------------------------------------
 constexpr int CG_THREADS = 256, CG_T = 64, CG_K = 16, ROW_THREADS = 256;
-enum { E_LIN = 0, E_GELU = 1, E_RES = 2, E_LSRES = 3, E_SWIGLU = 4 };
+enum { E_LIN = 0, E_GELU = 1, E_RES = 2, E_LSRES = 3, E_SWIGLU = 4, E_RESMAP = 5 };
 
 // x + (1 / exp(beta)) sin^2(exp(alpha) x) with a = exp(alpha), b = 1 / exp(beta) formed at load (SpeechTokenizerDecoder.swift:105-110)
 __device__ __forceinline__ float codec_snake(float x, float a, float b) {
@@ -147,6 +148,8 @@ struct ClipRows {
 // C = epilogue(sum_k A(m, k) Wt[k][n]), k = j C_in + c <-> x[rows(m).last - (taps - 1 - j) dil][c], zero before rows(m).first.
 // A [input rows][C_in], Wt [K][N].  bias[n], or bias[n % bmod] where Rows::BIAS_REPEATS (nullptr: none).  E_SWIGLU: columns 2 i,
 // 2 i + 1 are gate i, up i; C [M][N / 2].  Rows::SKIPS: tiles of dead rows return at once (block-uniform, before any barrier).
+// E_RESMAP: (+ R where given), then the map the one reader of C would apply at its load, snake(v ls[n] + ls[N + n]) with a = sa[n],
+// b = sb[n] (ls = nullptr: no affine), so that reader loads plain values (vae_voxcpm.hip).
 template <class Rows, bool SNAKE, int EPI>
 __global__ __launch_bounds__(CG_THREADS) void codec_gemm_kernel(const float* __restrict__ A, long M, int Cin, int taps, int dil, Rows rows,
                                                                 const float* __restrict__ Wt, int K, int N, const float* __restrict__ bias,
@@ -228,6 +231,11 @@ __global__ __launch_bounds__(CG_THREADS) void codec_gemm_kernel(const float* __r
             if (EPI == E_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
             if (EPI == E_RES) v = v + R[m * ldc + n];
             if (EPI == E_LSRES) v = v * ls[n] + R[m * ldc + n];
+            if (EPI == E_RESMAP) {
+                if (R) v = v + R[m * ldc + n];
+                if (ls) v = v * ls[n] + ls[N + n];
+                v = codec_snake(v, sa[n], sb[n]);
+            }
             C[m * ldc + n] = v;
         }
     }

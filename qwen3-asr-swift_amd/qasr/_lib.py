@@ -419,6 +419,28 @@ SIGNATURES = {
     "qasr_hift_decode": (C.c_int, [_E, _F, C.c_size_t, C.c_uint64, _F]),
     "qasr_hift_decode_batch": (C.c_int, [_E, _P(_F), _P(C.c_size_t), _P(C.c_uint64), C.c_size_t, _P(_F)]),
     "qasr_hift_timing": (C.c_int, [_E, _F]),
+    "qasr_avae_create": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t, _E, _P(_E)]),
+    "qasr_avae_destroy": (None, [_E]),
+    "qasr_avae_last_error": (C.c_char_p, [_E]),
+    "qasr_avae_is_loaded": (C.c_int, [_E]),
+    "qasr_avae_unload": (C.c_int, [_E]),
+    "qasr_avae_memory_footprint": (C.c_size_t, [_E]),
+    "qasr_avae_latent_dim": (C.c_int, [_E]),
+    "qasr_avae_in_sample_rate": (C.c_int, [_E]),
+    "qasr_avae_out_sample_rate": (C.c_int, [_E]),
+    "qasr_avae_hop": (C.c_int, [_E]),
+    "qasr_avae_samples_per_frame": (C.c_int, [_E]),
+    "qasr_avae_num_frames": (C.c_size_t, [_E, C.c_size_t]),
+    "qasr_avae_num_blocks": (C.c_int, [_E, C.c_int]),
+    "qasr_avae_stage_shape": (C.c_int, [_E, C.c_int, C.c_int, _I, _I]),
+    "qasr_avae_encode": (C.c_int, [_E, _F, C.c_size_t, _F]),
+    "qasr_avae_decode": (C.c_int, [_E, _F, C.c_size_t, C.c_int, _F]),
+    "qasr_avae_encode_batch": (C.c_int, [_E, _P(_F), _P(C.c_size_t), C.c_size_t, _P(_F)]),
+    "qasr_avae_decode_batch": (C.c_int, [_E, _P(_F), _P(C.c_size_t), C.c_size_t, C.c_int, _P(_F)]),
+    "qasr_avae_enc_stage": (C.c_int, [_E, _F, C.c_size_t, C.c_int, _F]),
+    "qasr_avae_dec_stage": (C.c_int, [_E, _F, C.c_size_t, C.c_int, C.c_int, _F]),
+    "qasr_avae_dec_output": (C.c_int, [_E, _F, C.c_size_t, _F]),
+    "qasr_avae_timing": (C.c_int, [_E, _F]),
     "qasr_tts_default_config": (C.c_int, [C.c_char_p, C.c_int, _P(QasrTtsConfig)]),
     "qasr_tts_default_sampling": (None, [C.c_int, _P(QasrTtsSampling)]),
     "qasr_tts_poll_interval": (C.c_int, []),

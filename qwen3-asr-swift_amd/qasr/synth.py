@@ -1263,3 +1263,109 @@ def write_cosyvoice_llm_safetensors(sd: dict, model_dir: str, drop=(), extra=(),
         os.makedirs(model_dir, exist_ok=True)
         os.replace(os.path.join(tmp, "model.safetensors"), os.path.join(model_dir, "llm.safetensors"))
     return model_dir
+
+
+# ---- VoxCPM2 AudioVAE (qasr_avae_*) -------------------------------------------------------------------------------------------
+VOXCPM2_AUDIOVAE_REAL = {"encoder_dim": 128, "encoder_rates": [2, 5, 8, 8], "latent_dim": 64, "decoder_dim": 2048,
+                         "decoder_rates": [8, 6, 5, 2, 2, 2], "sr_bin_boundaries": [20000, 30000, 40000]}
+
+
+def voxcpm2_audiovae_tensor_shapes(geom: dict) -> dict:
+    """key -> shape of every AudioVAE tensor as the reference's modules hold them (AudioVAE.swift; conv weights [out, k, in / groups],
+    alphas [1, 1, C], condition tables [buckets, C]), under the audio_vae. prefix."""
+    s = {}
+
+    def conv(k, out, kk, cin):
+        s[k + ".weight"], s[k + ".bias"] = (out, kk, cin), (out,)
+
+    def unit(p, C):
+        s[p + ".snake1.alpha"], s[p + ".snake2.alpha"] = (1, 1, C), (1, 1, C)
+        conv(p + ".conv1", C, 7, 1)
+        conv(p + ".conv2", C, 1, C)
+
+    conv("audio_vae.encoder.conv_in", geom["encoder_dim"], 7, 1)
+    C = geom["encoder_dim"]
+    for i, r in enumerate(geom["encoder_rates"]):
+        p = f"audio_vae.encoder.blocks.layers.{i}"
+        for u in (1, 2, 3):
+            unit(f"{p}.res{u}", C)
+        s[p + ".snake.alpha"] = (1, 1, C)
+        conv(p + ".conv", 2 * C, 2 * r, C)
+        C *= 2
+    conv("audio_vae.encoder.fc_mu", geom["latent_dim"], 3, C)
+    conv("audio_vae.decoder.conv_in.layers.0", geom["latent_dim"], 7, 1)
+    conv("audio_vae.decoder.conv_in.layers.1", geom["decoder_dim"], 1, geom["latent_dim"])
+    C, buckets = geom["decoder_dim"], len(geom["sr_bin_boundaries"]) + 1
+    for i, r in enumerate(geom["decoder_rates"]):
+        p, q = f"audio_vae.decoder.blocks.layers.{i}", f"audio_vae.decoder.sr_cond_layers.{i}"
+        s[q + ".scale_embed.weight"], s[q + ".bias_embed.weight"] = (buckets, C), (buckets, C)
+        s[p + ".snake.alpha"] = (1, 1, C)
+        conv(p + ".conv_t", C // 2, 2 * r, C)
+        for u in (1, 2, 3):
+            unit(f"{p}.res{u}", C // 2)
+        C //= 2
+    s["audio_vae.decoder.snake_out.alpha"] = (1, 1, C)
+    conv("audio_vae.decoder.conv_out", 1, 7, C)
+    return s
+
+
+def synth_voxcpm2_audiovae_state_dict(geom: dict, seed: int = 0, weight_norm: bool = True, prefixed: bool = True) -> dict:
+    """Seeded AudioVAE weights {key: float32 array} as a checkpoint stores them.  Convs are N(0, gain^2 / fan_in): 1 for the convs that
+    change the rate and the two conv_in, 0.6 for a unit's depthwise conv and 0.5 for its 1x1, so that the 12 / 18 units in a row leave the
+    signal O(1); conv_out 0.6 keeps tanh off its rails.  Snake alphas are log-normal around 1 (drawn positive, 0.4 .. 2.5 in practice); the
+    condition tables are 1 + 0.2 N and 0.2 N, a different row per sample-rate bucket.  weight_norm: every second conv weight (in key
+    order) is stored as a weight_g [out, 1, 1] / weight_v pair whose fusion is that weight up to rounding; 64-wide condition tables are
+    stored [n, 8, 8]; fc_logvar tensors holding 1e3 are added (the loader drops them).  prefixed False: keys start at encoder. /
+    decoder., which AudioVAE.sanitize completes."""
+    rng, split = np.random.default_rng(77003 + seed), np.random.default_rng(77103 + seed)     # the split draws leave the weights' stream alone
+    sd, nth = {}, 0
+    for key, shape in voxcpm2_audiovae_tensor_shapes(geom).items():
+        if key.endswith(".alpha"):
+            v = np.exp(0.35 * rng.standard_normal(shape))
+        elif key.endswith("scale_embed.weight"):
+            v = 1.0 + 0.2 * rng.standard_normal(shape)
+        elif key.endswith("bias_embed.weight"):
+            v = 0.2 * rng.standard_normal(shape)
+        elif key.endswith(".bias"):
+            v = 0.05 * rng.standard_normal(shape)
+        else:
+            fan = shape[1] * shape[2]
+            gain = 0.6 if ".conv1." in key or "conv_out" in key else 0.5 if ".conv2." in key else 1.0
+            v = gain * rng.standard_normal(shape) / math.sqrt(fan)
+        v = np.ascontiguousarray(v, dtype=np.float32)
+        if key.endswith("_embed.weight") and shape[1] == 64 and weight_norm:
+            v = v.reshape(shape[0], 8, 8)
+        if key.endswith(".weight") and len(shape) == 3 and weight_norm:
+            nth += 1
+            if nth % 2 == 0:
+                s = np.exp(0.5 * split.standard_normal((shape[0], 1, 1))).astype(np.float32)
+                vv = (v / s).astype(np.float32)
+                g = np.sqrt((vv.astype(np.float64).reshape(shape[0], -1) ** 2).sum(axis=1)).reshape(shape[0], 1, 1) * s
+                sd[key + "_v"], sd[key + "_g"] = vv, g.astype(np.float32)
+                continue
+        sd[key] = v
+    if weight_norm:
+        C = geom["encoder_dim"] << len(geom["encoder_rates"])
+        sd["audio_vae.encoder.fc_logvar.weight"] = np.full((geom["latent_dim"], 3, C), 1e3, dtype=np.float32)
+        sd["audio_vae.encoder.fc_logvar.bias"] = np.full((geom["latent_dim"],), 1e3, dtype=np.float32)
+    if not prefixed:
+        sd = {k[len("audio_vae."):]: v for k, v in sd.items()}
+    return sd
+
+
+def write_voxcpm2_audiovae_safetensors(sd: dict, model_dir: str, geom=None, dtype: str = "F32", drop=(), reshape=None, extra=(),
+                                       config_extra=None) -> str:
+    """Writes `sd` as model_dir/model.safetensors and, for a geometry given, model_dir/config.json with it (and config_extra's fields)
+    under "audio_vae_config".  `drop` / `reshape` / `extra`: as write_cosyvoice_hifigan_safetensors.  Returns model_dir."""
+    import json
+    import os
+    d = dict(sd)
+    for k, v in (extra.items() if isinstance(extra, dict) else extra):
+        d[k] = np.asarray(v, dtype=np.float32)
+    _write_safetensors(d, model_dir, dtype, drop, reshape)
+    if geom is not None or config_extra:
+        cfg = dict(geom or {})
+        cfg.update(config_extra or {})
+        with open(os.path.join(model_dir, "config.json"), "w") as f:
+            json.dump({"architecture": "voxcpm2", "audio_vae_config": cfg}, f)
+    return model_dir
