@@ -1534,6 +1534,73 @@ int qasr_s3tok_profile_batch(qasr_s3tok* h, const float* const* pcm, const size_
 /* ms[4] of the last encode / hidden / project / profile call, summed over passes: mel, stems, blocks, FSQ */
 int qasr_s3tok_timing(const qasr_s3tok* h, float* ms);
 
+/* ---- VoxCPM2 local networks: LocEnc and the LocDiT patch decoder (csrc/loc_voxcpm.hip, csrc/api_vloc.cpp) ------------------------------
+ * Reference: Sources/VoxCPM2TTS/MiniCPM4.swift, Configuration.swift:3-136, VoxCPM2TTS.swift:81-124, :377-449.  A patch is P latent frames
+ * [P][feat_dim], the layout qasr_avae_* reads and writes.  What each entry replaces:
+ *   the feat_encoder / feat_decoder / *_proj part of loadWeights (VoxCPM2TTS.swift:383-440)              -> qasr_vloc_create, qasr_vloc_check
+ *   makeUnifiedCFMTimeSpan (MiniCPM4.swift:152-166), zeroInitSteps (:687)                                -> qasr_vloc_schedule, _zero_steps
+ *   MiniCPMLongRoPE.init + callAsFunction (:43-89)                                                       -> qasr_vloc_rope_table
+ *   enc_to_lm_proj(feat_encoder(feat)) (:480-539, VoxCPM2TTS.swift:1312, :1388)                          -> qasr_vloc_encode
+ *   lm_to_dit_proj(lm hidden) || res_to_dit_proj(residual hidden) (VoxCPM2TTS.swift:1368-1371)           -> qasr_vloc_mu
+ *   VoxCPMLocDiTV2.callAsFunction with dt = 0 (:611-651)                                                 -> qasr_vloc_velocity
+ *   UnifiedCFM.solveEuler with CFG-zero-star (:674-727)                                                  -> qasr_vloc_solve
+ *   UnifiedCFM.sample (:729-745)                                                                         -> qasr_vloc_sample
+ *   MiniCPMModel.callAsFunction(inputsEmbeds:, isCausal: false) (:430-475)                               -> qasr_vloc_stack
+ * Deviations: MLXRandom is not reproduced, qasr_vloc_sample draws from the project's counter stream (see below); mean_mode true and a head
+ * width other than 128 are refused at create.  4-bit / 8-bit MLX checkpoints are dequantised to bf16 once at load.  A sequence gives the same bits alone, at any place of a
+ * batch and in a second run (as long as both launches lie on the same side of the tuning knob vloc_skinny_rows).  One handle, one thread at a time. */
+typedef struct qasr_vloc qasr_vloc;
+typedef struct qasr_vloc_geometry {
+    int32_t patch_size, feat_dim, lm_hidden, enc_hidden, dit_hidden, enc_layers, dit_layers, mu_dim, kv_heads;
+    size_t stored_bytes;
+} qasr_vloc_geometry;
+/* config.json and every tensor the handle reads, checked on the host alone (no HIP call): what qasr_vloc_create does first.  g may be NULL. */
+int qasr_vloc_check(const char* model_dir, qasr_vloc_geometry* g);
+/* model_dir holds config.json (optional, every key optional: the reference's defaults) and *.safetensors (F32 / F16 / BF16, or MLX 4-bit / 8-bit
+ * triplets weight U32 / scales / biases in groups of 64 for any Linear) with feat_encoder.*, feat_decoder.estimator.*, enc_to_lm_proj.*, lm_to_dit_proj.*, res_to_dit_proj.*.  A missing file or tensor is QASR_ERR_IO;
+ * a wrong shape or dtype, or a configuration value the kernels do not serve, is QASR_ERR_INVALID with the field named:
+ * qasr_vloc_last_error(NULL); all before any HIP call.  max_seqs: patches one device pass holds, 0 = 32, at most 1024. */
+int qasr_vloc_create(int device, const char* model_dir, size_t max_seqs, qasr_engine* order_with, qasr_vloc** out);
+void qasr_vloc_destroy(qasr_vloc* h);
+const char* qasr_vloc_last_error(const qasr_vloc* h);               /* h may be NULL: last create() / check() failure */
+int qasr_vloc_is_loaded(const qasr_vloc* h);
+int qasr_vloc_unload(qasr_vloc* h);                                 /* later device calls return QASR_ERR_NOT_LOADED */
+size_t qasr_vloc_memory_footprint(const qasr_vloc* h);              /* bytes as stored of the tensors read, 0 unloaded */
+int qasr_vloc_patch_size(const qasr_vloc* h);
+int qasr_vloc_feat_dim(const qasr_vloc* h);
+int qasr_vloc_lm_hidden(const qasr_vloc* h);
+int qasr_vloc_mu_dim(const qasr_vloc* h);                           /* mu tokens x the LocDiT's width */
+int qasr_vloc_hidden(const qasr_vloc* h, int which);                /* which: 0 LocEnc, 1 LocDiT */
+int qasr_vloc_depth(const qasr_vloc* h, int which);
+size_t qasr_vloc_max_seqs(const qasr_vloc* h);
+/* Pure CPU.  t[0 .. n_steps]: u + (cos(pi / 2 u) - 1 + u), u = 1 - i / n, in double, rounded to float; n_steps in 1..64. */
+int qasr_vloc_schedule(int n_steps, float* t);
+int qasr_vloc_zero_steps(int n_steps);                              /* max(1, Int((n + 1) 0.04)) leading steps with a zero derivative */
+/* Pure CPU.  The LongRoPE tables of model_dir's config.json for a head of head_dim values, positions 0 .. n_pos - 1: cos, sin
+ * [n_pos][head_dim], formed in double.  The attention scaling reads LMConfig.originalMaxPositionEmbeddings, which has no coding key and
+ * is therefore 32768 whatever rope_scaling says. */
+int qasr_vloc_rope_table(const char* model_dir, int head_dim, int n_pos, float* cos, float* sin);
+/* feats [n][P][feat_dim] -> cls [n][enc hidden] (token 0 after the final norm) and / or embed [n][lm_hidden]; one of them may be NULL.
+ * n over max_seqs runs in passes with identical results. */
+int qasr_vloc_encode(qasr_vloc* h, const float* feats, size_t n, float* cls, float* embed);
+/* B over max_seqs is QASR_ERR_CAPACITY in the four entries below. */
+int qasr_vloc_mu(qasr_vloc* h, const float* lm_hidden /* [B][lm_hidden] */, const float* res_hidden, size_t B, float* mu /* [B][mu_dim] */);
+/* one estimator call, mu as given: x, cond, v [B][P][feat_dim] */
+int qasr_vloc_velocity(qasr_vloc* h, const float* x, const float* mu, const float* cond, size_t B, float t, float* v);
+/* the Euler solve from the caller's noise z [B][P][feat_dim]: x_out the patch, v_out (may be NULL) the last step's guided derivative.
+ * The first solve of a (B, n_steps) runs its launches one by one, the second captures them into one graph, later ones replay it; at most
+ * 16 such graphs are kept, one more pair drops them all. */
+int qasr_vloc_solve(qasr_vloc* h, const float* mu, const float* cond, const float* z, size_t B, int n_steps, float cfg, float* x_out, float* v_out);
+/* qasr_vloc_solve from z[b][i] = temperature x the normal of draw row_index[b] P feat_dim + i of the counter stream `seed`
+ * (csrc/voc_cosyvoice.h: the stream of qasr_flow_generate); row_index NULL: b.  z_out (may be NULL) receives z. */
+int qasr_vloc_sample(qasr_vloc* h, const float* mu, const float* cond, size_t B, int n_steps, float cfg, float temperature, uint64_t seed,
+                     const uint64_t* row_index, float* z_out, float* x_out);
+/* stage entry: the first n_layers layers of a stack on embeddings x [n_seq][S][hidden], S in 1..32, n_seq up to 2 max_seqs; n_layers =
+ * depth adds the final norm */
+int qasr_vloc_stack(qasr_vloc* h, int which, const float* x, size_t n_seq, int S, int n_layers, float* out);
+/* ms[4] of the last encode (summed over passes) | mu | velocity or stack | solve, copies included */
+int qasr_vloc_timing(const qasr_vloc* h, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

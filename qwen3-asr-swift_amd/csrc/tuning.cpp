@@ -23,7 +23,7 @@ const Entry kEntries[] = {
     {"pa_form", &Tuning::pa_form, {1, 2, -1}, false}, {"pa_mt", &Tuning::pa_mt, {1, 2, -1}, false}, {"pa_order", &Tuning::pa_order, {0, 1, -1}, false}, {"pa_vfrag", &Tuning::pa_vfrag, {0, 1, -1}, false},
     {"pp_fuse_qk", &Tuning::pp_fuse_qk, {0, 1, -1}, false}, {"qknr_wide", &Tuning::qknr_wide, {0, 1, -1}, false},
     {"tts_packed_prompt", &Tuning::tts_packed_prompt, {0, 1, -1}, false}, {"codec_tail_rows", &Tuning::codec_tail_rows, {0, 1, -1}, false}, {"cvlm_prompt_chunk", &Tuning::cvlm_prompt_chunk, {1, 64, -1}, false},
-    {"vae_fuse_c", &Tuning::vae_fuse_c, {0, 128, -2}, false},
+    {"vae_fuse_c", &Tuning::vae_fuse_c, {0, 128, -2}, false}, {"vloc_skinny_rows", &Tuning::vloc_skinny_rows, {0, 256, -2}, false},
     {"conv_ktile", &Tuning::conv_ktile, {0, 1, -1}, false}, {"enc_attn", &Tuning::enc_attn, {0, 1, -1}, false}, {"mha_form", &Tuning::mha_form, {0, 1, 2, -1}, false},
     {"gemm_p8", &Tuning::gemm_p8, {0, 1, 2, -1}, false}, {"gemm_nbuf", &Tuning::gemm_nbuf, {0, 1, 2, -1}, false}, {"gemm_tm", &Tuning::gemm_tm, {1, 4, 8, 16, -1}, false},
     {"lmh_q_ring", &Tuning::lmh_q_ring, {0, 1, -1}, false}, {"lmh_grid", &Tuning::lmh_grid, {1, 4096, -2}, false}, {"lmh_order", &Tuning::lmh_order, {0, 1, -1}, false},

@@ -51,6 +51,8 @@ struct Tuning {
     int vae_fuse_c = 64;     // VoxCPM2 AudioVAE residual units (vae_voxcpm.hip): widths up to this value (a multiple of 4, at most 128) run as one launch with the rows and conv2's
                              // weights in LDS | wider ones as a depthwise launch + the shared f32 tile; 0 = never fused.  Measured: fused wins at 32 and 64
                              // channels (2.8 x and 1.2 x per block), loses at 128, where its 160 KB of LDS leave one workgroup per CU; every value passes the same parity tests
+    int vloc_skinny_rows = 256;  // VoxCPM2 local networks (loc_voxcpm.hip): a Linear over up to this many rows (0 .. 256) runs on the skinny kernel in 64-row blocks, a wider one
+                             // on the gemm.h tile behind a bf16 image of its rows; 0 = always the tile.  Measured: the skinny kernel wins up to 256 rows (8.5 against 22 ms a solve at 22 rows), the forms cross between 352 and 704
     int conv_ktile = 1;      // implicit-GEMM convolutions (C >= 64): tap decomposition once per staged K-tile on the scalar unit (AConv3x3s2W) | 0 per chunk
     int enc_attn = 1;        // Qwen3 audio-encoder window attention at head_dim 64: 1 the wav2vec2 path's 32x32x16 kernel | 0 16-row kernel
     int mha_form = 1;        // Omnilingual attention at head_dim 64: 1 | 2 transposed scores on 32x32x16 MFMAs, 128 | 256 queries per workgroup; 0 16x16x32 form

@@ -181,6 +181,11 @@ class QasrDecCase(C.Structure):
                                                                 "clear_words", "n_rope", "half", "n_audio", "r0")]
 
 
+class QasrVlocGeometry(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("patch_size", "feat_dim", "lm_hidden", "enc_hidden", "dit_hidden", "enc_layers", "dit_layers", "mu_dim",
+                                         "kv_heads")] + [("stored_bytes", C.c_size_t)]
+
+
 _P = C.POINTER
 _F = _P(C.c_float)
 _I = _P(C.c_int32)
@@ -552,6 +557,30 @@ SIGNATURES = {
     "qasr_s3tok_profile_batch": (C.c_int, [_E, _P(_F), _P(C.c_size_t), _P(C.c_int), C.c_size_t, _P(_I), _P(C.c_size_t), _P(_F), _P(C.c_size_t),
                                            _P(C.c_size_t), _P(C.c_size_t)]),
     "qasr_s3tok_timing": (C.c_int, [_E, _F]),
+    "qasr_vloc_check": (C.c_int, [C.c_char_p, _P(QasrVlocGeometry)]),
+    "qasr_vloc_create": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t, _E, _P(_E)]),
+    "qasr_vloc_destroy": (None, [_E]),
+    "qasr_vloc_last_error": (C.c_char_p, [_E]),
+    "qasr_vloc_is_loaded": (C.c_int, [_E]),
+    "qasr_vloc_unload": (C.c_int, [_E]),
+    "qasr_vloc_memory_footprint": (C.c_size_t, [_E]),
+    "qasr_vloc_patch_size": (C.c_int, [_E]),
+    "qasr_vloc_feat_dim": (C.c_int, [_E]),
+    "qasr_vloc_lm_hidden": (C.c_int, [_E]),
+    "qasr_vloc_mu_dim": (C.c_int, [_E]),
+    "qasr_vloc_hidden": (C.c_int, [_E, C.c_int]),
+    "qasr_vloc_depth": (C.c_int, [_E, C.c_int]),
+    "qasr_vloc_max_seqs": (C.c_size_t, [_E]),
+    "qasr_vloc_schedule": (C.c_int, [C.c_int, _F]),
+    "qasr_vloc_zero_steps": (C.c_int, [C.c_int]),
+    "qasr_vloc_rope_table": (C.c_int, [C.c_char_p, C.c_int, C.c_int, _F, _F]),
+    "qasr_vloc_encode": (C.c_int, [_E, _F, C.c_size_t, _F, _F]),
+    "qasr_vloc_mu": (C.c_int, [_E, _F, _F, C.c_size_t, _F]),
+    "qasr_vloc_velocity": (C.c_int, [_E, _F, _F, _F, C.c_size_t, C.c_float, _F]),
+    "qasr_vloc_solve": (C.c_int, [_E, _F, _F, _F, C.c_size_t, C.c_int, C.c_float, _F, _F]),
+    "qasr_vloc_sample": (C.c_int, [_E, _F, _F, C.c_size_t, C.c_int, C.c_float, C.c_float, C.c_uint64, _P(C.c_uint64), _F, _F]),
+    "qasr_vloc_stack": (C.c_int, [_E, C.c_int, _F, C.c_size_t, C.c_int, C.c_int, _F]),
+    "qasr_vloc_timing": (C.c_int, [_E, _F]),
 }
 
 _lib = None

@@ -1369,3 +1369,144 @@ def write_voxcpm2_audiovae_safetensors(sd: dict, model_dir: str, geom=None, dtyp
         with open(os.path.join(model_dir, "config.json"), "w") as f:
             json.dump({"architecture": "voxcpm2", "audio_vae_config": cfg}, f)
     return model_dir
+
+
+# ---- VoxCPM2 local networks (qasr_vloc_*) -------------------------------------------------------------------------------------
+# A geometry: {"enc": {hidden_dim, ffn_dim, num_heads, num_layers, kv_channels}, "dit": {...}, "lm": {hidden_size, num_key_value_heads,
+# use_mup, scale_depth, rms_norm_eps, rope_theta, max_position_embeddings, rope_scaling}, "patch_size", "feat_dim", "mu_tokens"}.
+VLOC_REAL = {
+    "enc": {"hidden_dim": 1024, "ffn_dim": 4096, "num_heads": 16, "num_layers": 12, "kv_channels": 128},
+    "dit": {"hidden_dim": 1024, "ffn_dim": 4096, "num_heads": 16, "num_layers": 12, "kv_channels": 128},
+    "lm": {"hidden_size": 2048, "num_key_value_heads": 2, "use_mup": False, "scale_depth": 1.4, "rms_norm_eps": 1e-5, "rope_theta": 10000.0,
+           "max_position_embeddings": 32768},
+    "patch_size": 4, "feat_dim": 64, "mu_tokens": 2,
+}
+
+
+def voxcpm2_local_geometry(depth=None, **over) -> dict:
+    """VLOC_REAL with both stacks at `depth` layers and top-level or "lm." / "enc." / "dit." fields replaced (e.g. lm__use_mup=True)."""
+    import copy
+    g = copy.deepcopy(VLOC_REAL)
+    if depth is not None:
+        g["enc"]["num_layers"] = g["dit"]["num_layers"] = int(depth)
+    for k, v in over.items():
+        if "__" in k:
+            part, field = k.split("__", 1)
+            g[part][field] = v
+        else:
+            g[k] = v
+    return g
+
+
+def voxcpm2_local_tensor_shapes(geom: dict) -> dict:
+    """key -> shape of every tensor qasr_vloc_create reads (VoxCPM2TTS.swift:383-440)."""
+    s = {}
+    F, L = geom["feat_dim"], geom["lm"]["hidden_size"]
+    kv = geom["lm"]["num_key_value_heads"]
+
+    def lin(k, out, inn):
+        s[k + ".weight"], s[k + ".bias"] = (out, inn), (out,)
+
+    def stack(p, g):
+        H, hd = g["hidden_dim"], g["kv_channels"]
+        for l in range(g["num_layers"]):
+            q = f"{p}.layers.{l}"
+            s[q + ".self_attn.q_proj.weight"] = (g["num_heads"] * hd, H)
+            s[q + ".self_attn.k_proj.weight"] = (kv * hd, H)
+            s[q + ".self_attn.v_proj.weight"] = (kv * hd, H)
+            s[q + ".self_attn.o_proj.weight"] = (H, g["num_heads"] * hd)
+            s[q + ".mlp.gate_proj.weight"] = (g["ffn_dim"], H)
+            s[q + ".mlp.up_proj.weight"] = (g["ffn_dim"], H)
+            s[q + ".mlp.down_proj.weight"] = (H, g["ffn_dim"])
+            s[q + ".input_layernorm.weight"] = (H,)
+            s[q + ".post_attention_layernorm.weight"] = (H,)
+        s[p + ".norm.weight"] = (H,)
+
+    He, Hd = geom["enc"]["hidden_dim"], geom["dit"]["hidden_dim"]
+    s["feat_encoder.special_token"] = (1, 1, 1, He)
+    lin("feat_encoder.in_proj", He, F)
+    stack("feat_encoder.encoder", geom["enc"])
+    for k in ("in_proj", "cond_proj"):
+        lin("feat_decoder.estimator." + k, Hd, F)
+    lin("feat_decoder.estimator.out_proj", F, Hd)
+    for m in ("time_mlp", "delta_time_mlp"):
+        for l in ("linear_1", "linear_2"):
+            lin(f"feat_decoder.estimator.{m}.{l}", Hd, Hd)
+    stack("feat_decoder.estimator.decoder", geom["dit"])
+    lin("enc_to_lm_proj", L, He)
+    mu_rows = geom["mu_tokens"] * Hd
+    lin("lm_to_dit_proj", mu_rows - mu_rows // 2, L)
+    lin("res_to_dit_proj", mu_rows // 2, L)
+    return s
+
+
+def bf16_values(a: np.ndarray) -> np.ndarray:
+    """a rounded to the nearest bfloat16 (ties to even), as float32."""
+    u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+    return ((u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000).astype(np.uint32).view(np.float32)
+
+
+def synth_voxcpm2_local_state_dict(geom: dict, seed: int = 0) -> dict:
+    """Seeded weights holding bfloat16 values: matrices N(0, 1 / K) so activations stay O(1), norm weights near 1, biases and the special
+    token O(0.1 .. 1)."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+    for key, shape in voxcpm2_local_tensor_shapes(geom).items():
+        if key.endswith("norm.weight") or key.endswith("layernorm.weight"):
+            v = 1.0 + 0.1 * rng.standard_normal(shape, dtype=np.float32)
+        elif key.endswith(".bias"):
+            v = 0.1 * rng.standard_normal(shape, dtype=np.float32)
+        elif key.endswith("special_token"):
+            v = rng.standard_normal(shape, dtype=np.float32)
+        else:
+            v = rng.standard_normal(shape, dtype=np.float32) * np.float32(1.0 / math.sqrt(shape[-1]))
+        sd[key] = bf16_values(v)
+    return sd
+
+
+def voxcpm2_local_config(geom: dict) -> dict:
+    """The config.json of a geometry."""
+    cfg = {"architecture": "voxcpm2", "lm_config": dict(geom["lm"]), "encoder_config": dict(geom["enc"]), "dit_config": dict(geom["dit"]),
+           "patch_size": geom["patch_size"], "feat_dim": geom["feat_dim"]}
+    return cfg
+
+
+def write_voxcpm2_local_safetensors(sd: dict, model_dir: str, geom=None, dtype: str = "BF16", drop=(), reshape=None, config=None) -> str:
+    """Writes `sd` as model_dir/model.safetensors and, for a geometry (or a whole config dict) given, model_dir/config.json.  `drop` /
+    `reshape`: as write_silero_safetensors.  Returns model_dir."""
+    import json
+    import os
+    _write_safetensors(sd, model_dir, dtype, drop, reshape)
+    if geom is not None or config is not None:
+        with open(os.path.join(model_dir, "config.json"), "w") as f:
+            json.dump(config if config is not None else voxcpm2_local_config(geom), f)
+    return model_dir
+
+
+def quantize_voxcpm2_local_state_dict(sd: dict, bits: int) -> dict:
+    """The MLX 4-bit / 8-bit form of a VoxCPM2 local-network state dict: every Linear weight [out, in] becomes the triplet {weight: packed
+    uint32 words (as int32), scales, biases} of quantize_linear with bfloat16 scales (group 64); vectors, and a Linear whose input width is
+    no multiple of 64, stay float.  torch tensors."""
+    out = {}
+    for k, v in sd.items():
+        a = np.asarray(v)
+        if k.endswith(".weight") and a.ndim == 2 and a.shape[1] % QUANT_GROUP == 0:
+            stem = k[:-len(".weight")]
+            out[k], out[stem + ".scales"], out[stem + ".biases"] = quantize_linear(torch.from_numpy(a).to(torch.bfloat16), bits)
+        else:
+            out[k] = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+    return out
+
+
+def write_voxcpm2_local_quantized_safetensors(qsd: dict, model_dir: str, geom: dict, bits: int, drop=(), reshape=None) -> str:
+    """Writes a quantize_voxcpm2_local_state_dict result as model_dir/model.safetensors (U32 words, BF16 scales / biases, F32 vectors) with
+    the geometry's config.json and its "quantization" entry.  Returns model_dir."""
+    import json
+    import os
+    write_cosyvoice_flow_safetensors(qsd, model_dir, drop=drop, reshape=reshape)
+    os.replace(os.path.join(model_dir, "flow.safetensors"), os.path.join(model_dir, "model.safetensors"))
+    cfg = voxcpm2_local_config(geom)
+    cfg["quantization"] = {"bits": int(bits), "group_size": QUANT_GROUP}
+    with open(os.path.join(model_dir, "config.json"), "w") as f:
+        json.dump(cfg, f)
+    return model_dir
