@@ -296,6 +296,36 @@ int qasr_attn_case_probe(qasr_engine* e, int op, const qasr_attn_case* g, uint16
                          const int32_t* cu, const int32_t* slot_of_clip, const int32_t* pos, const int32_t* slot, const uint16_t* qn_w,
                          const uint16_t* kn_w, uint16_t* kcache, uint16_t* vfrag, const uint16_t* vt, uint16_t* qr, uint16_t* out);
 
+/* Diagnostic: the attention kernels of the speech-synthesis stacks, by themselves, on host data; needs no weights.  Nothing is restated: one
+ * call of the product's launch entry, the one its owning class calls.  The RoPE tables are data: cos / sin f32 [n_table][...].
+ *   QASR_SYN_CVLM  cvlm_rope_append_launch, then cvlm_attention_launch (csrc/llm_cosyvoice.h; head_dim 64).  qkv bf16 [rows][(heads + 2 kv_heads)
+ *                  * 64]; row r sits at (slot[r], pos[r]); tables [n_table][32]; kcache / vcache bf16 [n_slots][kv_heads][max_ctx][64];
+ *                  qr and out bf16 [out_rows][heads * 64].
+ *   QASR_SYN_CP    tts_cp_attn_launch at position `pos` (csrc/tts_talker.h; head_dim 128).  qkv bf16 [rows][(heads + 2 kv_heads) * 128]; qn_w /
+ *                  kn_w bf16 [128]; tables [n_table][64]; kcache / vcache bf16 [n_slots][kv_heads][16][128] (n_slots >= rows cache rows, max_ctx
+ *                  = 16); out bf16 [out_rows][heads * 128].
+ *   QASR_SYN_VL    vl_attention_launch (csrc/loc_voxcpm.h; head_dim 128, f32).  qkv f32 [rows][(heads + 2 kv_heads) * 128], rows = n_seq * S;
+ *                  tables [n_table][128]; out f32 [out_rows][heads * 128].
+ * kcache, vcache, qr and out are uploaded before the launch and downloaded after it, so an untouched byte comes back as it went in; out_rows >=
+ * rows.  qkv_elems, cache_elems, out_elems and table_elems are the element counts of the caller's arrays.  Refused with QASR_ERR_INVALID before
+ * anything is launched: an unknown op, a missing array, heads / kv_heads above 16 (CVLM) or not integral, pos outside 0 .. 15 (CP), S outside
+ * 1 .. 32 or heads x 128 no multiple of 512 (VL), a slot or position outside the cache or the tables, two rows on one cache row, an element
+ * count that contradicts the geometry.  tests/test_gpu_syn_attn_cases.py. */
+enum { QASR_SYN_CVLM = 0, QASR_SYN_CP = 1, QASR_SYN_VL = 2 };
+typedef struct qasr_syn_attn_case {
+    int32_t heads, kv_heads;
+    int32_t rows, out_rows;           /* rows the launch is told about (VL: n_seq * S); rows of qr / out */
+    int32_t n_slots, max_ctx;         /* CVLM: the cache; CP: cache rows (>= rows) and 16 */
+    int32_t pos;                      /* CP */
+    int32_t S, n_seq;                 /* VL */
+    int32_t n_table;                  /* positions of cos / sin */
+    int64_t qkv_elems, cache_elems, out_elems, table_elems;
+    float eps;                        /* CP */
+} qasr_syn_attn_case;
+int qasr_syn_attn_case_probe(qasr_engine* e, int op, const qasr_syn_attn_case* g, const void* qkv, const int32_t* slot, const int32_t* pos,
+                             const uint16_t* qn_w, const uint16_t* kn_w, const float* cos, const float* sin, uint16_t* kcache, uint16_t* vcache,
+                             uint16_t* qr, void* out);
+
 /* Diagnostic: the encoder-side kernels that are not the GEMM, one launch of the product's own entry (csrc/enc_kernels.h, csrc/ctc_kernels.h)
  * on host data; needs no weights.  Nothing is restated.  `in` and `out` hold in_extra / out_extra ROWS beyond what the launch is told about
  * (the caller fills them with NaN patterns / a sentinel); `out` is uploaded before the launch and downloaded after it, so an untouched byte

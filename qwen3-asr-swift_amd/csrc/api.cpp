@@ -119,6 +119,52 @@ static const char* attn_case_refusal(int op, const qasr_attn_case& g, const uint
     return nullptr;
 }
 
+// qasr_syn_attn_case_probe: why the arguments are refused, or null.  Everything a launch would index with is checked here, on the host, and
+// the element counts the caller states for its arrays must be the geometry's.
+static const char* syn_attn_case_refusal(int op, const qasr_syn_attn_case& g, const void* qkv, const int32_t* slot, const int32_t* pos,
+                                         const uint16_t* qn_w, const uint16_t* kn_w, const float* cos, const float* sin, const uint16_t* kcache,
+                                         const uint16_t* vcache, const uint16_t* qr, const void* out) {
+    if (op != QASR_SYN_CVLM && op != QASR_SYN_CP && op != QASR_SYN_VL) return "syn attn case: unknown operation";
+    if (!qkv || !cos || !sin || !out) return "syn attn case: qkv, cos, sin or out is missing";
+    if (g.heads < 1 || g.kv_heads < 1 || g.heads > 64) return "syn attn case: heads in [1, 64], kv_heads positive";
+    if (g.heads % g.kv_heads) return "syn attn case: heads must be a multiple of kv_heads";
+    if (g.rows < 1 || g.out_rows < g.rows || g.out_rows > 65536) return "syn attn case: rows positive, out_rows in [rows, 65536]";
+    if (g.n_table < 1 || g.n_table > 32768) return "syn attn case: n_table in [1, 32768]";
+    const int64_t nh = g.heads + 2 * g.kv_heads;
+    if (op == QASR_SYN_CVLM) {
+        if (g.heads / g.kv_heads > 16) return "syn attn case: the CosyVoice attention serves at most 16 query heads per kv head";
+        if (!slot || !pos || !kcache || !vcache || !qr) return "syn attn case: slot, pos, the caches or qr is missing";
+        if (g.n_slots < 1 || g.max_ctx < 1 || g.rows > 4096 || (double)g.n_slots * g.kv_heads * g.max_ctx * 64 > 64.0 * 1024 * 1024)
+            return "syn attn case: geometry above the probe's limits (4096 rows, 64 Mi cache elements)";
+        for (int r = 0; r < g.rows; ++r) {
+            if (slot[r] < 0 || slot[r] >= g.n_slots) return "syn attn case: a slot is outside the cache";
+            if (pos[r] < 0 || pos[r] >= g.max_ctx || pos[r] >= g.n_table) return "syn attn case: a position is outside the cache or the rope tables";
+            for (int q = 0; q < r; ++q)
+                if (slot[q] == slot[r] && pos[q] == pos[r]) return "syn attn case: two rows share a cache row";
+        }
+        if (g.qkv_elems != g.rows * nh * 64 || g.cache_elems != (int64_t)g.n_slots * g.kv_heads * g.max_ctx * 64 ||
+            g.out_elems != (int64_t)g.out_rows * g.heads * 64 || g.table_elems != (int64_t)g.n_table * 32)
+            return "syn attn case: an array's size contradicts the geometry";
+        return nullptr;
+    }
+    if (op == QASR_SYN_CP) {
+        if (!qn_w || !kn_w || !kcache || !vcache) return "syn attn case: the norm weights or the caches are missing";
+        if (g.pos < 0 || g.pos >= 16 || g.pos >= g.n_table) return "syn attn case: the code predictor's position is outside 0 .. 15 or the rope tables";
+        if (g.max_ctx != 16 || g.n_slots < g.rows || g.n_slots > 65536) return "syn attn case: the code predictor's cache holds 16 entries for each of n_slots >= rows rows";
+        if (!(g.eps > 0.0f) || !(g.eps < 1.0f)) return "syn attn case: eps in (0, 1)";
+        if (g.qkv_elems != g.rows * nh * 128 || g.cache_elems != (int64_t)g.n_slots * g.kv_heads * 16 * 128 ||
+            g.out_elems != (int64_t)g.out_rows * g.heads * 128 || g.table_elems != (int64_t)g.n_table * 64)
+            return "syn attn case: an array's size contradicts the geometry";
+        return nullptr;
+    }
+    if (g.S < 1 || g.S > 32 || g.S > g.n_table) return "syn attn case: S outside 1 .. 32 or the rope tables";
+    if ((g.heads * 128) % 512) return "syn attn case: heads x 128 must be a multiple of 512";
+    if (g.n_seq < 1 || (int64_t)g.n_seq * g.S != g.rows) return "syn attn case: rows must equal n_seq * S";
+    if (g.qkv_elems != g.rows * nh * 128 || g.out_elems != (int64_t)g.out_rows * g.heads * 128 || g.table_elems != (int64_t)g.n_table * 128)
+        return "syn attn case: an array's size contradicts the geometry";
+    return nullptr;
+}
+
 // qasr_enc_case_probe: why the arguments are refused, or null.  Everything a launch would index with is checked here, on the host.
 static const char* enc_case_refusal(int op, const qasr_enc_case& g, const void* in, const int32_t* idx, const int64_t* off, const float* pf,
                                     const uint16_t* pw) {
@@ -449,6 +495,15 @@ int qasr_attn_case_probe(qasr_engine* e, int op, const qasr_attn_case* g, uint16
     if (!e || !g || !qkv || !qn_w || !kn_w || !kcache || !vfrag || !out) return QASR_ERR_INVALID;
     if (const char* why = attn_case_refusal(op, *g, x, W, cu, slot_of_clip, pos, slot, vt, qr)) return fail(e, QASR_ERR_INVALID, why);
     return on_device(e, [&] { e->impl->attn_case_probe(op, *g, qkv, x, W, cu, slot_of_clip, pos, slot, qn_w, kn_w, kcache, vfrag, vt, qr, out); });
+}
+
+int qasr_syn_attn_case_probe(qasr_engine* e, int op, const qasr_syn_attn_case* g, const void* qkv, const int32_t* slot, const int32_t* pos,
+                             const uint16_t* qn_w, const uint16_t* kn_w, const float* cos, const float* sin, uint16_t* kcache, uint16_t* vcache,
+                             uint16_t* qr, void* out) {
+    if (!e || !g) return QASR_ERR_INVALID;
+    if (const char* why = syn_attn_case_refusal(op, *g, qkv, slot, pos, qn_w, kn_w, cos, sin, kcache, vcache, qr, out))
+        return fail(e, QASR_ERR_INVALID, why);
+    return on_device(e, [&] { e->impl->syn_attn_case_probe(op, *g, qkv, slot, pos, qn_w, kn_w, cos, sin, kcache, vcache, qr, out); });
 }
 
 int qasr_enc_case_probe(qasr_engine* e, int op, const qasr_enc_case* g, const void* in, const int32_t* idx, const int64_t* off, const float* pf,

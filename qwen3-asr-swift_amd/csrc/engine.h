@@ -116,6 +116,9 @@ public:
     void attn_case_probe(int op, const qasr_attn_case& g, uint16_t* qkv, const uint16_t* x, const uint16_t* W, const int32_t* cu,
                          const int32_t* slot_of_clip, const int32_t* pos, const int32_t* slot, const uint16_t* qn_w, const uint16_t* kn_w,
                          uint16_t* kcache, uint16_t* vfrag, const uint16_t* vt, uint16_t* qr, uint16_t* out);
+    // qasr_syn_attn_case_probe (csrc/syn_attn_cases.hip): one launch of a synthesis stack's attention entry (CosyVoice LLM, code predictor, VoxCPM2)
+    void syn_attn_case_probe(int op, const qasr_syn_attn_case& g, const void* qkv, const int32_t* slot, const int32_t* pos, const uint16_t* qn_w,
+                             const uint16_t* kn_w, const float* cos, const float* sin, uint16_t* kcache, uint16_t* vcache, uint16_t* qr, void* out);
     // qasr_enc_case_probe (csrc/enc_cases.hip): one launch of an encoder-side kernel that is not the GEMM, on host data
     void enc_case_probe(int op, const qasr_enc_case& g, const void* in, const int32_t* idx, const int64_t* off, const float* pf,
                         const uint16_t* pw, void* out);

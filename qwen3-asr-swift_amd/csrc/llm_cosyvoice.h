@@ -55,6 +55,15 @@ struct CvlmRow {                         // one row of a request, checked by the
     long long index;                     // the caller's row index (random stream)
 };
 
+// The launch entries of the attention path (kernels in llm_cosyvoice.hip; head_dim 64).  Row r sits at (slot[r], pos[r]), device arrays.
+// append: split-half RoPE at pos[r] on the q and k thirds of qkv [rows][(heads + 2 kv_heads) * 64] (cos_t / sin_t [positions][32]),
+// q -> qr [rows][heads * 64], k and v -> row pos[r] of the caches [slots][kv_heads][max_ctx][64].  attention: row r over keys 0 .. pos[r] of
+// its slot -> out [rows][heads * 64]; std::invalid_argument unless heads / kv_heads is integral and at most 16.
+void cvlm_rope_append_launch(const bf16_t* qkv, const int* slot, const int* pos, int rows, int heads, int kv_heads, const float* cos_t,
+                             const float* sin_t, bf16_t* qr, bf16_t* kc, bf16_t* vc, int max_ctx, hipStream_t s);
+void cvlm_attention_launch(const bf16_t* qr, const int* slot, const int* pos, int rows, int heads, int kv_heads, const bf16_t* kc,
+                           const bf16_t* vc, int max_ctx, bf16_t* out, hipStream_t s);
+
 enum CvlmLinear { CVLM_LIN_QKV = 0, CVLM_LIN_O = 1, CVLM_LIN_GATE_UP = 2, CVLM_LIN_DOWN = 3, CVLM_LIN_HEAD = 4 };
 
 class CosyLlm {

@@ -359,6 +359,22 @@ __global__ __launch_bounds__(256) void cvlm_attention_kernel(const bf16_t* __res
     }
 }
 
+// the launch entries of the two kernels above (llm_cosyvoice.h): CosyLlm::layers and qasr_syn_attn_case_probe call these
+void cvlm_rope_append_launch(const bf16_t* qkv, const int* slot, const int* pos, int rows, int heads, int kv_heads, const float* cos_t,
+                             const float* sin_t, bf16_t* qr, bf16_t* kc, bf16_t* vc, int max_ctx, hipStream_t s) {
+    if (rows <= 0) return;
+    hipLaunchKernelGGL(cvlm_rope_append_kernel, dim3(rows), dim3(256), 0, s, qkv, slot, pos, heads, kv_heads, cos_t, sin_t, qr, kc, vc, max_ctx);
+}
+
+void cvlm_attention_launch(const bf16_t* qr, const int* slot, const int* pos, int rows, int heads, int kv_heads, const bf16_t* kc,
+                           const bf16_t* vc, int max_ctx, bf16_t* out, hipStream_t s) {
+    if (heads < 1 || kv_heads < 1 || heads % kv_heads != 0 || heads / kv_heads > 16)    // s_q[16][64]
+        throw std::invalid_argument("cosyvoice llm: the attention kernel serves 1 .. 16 query heads per kv head, heads a multiple of kv_heads");
+    if (rows <= 0) return;
+    hipLaunchKernelGGL(cvlm_attention_kernel, dim3(kv_heads, rows), dim3(256), 0, s, qr, slot, pos, heads, kv_heads, kc, vc, max_ctx, out,
+                       1.0f / sqrtf(64.0f));
+}
+
 // ------------------------------------------------------------------------------------------------
 // The sampler: one workgroup per row, the row's logits and history window in LDS.  Steps as cvlm_sampler.cpp (the host twin) numbers
 // them.  Top-k's threshold, the k-th largest value, is found exactly by bisection over an order-preserving integer key.  Top-p: the
@@ -870,11 +886,9 @@ void CosyLlm::layers(int rows, const int* slot, const int* pos, bool last_kv_onl
         const Layer& L = layers_[l];
         bf16_t *kc = d_k_ + l * per, *vc = d_v_ + l * per;
         gemv(CV_EPI_BF16, L.qkv, d_x_, rows, L.ln1, d_qkv_, nullptr);
-        hipLaunchKernelGGL(cvlm_rope_append_kernel, dim3(rows), dim3(256), 0, stream_, (const bf16_t*)d_qkv_, slot, pos, c.heads, c.kv_heads,
-                           (const float*)d_cos_, (const float*)d_sin_, d_qr_, kc, vc, max_ctx_);
+        cvlm_rope_append_launch(d_qkv_, slot, pos, rows, c.heads, c.kv_heads, d_cos_, d_sin_, d_qr_, kc, vc, max_ctx_, stream_);
         if (last_kv_only && l + 1 == layers_.size()) break;
-        hipLaunchKernelGGL(cvlm_attention_kernel, dim3(c.kv_heads, rows), dim3(256), 0, stream_, (const bf16_t*)d_qr_, slot, pos, c.heads,
-                           c.kv_heads, (const bf16_t*)kc, (const bf16_t*)vc, max_ctx_, d_attn_, 1.0f / sqrtf((float)c.head_dim));
+        cvlm_attention_launch(d_qr_, slot, pos, rows, c.heads, c.kv_heads, kc, vc, max_ctx_, d_attn_, stream_);
         gemv(CV_EPI_RESID, L.o, d_attn_, rows, nullptr, d_x_, nullptr);
         gemv(CV_EPI_SWIGLU, L.gu, d_x_, rows, L.ln2, d_act_, nullptr);
         gemv(CV_EPI_RESID, L.down, d_act_, rows, nullptr, d_x_, nullptr);

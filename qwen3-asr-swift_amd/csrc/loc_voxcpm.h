@@ -64,6 +64,12 @@ int vloc_zero_steps(int n_steps);
 // whose length is neither 0, 1 nor head_dim / 2
 void vloc_rope_table(const VlocConfig& cfg, int head_dim, int n_pos, float* cos, float* sin);
 
+// The launch entry of the stacks' attention (kernel in loc_voxcpm.hip; head_dim 128, f32, no mask): qkv [n_seq * S][(heads + 2 kv_heads) *
+// 128], RoPE from rows 0 .. S - 1 of rcos / rsin [positions][128] -> out [n_seq * S][heads * 128].  Query head h reads K/V head
+// h / (heads / kv_heads).  std::invalid_argument for S outside 1 .. 32 or heads no multiple of kv_heads.
+void vl_attention_launch(const float* qkv, long n_seq, int S, int heads, int kv_heads, const float* rcos, const float* rsin, float* out,
+                         hipStream_t s);
+
 class LocVoxcpm {
   public:
     LocVoxcpm(int device, const VlocConfig& cfg, const VlocWeights& w, long max_seqs, hipStream_t work);

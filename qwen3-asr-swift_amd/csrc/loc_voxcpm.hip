@@ -333,6 +333,16 @@ __global__ __launch_bounds__(256) void vl_attention_kernel(const float* __restri
     }
 }
 
+// the kernel's launch entry (loc_voxcpm.h): LocVoxcpm::run_stack and qasr_syn_attn_case_probe call this
+void vl_attention_launch(const float* qkv, long n_seq, int S, int heads, int kv_heads, const float* rcos, const float* rsin, float* out,
+                         hipStream_t s) {
+    if (S < 1 || S > VL_MAX_S) throw std::invalid_argument("voxcpm2 local networks: attention serves sequences of 1 .. 32 tokens");
+    if (heads < 1 || kv_heads < 1 || heads % kv_heads != 0)
+        throw std::invalid_argument("voxcpm2 local networks: heads must be a multiple of kv_heads");
+    if (n_seq <= 0) return;
+    hipLaunchKernelGGL(vl_attention_kernel, dim3((unsigned)n_seq, (unsigned)heads), dim3(256), 0, s, qkv, S, heads, kv_heads, rcos, rsin, out);
+}
+
 // CFG-zero-star and the Euler line for one patch per workgroup (the order: loc_voxcpm.h).  v [2 B][n]: positive rows, then negative rows.
 __global__ __launch_bounds__(256) void vl_euler_kernel(const float* __restrict__ v, long B, int n, int n2, const float* __restrict__ cfg, float dt,
                                                        float* __restrict__ x, float* __restrict__ d_out) {
@@ -779,8 +789,7 @@ void LocVoxcpm::run_stack(const Net& net, long n_seq, int S, int n_layers) {
     for (int l = 0; l < n_layers; ++l) {
         const Layer& L = net.layers[l];
         gemm(L.qkv, h, H, 1, 1, 0, Wf(L.n1), nullptr, 0, 1.0f, 0, false, qkv, qkvw, rows);
-        hipLaunchKernelGGL(vl_attention_kernel, dim3((unsigned)n_seq, (unsigned)g.heads), dim3(256), 0, work_, qkv, S, g.heads, cfg_.kv_heads,
-                           Wf(rope_cos_), Wf(rope_sin_), attn);
+        vl_attention_launch(qkv, n_seq, S, g.heads, cfg_.kv_heads, Wf(rope_cos_), Wf(rope_sin_), attn, work_);
         QASR_HIP(hipGetLastError());
         gemm(L.o, attn, qd, 1, 1, 0, nullptr, h, H, net.s, 0, false, h, H, rows);
         gemm(L.gu, h, H, 1, 1, 0, Wf(L.n2), nullptr, 0, 1.0f, 0, true, act, g.ffn, rows);

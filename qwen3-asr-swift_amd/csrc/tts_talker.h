@@ -57,6 +57,13 @@ __host__ __device__ inline float tts_uniform(unsigned long long key, int i) {
 // null); returns the token.  Pure host code.
 int tts_sample_host(const float* logits, int V, const TtsSampleParams& p, const unsigned char* seen, long long row, int frame, int group);
 
+// The launch entry of the code predictor's attention (kernel in tts_talker.hip; head_dim 128): position pos (0 .. 15) of the frame for B
+// rows of qkv [B][(heads + 2 kv_heads) * 128].  q/k RMSNorm (qn / kn [128]) + RoPE (row pos of cos_t / sin_t [16][64]); k and v go to entry
+// pos of the caches [B][kv_heads][16][128], the row attends entries 0 .. pos -> out [B][heads * 128].  std::invalid_argument for a pos
+// outside 0 .. 15 or heads no multiple of kv_heads.
+void tts_cp_attn_launch(const bf16_t* qkv, int pos, int B, int heads, int kv_heads, const bf16_t* qn, const bf16_t* kn, float eps,
+                        const float* cos_t, const float* sin_t, bf16_t* kc, bf16_t* vc, bf16_t* out, hipStream_t s);
+
 struct TtsRow {                         // one row of a request, checked by the C ABI
     const int32_t* text; int n_text;
     int language, speaker;              // speaker < 0: none

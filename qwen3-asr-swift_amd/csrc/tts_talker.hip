@@ -151,6 +151,18 @@ __global__ __launch_bounds__(64) void tts_cp_attn_kernel(const bf16_t* __restric
     }
 }
 
+// the kernel's launch entry (tts_talker.h): TtsTalker::layer_steps and qasr_syn_attn_case_probe call this
+void tts_cp_attn_launch(const bf16_t* qkv, int pos, int B, int heads, int kv_heads, const bf16_t* qn, const bf16_t* kn, float eps,
+                        const float* cos_t, const float* sin_t, bf16_t* kc, bf16_t* vc, bf16_t* out, hipStream_t s) {
+    if (pos < 0 || pos >= TTS_GROUPS)                                            // s_k[16][128]
+        throw std::invalid_argument("qwen3-tts code predictor: attention position outside 0 .. 15");
+    if (heads < 1 || kv_heads < 1 || heads % kv_heads != 0)
+        throw std::invalid_argument("qwen3-tts code predictor: heads must be a multiple of kv_heads");
+    if (B <= 0) return;
+    hipLaunchKernelGGL(tts_cp_attn_kernel, dim3(kv_heads, B), dim3(64), 0, s, qkv, pos, heads, kv_heads, qn, kn, eps, cos_t, sin_t, kc, vc, out,
+                       1.0f / sqrtf(128.0f));
+}
+
 // ------------------------------------------------------------------------------------------------
 // The sampler: one workgroup per batch row, the row's logits in LDS.  Steps as tts_sampler.cpp (the host twin) numbers them.  Top-k's
 // threshold, the k-th largest value, is found exactly by bisection over the 32 bits of an order-preserving integer key (count of
@@ -771,9 +783,8 @@ void TtsTalker::layer_steps(const Net& n, bf16_t* x, int B, bool talker, int cp_
                                     d_rope_rows_ + (size_t)(MB + row0) * half, kv, d_attn_, stream_);
         } else {
             const size_t per = (size_t)MB * n.kv * TTS_GROUPS * n.hd;
-            hipLaunchKernelGGL(tts_cp_attn_kernel, dim3(n.kv, B), dim3(64), 0, stream_, (const bf16_t*)d_qkv_, cp_pos, n.heads, n.kv, L.qn, L.kn,
-                               n.eps, (const float*)d_cp_cos_, (const float*)d_cp_sin_, d_cpk_ + l * per, d_cpv_ + l * per, d_attn_,
-                               1.0f / sqrtf((float)n.hd));
+            tts_cp_attn_launch(d_qkv_, cp_pos, B, n.heads, n.kv, L.qn, L.kn, n.eps, d_cp_cos_, d_cp_sin_, d_cpk_ + l * per, d_cpv_ + l * per,
+                               d_attn_, stream_);
         }
         if (kv_only_last && l + 1 == n.layers.size()) break;
         a.X = d_attn_; a.N = n.H; a.K = nq; a.out = x;

@@ -21,8 +21,10 @@ EPS, THETA = 1e-6, 1e6                       # Configuration.swift:11-12
 STOPS = 3                                    # speech_tokens + 0 .. 2 (Configuration.swift:33-35)
 
 
-def layers_forward(x, W, pol):
-    """x [S, H] at positions 0 .. S-1 -> the residual stream after the last layer (CosyVoiceBlock, LLM.swift:238-260)."""
+def layers_forward(x, W, pol, mask_edit=None):
+    """x [S, H] at positions 0 .. S-1 -> the residual stream after the last layer (CosyVoiceBlock, LLM.swift:238-260).  mask_edit: a function
+    of the causal mask [S, S] (True = hidden) that returns the mask to use: tests/test_syn_attn_cases_cpu.py measures with it what a wrong
+    key set does to the network's outputs."""
     g = W.g
     heads, kv, hd = g["heads"], g["kv_heads"], g["head_dim"]
     S = x.shape[0]
@@ -30,6 +32,8 @@ def layers_forward(x, W, pol):
     cos, sin = rope_tables(THETA, half, np.arange(S), pol)
     cos, sin = cos.to(pol["dtype"]), sin.to(pol["dtype"])
     mask = torch.triu(torch.ones(S, S, dtype=torch.bool), diagonal=1)
+    if mask_edit is not None:
+        mask = mask_edit(mask)
     scale = 1.0 / math.sqrt(hd)
 
     def lin(h, key):
@@ -75,14 +79,14 @@ def embed(plan, W, pol):
     return torch.stack([se[i] if kind == "speech" else te[i] for kind, i in plan])
 
 
-def forced_pass(row, tokens, W, pol):
+def forced_pass(row, tokens, W, pol, mask_edit=None):
     """tokens [T] -> dict(logits [T, V], hidden [T, H]): logits[f] at position prefix - 1 + f after feeding tokens 0 .. f - 1."""
     tokens = [int(t) for t in tokens]
     with torch.no_grad():
         plan = prefix_plan(row["text"], row.get("prompt"), W.g["speech_tokens"])
         P = len(plan)
         x = embed(plan + [("speech", t) for t in tokens[:-1]], W, pol)
-        hn = rms(layers_forward(x, W, pol), W.get("norm.weight", pol), EPS, pol)[P - 1:]
+        hn = rms(layers_forward(x, W, pol, mask_edit), W.get("norm.weight", pol), EPS, pol)[P - 1:]
         logits = hn @ W.get("speech_head.weight", pol).T
     return {"logits": logits.numpy(), "hidden": hn.numpy()}
 

@@ -67,13 +67,16 @@ def rope_tables(theta, half, positions, pol):
     return torch.from_numpy(np.cos(ang)), torch.from_numpy(np.sin(ang))
 
 
-def layers_forward(x, W, prefix, n_layers, heads, kv, hd, eps, theta, pol, p_bf16):
-    """x [N, S, H] (N independent causal sequences at positions 0 .. S-1) -> the residual stream after the last layer."""
+def layers_forward(x, W, prefix, n_layers, heads, kv, hd, eps, theta, pol, p_bf16, mask_edit=None):
+    """x [N, S, H] (N independent causal sequences at positions 0 .. S-1) -> the residual stream after the last layer.  mask_edit: a
+    function of the causal mask [S, S] (True = hidden) that returns the mask to use (tests/test_syn_attn_cases_cpu.py)."""
     N, S, H = x.shape
     half = hd // 2
     cos, sin = rope_tables(theta, half, np.arange(S), pol)
     cos, sin = cos.to(pol["dtype"]), sin.to(pol["dtype"])
     mask = torch.triu(torch.ones(S, S, dtype=torch.bool), diagonal=1)
+    if mask_edit is not None:
+        mask = mask_edit(mask)
     scale = 1.0 / math.sqrt(hd)
 
     def lin(h, key):
@@ -174,7 +177,7 @@ def talker_pass(x_seq, W, pol):
     return hn, hn @ W.get(T_ + "codec_head.weight", pol).T
 
 
-def cp_pass(hn, codes, W, pol, n_groups=GROUPS - 1):
+def cp_pass(hn, codes, W, pol, n_groups=GROUPS - 1, mask_edit=None):
     """hn [N, H], codes [N, >= n_groups] (codes 0 .. n_groups-1 are read) -> logits [N, n_groups, cp_vocab]: logits g give code g + 1."""
     g = W.g
     N = hn.shape[0]
@@ -185,7 +188,7 @@ def cp_pass(hn, codes, W, pol, n_groups=GROUPS - 1):
     x = torch.stack(seq, dim=1)                                           # [N, n_groups + 1, E]
     if g["cp_embedding_dim"] != g["cp_hidden"]:
         x = r(x @ W.get(C_ + "small_to_mtp_projection.weight", pol).T + W.get(C_ + "small_to_mtp_projection.bias", pol), pol)
-    x = layers_forward(x, W, C_, g["cp_layers"], g["cp_heads"], g["cp_kv_heads"], g["cp_head_dim"], 1e-6, 1e6, pol, p_bf16=False)
+    x = layers_forward(x, W, C_, g["cp_layers"], g["cp_heads"], g["cp_kv_heads"], g["cp_head_dim"], 1e-6, 1e6, pol, p_bf16=False, mask_edit=mask_edit)
     hn2 = rms(x, W.get(C_ + "model.norm.weight", pol), 1e-6, pol)
     out = [hn2[:, j + 1] @ W.get(C_ + f"lm_head.{j}.weight", pol).T for j in range(n_groups)]
     return torch.stack(out, dim=1)

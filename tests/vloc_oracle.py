@@ -91,6 +91,7 @@ class Model:
 
     def __init__(self, sd, geom, twin=False):
         self.g, self.twin = geom, twin
+        self.kv_edit = None                            # (k, v) [n, S, kv heads, 128] -> what attention reads (tests/test_syn_attn_cases_cpu.py)
         self.dt = np.float32 if twin else np.float64
         self.w = {k: (bf16(v) if twin and np.ndim(v) == 2 else np.asarray(v, dtype=self.dt)) for k, v in sd.items()}
         lm = geom["lm"]
@@ -127,6 +128,8 @@ class Model:
         q = self.rope(self.lin(h, p + ".self_attn.q_proj", False).reshape(n, S, heads, 128))
         k = self.rope(self.lin(h, p + ".self_attn.k_proj", False).reshape(n, S, self.kv, 128))
         v = self.lin(h, p + ".self_attn.v_proj", False).reshape(n, S, self.kv, 128)
+        if self.kv_edit is not None:
+            k, v = self.kv_edit(k, v)
         rep = heads // self.kv
         k, v = np.repeat(k, rep, axis=2), np.repeat(v, rep, axis=2)
         sc = np.einsum("nihd,njhd->nhij", q, k) * self.dt(1.0 / math.sqrt(128.0))
