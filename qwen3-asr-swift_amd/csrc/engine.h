@@ -50,6 +50,49 @@ struct HostBuf {
     template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// The launches `issue` puts on `s`, as an executable graph.  A throwing `issue` ends the capture and is rethrown.
+template <class F>
+hipGraphExec_t capture_graph(hipStream_t s, F&& issue) {
+    hipGraph_t g = nullptr;
+    hipGraphExec_t ge = nullptr;
+    QASR_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    try { issue(); }
+    catch (...) { (void)hipStreamEndCapture(s, &g); if (g) (void)hipGraphDestroy(g); throw; }
+    QASR_HIP(hipStreamEndCapture(s, &g));
+    const hipError_t e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    QASR_HIP(e);
+    return ge;
+}
+
+// One launch sequence per key (a batch size), replayed as a graph.  The first run of a key issues eagerly (kernel attributes are set and
+// code objects load outside a capture), the second captures, every run from the second on launches the graph.  A change of
+// tuning().epoch drops every graph: they hold the old routing.
+class StepGraphs {
+  public:
+    StepGraphs() = default;
+    StepGraphs(const StepGraphs&) = delete;
+    StepGraphs& operator=(const StepGraphs&) = delete;
+    ~StepGraphs() { drop(); }
+    template <class F>
+    void run(int key, hipStream_t s, F&& issue) {
+        if (epoch_ != tuning().epoch) { drop(); epoch_ = tuning().epoch; }
+        if (warmed_.insert(key).second) { issue(); return; }
+        auto it = graphs_.find(key);
+        if (it == graphs_.end()) it = graphs_.emplace(key, capture_graph(s, issue)).first;
+        QASR_HIP(hipGraphLaunch(it->second, s));
+    }
+    void drop() {
+        for (auto& kv : graphs_) (void)hipGraphExecDestroy(kv.second);
+        graphs_.clear();
+    }
+
+  private:
+    std::map<int, hipGraphExec_t> graphs_;
+    std::set<int> warmed_;
+    unsigned epoch_ = 0;
+};
+
 struct Tensor {           // a named parameter resident in HBM
     DevBuf buf;
     std::vector<int64_t> shape;

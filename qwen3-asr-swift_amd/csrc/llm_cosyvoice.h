@@ -5,16 +5,15 @@
 // :387-417, generate :479-560), Configuration.swift:5-41,124-133, WeightLoading.swift:18-110 (keys of llm.safetensors).  A Qwen2.5-0.5B
 // shaped decoder: head_dim 64, no q/k norm, a Linear bias on q, k and v, separate text and speech embeddings, a quantised speech head.
 // MLX affine 4 / 8 bit Linears stay packed (the images of dec_quant.h); bf16 activations between ops, f32 accumulation, f32 norms,
-// softmax and logits.  Every kernel of the step is in llm_cosyvoice.hip; nothing is shared with the Engine or the Talker beyond the
-// image builder (quant_pack_launch), the RoPE tables and the counter random stream of tts_talker.h.  DESIGN.md section 23.
+// softmax and logits.  Every kernel of the step is in llm_cosyvoice.hip.  Shared with the Talker (tts_talker.h): the checked weight
+// loader and its arena (qlm_weights.h, which builds the images with quant_pack_launch), the per-batch-size graph cache (StepGraphs,
+// engine.h), the RoPE tables (rope_tables_host), the counter random stream of tts_talker.h and the samplers' two reduction helpers
+// (sample_dev.h).  DESIGN.md section 23.
 #pragma once
-#include "dec_quant.h"
-#include "safetensors.h"
+#include "qlm_weights.h"
 #include "tts_talker.h"      // tts_stream_key, tts_uniform
 #include "qasr.h"
-#include <map>
 #include <memory>
-#include <set>
 #include <string>
 #include <vector>
 
@@ -73,8 +72,8 @@ class CosyLlm {
     ~CosyLlm();
     const qasr_cvlm_config& config() const { return cfg_; }
     int vocab() const { return cfg_.speech_tokens + cfg_.speech_extra; }
-    size_t footprint() const { return param_bytes_; }
-    size_t device_bytes() const { return device_bytes_; }
+    size_t footprint() const { return wl_ ? wl_->param_bytes() : 0; }      // a host_only object holds nothing
+    size_t device_bytes() const { return wl_ ? wl_->device_bytes() : 0; }
     static void check_geometry(const qasr_cvlm_config& c);      // std::invalid_argument for what the kernels do not serve
     static int context(const qasr_cvlm_config& c);              // positions of a row's cache
     // the prefix of a row as the prompt pass reads it: text ids as they are, speech ids as -1 - id (buildInputSequence)
@@ -92,27 +91,19 @@ class CosyLlm {
     struct State;                        // per-row device state (llm_cosyvoice.hip)
 
   private:
-    struct QLin { QuantImg img; const float* bias = nullptr; int N = 0, K = 0; };
-    struct Layer { QLin qkv, o, gu, down; const bf16_t *ln1 = nullptr, *ln2 = nullptr; };
-    QLin load_qlin(const SafeTensorsDir& st, const std::vector<std::string>& stems, int K, bool bias, int interleave, int pad_to = 0);
-    const bf16_t* load_bf16(const SafeTensorsDir& st, const std::string& key, std::vector<int64_t> shape);
-    void load_all(const SafeTensorsDir& st);
-    void* dev_upload(const void* src, size_t bytes);
+    using Layer = QlmLayer;
+    void load_all(const SafeTensorsDir& st, QlmLoader& wl);
     void gemv(int epi, const QLin& w, const bf16_t* X, int B, const bf16_t* norm_w, bf16_t* out, float* logits);
     void layers(int rows, const int* slot, const int* pos, bool last_kv_only);
     void prefill(const std::vector<CvlmRow>& rows, const qasr_cvlm_sampling* s, int forced_T);
     void issue_step(int B, bool forced_mode);
     void run_step(int B);
     void set_knobs(const qasr_cvlm_sampling& s, unsigned long long seed);
-    void drop_graphs();
     State state() const;
 
     qasr_cvlm_config cfg_;
-    bool dry_ = false;
-    std::set<std::string> seen_keys_;
     hipStream_t stream_ = nullptr;
-    size_t param_bytes_ = 0, device_bytes_ = 0;
-    std::vector<std::unique_ptr<DevBuf>> bufs_;
+    std::unique_ptr<QlmLoader> wl_;      // the weights' and workspaces' arena; null in a host_only object
     std::vector<Layer> layers_;
     QLin head_;
     const bf16_t *text_emb_ = nullptr, *speech_emb_ = nullptr, *norm_ = nullptr;
@@ -129,9 +120,7 @@ class CosyLlm {
     int* d_f_tok_ = nullptr;
     int forced_T_ = 0;
     std::unique_ptr<DevBuf> forced_buf_[3];
-    std::map<int, hipGraphExec_t> graphs_;                      // the step's launch sequence per batch size
-    std::set<int> warmed_;
-    unsigned graph_epoch_ = 0;
+    StepGraphs graphs_;                                         // the step's launch sequence per batch size
 };
 
 }  // namespace qasr

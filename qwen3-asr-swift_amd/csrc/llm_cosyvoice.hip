@@ -6,6 +6,7 @@
 // state.  The prompt pass is the same sequence with rows = packed (slot, position) pairs.  No launch waits on another workgroup.
 #include "llm_cosyvoice.h"
 #include "dec_quant_dev.h"
+#include "sample_dev.h"
 #include "tuning.h"
 #include <algorithm>
 #include <cmath>
@@ -393,30 +394,6 @@ struct CvlmSampleArgs {
     int* out;                            // [B]
 };
 
-__device__ __forceinline__ unsigned cvlm_order_key(float v) {
-    const unsigned u = __float_as_uint(v + 0.0f);                             // -0 -> +0: the host compares values
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// first maximum of the workgroup's (value, index) pairs; every thread passes its own best with the lowest index among equals
-__device__ __forceinline__ int cvlm_block_argmax(float v, int i, float* r_v, int* r_i) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o, 64);
-        const int oi = __shfl_xor(i, o, 64);
-        if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-    }
-    __syncthreads();
-    if ((tid & 63) == 0) { r_v[tid >> 6] = v; r_i[tid >> 6] = i; }
-    __syncthreads();
-    float bv = r_v[0];
-    int bi = r_i[0];
-    for (int w = 1; w < 16; ++w)
-        if (r_v[w] > bv || (r_v[w] == bv && r_i[w] < bi)) { bv = r_v[w]; bi = r_i[w]; }
-    return bi;
-}
-
 __device__ __forceinline__ bool cvlm_is_stop(int i, int st) { return i >= st && i < st + CVLM_STOPS; }
 
 // logit i after steps 1 and 2
@@ -451,7 +428,7 @@ __global__ __launch_bounds__(1024) void cvlm_sample_kernel(CvlmSampleArgs a) {
         for (int bit = 31; bit >= 0; --bit) {
             const unsigned cand = prefix | (1u << bit);
             int c = 0;
-            for (int i = tid; i < V; i += 1024) c += cvlm_order_key(s_v[i]) >= cand ? 1 : 0;
+            for (int i = tid; i < V; i += 1024) c += sample_order_key(s_v[i]) >= cand ? 1 : 0;
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
             if ((tid & 63) == 0) s_cnt[bit & 1][tid >> 6] = c;
@@ -461,7 +438,7 @@ __global__ __launch_bounds__(1024) void cvlm_sample_kernel(CvlmSampleArgs a) {
             if (total >= p.top_k) prefix = cand;
         }
         for (int i = tid; i < V; i += 1024)
-            if (cvlm_order_key(s_v[i]) < prefix) s_v[i] = -1e9f;
+            if (sample_order_key(s_v[i]) < prefix) s_v[i] = -1e9f;
         __syncthreads();
     }
     if (p.top_p < 1.0f) {                                                                                               // 4
@@ -504,7 +481,7 @@ __global__ __launch_bounds__(1024) void cvlm_sample_kernel(CvlmSampleArgs a) {
             const float v = s_v[i] - logf(-logf(tts_uniform(key, i)));
             if (v > bv || bi == 0x7fffffff) { bv = v; bi = i; }
         }
-        tok = cvlm_block_argmax(bv, bi, r_v, r_i);
+        tok = sample_block_argmax(bv, bi, r_v, r_i);
     }
     if (tok < 0 || tok >= V) tok = 0;                                         // all-NaN logits: keep the gather inside its table
     if (p.win_size > 0 && nh > 0) {                                                                                     // 6
@@ -520,7 +497,7 @@ __global__ __launch_bounds__(1024) void cvlm_sample_kernel(CvlmSampleArgs a) {
                 v = v - logf(-logf(tts_uniform(key, i)));
                 if (v > bv || bi == 0x7fffffff) { bv = v; bi = i; }
             }
-            tok = cvlm_block_argmax(bv, bi, r_v, r_i);
+            tok = sample_block_argmax(bv, bi, r_v, r_i);
             if (tok < 0 || tok >= V) tok = 0;
         }
     }
@@ -640,224 +617,87 @@ std::vector<int> CosyLlm::plan_prefix(const qasr_cvlm_config& c, const CvlmRow& 
     return p;
 }
 
-void* CosyLlm::dev_upload(const void* src, size_t bytes) {
-    auto buf = std::make_unique<DevBuf>();
-    buf->alloc(bytes);
-    device_bytes_ += buf->bytes;
-    if (src) QASR_HIP(hipMemcpyAsync(buf->p, src, bytes, hipMemcpyHostToDevice, stream_));
-    void* p = buf->p;
-    bufs_.push_back(std::move(buf));
-    if (src) QASR_HIP(hipStreamSynchronize(stream_));     // src may be a temporary
-    return p;
-}
-
-static std::string shape_str(const std::vector<int64_t>& s) {
-    std::string r = "[";
-    for (size_t i = 0; i < s.size(); ++i) r += (i ? ", " : "") + std::to_string(s[i]);
-    return r + "]";
-}
-static bool is_float(const SafeEntry& e) { return e.dtype == "F32" || e.dtype == "F16" || e.dtype == "BF16"; }
-
-static const SafeEntry& need(const SafeTensorsDir& st, std::set<std::string>& seen, const std::string& key) {
-    auto it = st.entries.find(key);
-    if (it == st.entries.end()) throw WeightLoadError(QASR_ERR_IO, std::string(WHO) + ": missing tensor " + key);
-    seen.insert(key);
-    return it->second;
-}
-
-const bf16_t* CosyLlm::load_bf16(const SafeTensorsDir& st, const std::string& key, std::vector<int64_t> shape) {
-    const SafeEntry& e = need(st, seen_keys_, key);
-    if (e.shape != shape)
-        throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": tensor " + key + " has shape " + shape_str(e.shape) + ", expected " + shape_str(shape));
-    if (!is_float(e)) throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": tensor " + key + " has dtype " + e.dtype + " (F32 / F16 / BF16)");
-    if (dry_) return nullptr;
-    param_bytes_ += e.bytes;
-    if (e.dtype == "BF16") return (const bf16_t*)dev_upload(e.data, e.bytes);
-    std::vector<bf16_t> h(e.numel());
-    for (size_t i = 0; i < h.size(); ++i) h[i] = f32_to_bf16_host(safe_elem_f32(e, i));
-    return (const bf16_t*)dev_upload(h.data(), h.size() * sizeof(bf16_t));
-}
-
-// One quantised Linear, or several fused row-wise: stems concatenated (q | k | v, each with its float bias), or two stems interleaved in
-// blocks of `interleave` rows (gate | up, the layout the SWIGLU epilogue reads).  pad_to: zero rows up to that many (the head).
-CosyLlm::QLin CosyLlm::load_qlin(const SafeTensorsDir& st, const std::vector<std::string>& stems, int K, bool bias, int interleave, int pad_to) {
-    const int bits = cfg_.bits, wrow = K * bits / 32, G = K / 64;
-    struct Part { const SafeEntry *w, *s, *b, *lb; int N; };
-    std::vector<Part> parts;
-    std::string sdtype;
-    for (const auto& stem : stems) {
-        const SafeEntry& w = need(st, seen_keys_, stem + ".weight");
-        if (is_float(w))
-            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": tensor " + stem + ".weight is float (" + w.dtype +
-                                                        "): a float (unquantised) checkpoint is not served, only MLX affine 4 / 8 bit");
-        if (w.dtype != "U32" || w.shape.size() != 2 || w.shape[1] != wrow)
-            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": tensor " + stem + ".weight has dtype " + w.dtype + " shape " +
-                                                        shape_str(w.shape) + ", expected U32 [N, " + std::to_string(wrow) + "] (bits / width mismatch)");
-        const SafeEntry &s = need(st, seen_keys_, stem + ".scales"), &b = need(st, seen_keys_, stem + ".biases");
-        for (const SafeEntry* t : {&s, &b}) {
-            if (t->shape != std::vector<int64_t>{w.shape[0], (int64_t)G})
-                throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": " + stem + " scales / biases have shape " + shape_str(t->shape) +
-                                                            ", expected " + shape_str({w.shape[0], (int64_t)G}));
-            if (!is_float(*t)) throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": " + stem + " scales / biases have dtype " + t->dtype);
-        }
-        if (s.dtype != b.dtype || (!sdtype.empty() && sdtype != s.dtype))
-            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": " + stem + " scales / biases differ in dtype");
-        sdtype = s.dtype;
-        const SafeEntry* lb = nullptr;
-        if (bias) {
-            lb = &need(st, seen_keys_, stem + ".bias");
-            if (lb->shape != std::vector<int64_t>{w.shape[0]} || !is_float(*lb))
-                throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": tensor " + stem + ".bias has shape " + shape_str(lb->shape) +
-                                                            " dtype " + lb->dtype + ", expected float [" + std::to_string(w.shape[0]) + "]");
-        }
-        parts.push_back({&w, &s, &b, lb, (int)w.shape[0]});
-        if (!dry_) param_bytes_ += w.bytes + s.bytes + b.bytes + (lb ? lb->bytes : 0);
-    }
-    std::vector<std::pair<int, int>> order;            // (part, row)
-    if (interleave) {
-        if (parts.size() != 2 || parts[0].N != parts[1].N || parts[0].N % interleave)
-            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": " + stems[0] + ": gate / up row counts do not interleave");
-        for (int blk = 0; blk < parts[0].N / interleave; ++blk)
-            for (int pi = 0; pi < 2; ++pi)
-                for (int r = 0; r < interleave; ++r) order.push_back({pi, blk * interleave + r});
-    } else {
-        for (size_t pi = 0; pi < parts.size(); ++pi)
-            for (int r = 0; r < parts[pi].N; ++r) order.push_back({(int)pi, r});
-    }
-    const int Nsrc = (int)order.size(), N = std::max(Nsrc, pad_to);
-    QLin L;
-    L.N = Nsrc; L.K = K;
-    if (dry_) return L;
-    const bool keep_bf16 = sdtype == "BF16";
-    const size_t sel = keep_bf16 ? 2 : 4;
-    std::vector<uint32_t> hw((size_t)N * wrow, 0u);
-    std::vector<uint8_t> hs((size_t)N * G * sel, 0), hb((size_t)N * G * sel, 0);
-    std::vector<float> hl(bias ? N : 0, 0.0f);
-    for (int n = 0; n < Nsrc; ++n) {
-        const Part& pt = parts[order[n].first];
-        const int r = order[n].second;
-        std::memcpy(&hw[(size_t)n * wrow], pt.w->data + (size_t)r * wrow * 4, (size_t)wrow * 4);
-        if (keep_bf16 || sdtype == "F32") {
-            std::memcpy(&hs[(size_t)n * G * sel], pt.s->data + (size_t)r * G * sel, G * sel);
-            std::memcpy(&hb[(size_t)n * G * sel], pt.b->data + (size_t)r * G * sel, G * sel);
-        } else {
-            for (int g = 0; g < G; ++g) {
-                reinterpret_cast<float*>(hs.data())[(size_t)n * G + g] = safe_elem_f32(*pt.s, (size_t)r * G + g);
-                reinterpret_cast<float*>(hb.data())[(size_t)n * G + g] = safe_elem_f32(*pt.b, (size_t)r * G + g);
-            }
-        }
-        if (bias) hl[n] = bf16_to_f32_host(f32_to_bf16_host(safe_elem_f32(*pt.lb, r)));      // float tensors are kept as bf16
-    }
-    QuantRaw raw;
-    raw.wq = (const uint32_t*)dev_upload(hw.data(), hw.size() * 4);
-    raw.scales = dev_upload(hs.data(), hs.size());
-    raw.biases = dev_upload(hb.data(), hb.size());
-    raw.sb_f32 = keep_bf16 ? 0 : 1; raw.N = N; raw.K = K; raw.bits = bits;
-    L.img.raw = raw; L.img.bits = bits; L.img.sb_f32 = raw.sb_f32;
-    uint32_t* qp = (uint32_t*)dev_upload(nullptr, quant_q_bytes(N, K, bits));
-    void* sb = dev_upload(nullptr, quant_sb_bytes(N, K, raw.sb_f32));
-    quant_pack_launch(raw, qp, sb, stream_);
-    QASR_HIP(hipGetLastError());
-    L.img.qp = qp; L.img.sb = sb;
-    if (bias) L.bias = (const float*)dev_upload(hl.data(), hl.size() * 4);
-    return L;
-}
-
-// every tensor of llm.safetensors; with dry_ set: the host checks alone (presence, shape, dtype of every key, no unexpected key)
-void CosyLlm::load_all(const SafeTensorsDir& st) {
+// every tensor of llm.safetensors; a dry loader: the host checks alone (presence, shape, dtype of every key, no unexpected key)
+void CosyLlm::load_all(const SafeTensorsDir& st, QlmLoader& wl) {
     const auto& c = cfg_;
-    const int H = c.hidden, nq = c.heads * c.head_dim, nkv = c.kv_heads * c.head_dim, V = vocab();
-    seen_keys_.clear();
+    const int H = c.hidden, V = vocab();
+    const QlmLayerGeom g{H, c.heads * c.head_dim, c.kv_heads * c.head_dim, c.inter, c.bits};
     layers_.clear();
-    text_emb_ = load_bf16(st, "text_embedding.weight", {c.text_vocab, H});
-    speech_emb_ = load_bf16(st, "speech_embedding.weight", {V, H});
+    text_emb_ = wl.bf16(st, "text_embedding.weight", {c.text_vocab, H});
+    speech_emb_ = wl.bf16(st, "speech_embedding.weight", {V, H});
     for (int l = 0; l < c.layers; ++l) {
         const std::string p = "layers." + std::to_string(l) + ".";
-        Layer L;
-        L.qkv = load_qlin(st, {p + "self_attn.q_proj", p + "self_attn.k_proj", p + "self_attn.v_proj"}, H, true, 0);
-        if (L.qkv.N != nq + 2 * nkv)
-            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": " + p + "self_attn q/k/v_proj hold " + std::to_string(L.qkv.N) +
-                                                        " rows, expected " + std::to_string(nq + 2 * nkv));
-        L.o = load_qlin(st, {p + "self_attn.o_proj"}, nq, false, 0);
-        L.gu = load_qlin(st, {p + "mlp.gate_proj", p + "mlp.up_proj"}, H, false, 16);
-        L.down = load_qlin(st, {p + "mlp.down_proj"}, c.inter, false, 0);
-        if (L.o.N != H || L.gu.N != 2 * c.inter || L.down.N != H)
-            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": " + p + " o_proj / mlp row counts do not match the geometry");
-        L.ln1 = load_bf16(st, p + "input_layernorm.weight", {H});
-        L.ln2 = load_bf16(st, p + "post_attention_layernorm.weight", {H});
+        Layer L = qlm_load_layer(wl, st, p, g, QlmBias::BF16);               // q, k and v carry a bias; float tensors are kept as bf16
+        for (QLin* q : {&L.qkv, &L.o, &L.gu, &L.down}) wl.pack(*q);
         // named by the reference loader's comment and never loaded (WeightLoading.swift:28-29): present or not, they are not read
-        seen_keys_.insert(p + "self_attn.q_norm.weight");
-        seen_keys_.insert(p + "self_attn.k_norm.weight");
+        wl.mark_seen(p + "self_attn.q_norm.weight");
+        wl.mark_seen(p + "self_attn.k_norm.weight");
         layers_.push_back(L);
     }
-    norm_ = load_bf16(st, "norm.weight", {H});
-    head_ = load_qlin(st, {"speech_head"}, H, false, 0, (V + 15) / 16 * 16);
-    if (head_.N != V)
-        throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": speech_head holds " + std::to_string(head_.N) + " rows, expected " + std::to_string(V));
-    for (const auto& kv : st.entries)
-        if (!seen_keys_.count(kv.first)) throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": unexpected tensor " + kv.first);
+    norm_ = wl.bf16(st, "norm.weight", {H});
+    head_ = wl.qlin(st, {"speech_head"}, H, c.bits, QlmBias::NONE, 0, (V + 15) / 16 * 16);   // zero rows up to the GEMV's 16-row tiles
+    if (head_.N != V) wl.refuse("speech_head holds " + std::to_string(head_.N) + " rows, expected " + std::to_string(V));
+    wl.pack(head_);
+    wl.refuse_unexpected(st);
 }
 
 CosyLlm::CosyLlm(const qasr_cvlm_config& cfg, const SafeTensorsDir& st, bool host_only) : cfg_(cfg) {
     check_geometry(cfg_);
     const auto& c = cfg_;
-    dry_ = true;
-    load_all(st);                                                          // throws before any HIP call
+    {
+        QlmLoader dry(WHO, nullptr, true);
+        load_all(st, dry);                                                 // throws before any HIP call
+    }
     if (host_only) return;
-    dry_ = false;
     QASR_HIP(hipSetDevice(c.device));
     QASR_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     try {
-        load_all(st);
+        wl_ = std::make_unique<QlmLoader>(WHO, stream_, false);
+        load_all(st, *wl_);
         const int MB = c.max_batch, R = CVLM_PASS_ROWS, H = c.hidden, half = c.head_dim / 2, V = vocab();
         const int nq = c.heads * c.head_dim, nkv = c.kv_heads * c.head_dim;
         max_ctx_ = context(c);
         max_prefix_ = 2 + c.max_text + c.max_prompt_tokens;
         std::vector<float> rc, rs;
         rope_tables_host(c.rope_theta, half, max_ctx_, rc, rs);
-        d_cos_ = (float*)dev_upload(rc.data(), rc.size() * 4);
-        d_sin_ = (float*)dev_upload(rs.data(), rs.size() * 4);
+        d_cos_ = (float*)wl_->upload(rc.data(), rc.size() * 4);
+        d_sin_ = (float*)wl_->upload(rs.data(), rs.size() * 4);
         const size_t kv_bytes = (size_t)c.layers * MB * c.kv_heads * max_ctx_ * c.head_dim * 2;
-        d_k_ = (bf16_t*)dev_upload(nullptr, kv_bytes);                      // the sweep reads keys 0 .. pos only: no zero fill
-        d_v_ = (bf16_t*)dev_upload(nullptr, kv_bytes);
-        d_x_ = (bf16_t*)dev_upload(nullptr, (size_t)R * H * 2);
-        d_hn_ = (bf16_t*)dev_upload(nullptr, (size_t)R * H * 2);
-        d_qkv_ = (bf16_t*)dev_upload(nullptr, (size_t)R * (nq + 2 * nkv) * 2);
-        d_qr_ = (bf16_t*)dev_upload(nullptr, (size_t)R * nq * 2);
-        d_attn_ = (bf16_t*)dev_upload(nullptr, (size_t)R * nq * 2);
-        d_act_ = (bf16_t*)dev_upload(nullptr, (size_t)R * c.inter * 2);
-        d_res_ = (bf16_t*)dev_upload(nullptr, (size_t)R * std::max({H, c.inter, nq + 2 * nkv}) * 2);
-        d_logits_ = (float*)dev_upload(nullptr, (size_t)R * V * 4);
-        d_state_ = (int*)dev_upload(nullptr, (size_t)5 * MB * 4);
-        d_tokens_ = (int*)dev_upload(nullptr, (size_t)R * c.max_tokens * 4);
-        d_pick_ = (int*)dev_upload(nullptr, (size_t)R * 4);
-        d_prefix_ = (int*)dev_upload(nullptr, (size_t)MB * max_prefix_ * 4);
-        d_pairs_ = (int*)dev_upload(nullptr, (size_t)2 * MB * max_prefix_ * 4);
-        d_probe_ = (int*)dev_upload(nullptr, (size_t)3 * R * 4);
-        d_row_index_ = (long long*)dev_upload(nullptr, (size_t)R * 8);
-        d_knobs_ = (CvlmSampleParams*)dev_upload(nullptr, sizeof(CvlmSampleParams));
+        d_k_ = (bf16_t*)wl_->upload(nullptr, kv_bytes);                      // the sweep reads keys 0 .. pos only: no zero fill
+        d_v_ = (bf16_t*)wl_->upload(nullptr, kv_bytes);
+        d_x_ = (bf16_t*)wl_->upload(nullptr, (size_t)R * H * 2);
+        d_hn_ = (bf16_t*)wl_->upload(nullptr, (size_t)R * H * 2);
+        d_qkv_ = (bf16_t*)wl_->upload(nullptr, (size_t)R * (nq + 2 * nkv) * 2);
+        d_qr_ = (bf16_t*)wl_->upload(nullptr, (size_t)R * nq * 2);
+        d_attn_ = (bf16_t*)wl_->upload(nullptr, (size_t)R * nq * 2);
+        d_act_ = (bf16_t*)wl_->upload(nullptr, (size_t)R * c.inter * 2);
+        d_res_ = (bf16_t*)wl_->upload(nullptr, (size_t)R * std::max({H, c.inter, nq + 2 * nkv}) * 2);
+        d_logits_ = (float*)wl_->upload(nullptr, (size_t)R * V * 4);
+        d_state_ = (int*)wl_->upload(nullptr, (size_t)5 * MB * 4);
+        d_tokens_ = (int*)wl_->upload(nullptr, (size_t)R * c.max_tokens * 4);
+        d_pick_ = (int*)wl_->upload(nullptr, (size_t)R * 4);
+        d_prefix_ = (int*)wl_->upload(nullptr, (size_t)MB * max_prefix_ * 4);
+        d_pairs_ = (int*)wl_->upload(nullptr, (size_t)2 * MB * max_prefix_ * 4);
+        d_probe_ = (int*)wl_->upload(nullptr, (size_t)3 * R * 4);
+        d_row_index_ = (long long*)wl_->upload(nullptr, (size_t)R * 8);
+        d_knobs_ = (CvlmSampleParams*)wl_->upload(nullptr, sizeof(CvlmSampleParams));
         std::vector<int> iota(R);
         for (int i = 0; i < R; ++i) iota[i] = i;
-        d_iota_ = (int*)dev_upload(iota.data(), iota.size() * 4);
+        d_iota_ = (int*)wl_->upload(iota.data(), iota.size() * 4);
         ensure_dynamic_lds(reinterpret_cast<const void*>(cvlm_sample_kernel), 4 * CVLM_MAX_VOCAB * 4);
         QASR_HIP(hipStreamSynchronize(stream_));
     } catch (...) {
-        bufs_.clear();
+        wl_.reset();
         (void)hipStreamDestroy(stream_);
         stream_ = nullptr;
         throw;
     }
 }
 
-void CosyLlm::drop_graphs() {
-    for (auto& kv : graphs_) (void)hipGraphExecDestroy(kv.second);
-    graphs_.clear();
-}
-
 CosyLlm::~CosyLlm() {
     if (stream_) (void)hipStreamSynchronize(stream_);
-    drop_graphs();
-    bufs_.clear();
+    graphs_.drop();
+    wl_.reset();
     for (auto& f : forced_buf_) f.reset();
     if (stream_) (void)hipStreamDestroy(stream_);
 }
@@ -923,22 +763,7 @@ void CosyLlm::issue_step(int B, bool forced_mode) {
 }
 
 void CosyLlm::run_step(int B) {
-    if (graph_epoch_ != tuning().epoch) { drop_graphs(); graph_epoch_ = tuning().epoch; }
-    if (warmed_.insert(B).second) { issue_step(B, false); return; }        // kernel attributes are set outside a capture
-    auto it = graphs_.find(B);
-    if (it == graphs_.end()) {
-        hipGraph_t g = nullptr;
-        hipGraphExec_t ge = nullptr;
-        QASR_HIP(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
-        try { issue_step(B, false); }
-        catch (...) { (void)hipStreamEndCapture(stream_, &g); if (g) (void)hipGraphDestroy(g); throw; }
-        QASR_HIP(hipStreamEndCapture(stream_, &g));
-        hipError_t e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        QASR_HIP(e);
-        it = graphs_.emplace(B, ge).first;
-    }
-    QASR_HIP(hipGraphLaunch(it->second, stream_));
+    graphs_.run(B, stream_, [&] { issue_step(B, false); });
 }
 
 // buildInputSequence for every row, the rows' state, then every prefix position but a row's last through the layers: packed (slot,

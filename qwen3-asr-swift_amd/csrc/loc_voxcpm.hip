@@ -942,14 +942,7 @@ void LocVoxcpm::solve(const float* mu, const float* cond, const float* z, long B
     if (fresh) {                                       // the first solve of a shape runs eagerly: code objects load outside a capture
         issue_solve(B, n_steps, sv.ttok.as<float>());
     } else if (!sv.exec && vloc_zero_steps(n_steps) < n_steps) {
-        hipGraph_t g = nullptr;
-        QASR_HIP(hipStreamBeginCapture(work_, hipStreamCaptureModeThreadLocal));
-        try { issue_solve(B, n_steps, sv.ttok.as<float>()); }
-        catch (...) { (void)hipStreamEndCapture(work_, &g); if (g) (void)hipGraphDestroy(g); throw; }
-        QASR_HIP(hipStreamEndCapture(work_, &g));
-        const hipError_t e = hipGraphInstantiate(&sv.exec, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        QASR_HIP(e);
+        sv.exec = capture_graph(work_, [&] { issue_solve(B, n_steps, sv.ttok.as<float>()); });
     }
     if (!fresh && sv.exec) QASR_HIP(hipGraphLaunch(sv.exec, work_));
     QASR_HIP(hipMemcpyAsync(x_out, d_x_.p, pb, hipMemcpyDeviceToHost, work_));

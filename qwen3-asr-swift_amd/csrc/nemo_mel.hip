@@ -318,14 +318,7 @@ void NemoMel::extract(int variant, const float* const* pcm, const size_t* n, siz
         const long key[6] = {variant, (long)B, (long)n[0], fit, (long)stride, (long)off};
         if (!graph_ || std::memcmp(key, graph_key_, sizeof(key)) != 0) {
             drop_graph();
-            hipGraph_t g = nullptr;
-            QASR_HIP(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
-            try { issue(variant, (int)B, max_frames, fit, stride, (size_t)off, stream_); }
-            catch (...) { (void)hipStreamEndCapture(stream_, &g); if (g) (void)hipGraphDestroy(g); throw; }
-            QASR_HIP(hipStreamEndCapture(stream_, &g));
-            hipError_t e = hipGraphInstantiate(&graph_, g, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(g);
-            if (e != hipSuccess) { graph_ = nullptr; QASR_HIP(e); }
+            graph_ = capture_graph(stream_, [&] { issue(variant, (int)B, max_frames, fit, stride, (size_t)off, stream_); });
             std::memcpy(graph_key_, key, sizeof(key));
         }
         QASR_HIP(hipGraphLaunch(graph_, stream_));

@@ -6,15 +6,14 @@
 // (dec_quant.h); bf16 activations between layers, f32 accumulation, f32 norms / softmax / logits.  Nothing here is shared with the Engine
 // class: the layer GEMVs and the Talker's attention are the decode step's launch functions (decode_gemv_q_launch,
 // decode_attention_launch), and for ICL prompts the engine's prompt-pass launch functions (quant_dequant_multi_launch, gemm_nt*,
-// qk_norm_rope_launch, prefill_attention_launch); everything else is in tts_talker.hip.  DESIGN.md section 18.
+// qk_norm_rope_launch, prefill_attention_launch).  Shared with the CosyVoice3 LLM (llm_cosyvoice.h): the checked
+// weight loader and its arena (qlm_weights.h), the per-batch-size graph cache (StepGraphs, engine.h), the RoPE tables (rope_tables_host)
+// and the samplers' two reduction helpers (sample_dev.h); every other kernel of the frame is in tts_talker.hip.  DESIGN.md section 18.
 #pragma once
 #include "engine.h"
-#include "dec_quant.h"
-#include "safetensors.h"
+#include "qlm_weights.h"
 #include "qasr.h"
-#include <map>
 #include <memory>
-#include <set>
 #include <string>
 #include <vector>
 
@@ -89,8 +88,8 @@ class TtsTalker {
     TtsTalker(const qasr_tts_config& cfg, const SafeTensorsDir& st, int max_ref_frames = 0, int max_ref_text = 0);
     ~TtsTalker();
     const qasr_tts_config& config() const { return cfg_; }
-    size_t footprint() const { return param_bytes_; }
-    size_t device_bytes() const { return device_bytes_; }
+    size_t footprint() const { return wl_->param_bytes(); }
+    size_t device_bytes() const { return wl_->device_bytes(); }
     // codes [B][16][max_frames] (row stride 16 * max_frames), n_frames [B]
     void generate(const std::vector<TtsRow>& rows, const qasr_tts_sampling& s, unsigned long long seed, int max_frames, int32_t* codes,
                   int32_t* n_frames);
@@ -112,14 +111,10 @@ class TtsTalker {
     struct Knobs;                        // device-side per-call values (tts_talker.hip)
 
   private:
-    struct QLin { QuantImg img; const float* bias = nullptr; int N = 0, K = 0; };
-    struct Layer { QLin qkv, o, gu, down; const bf16_t *ln1, *ln2, *qn, *kn; };
+    struct Layer : QlmLayer { const bf16_t *qn = nullptr, *kn = nullptr; };
     struct Net { std::vector<Layer> layers; const bf16_t* norm = nullptr; int H, heads, kv, hd, I; float eps; };
-    QLin load_qlin(const SafeTensorsDir& st, const std::vector<std::string>& stems, int K, bool bias, int interleave);
-    const bf16_t* load_bf16(const SafeTensorsDir& st, const std::string& key, std::vector<int64_t> shape);
-    void load_net(const SafeTensorsDir& st, const std::string& prefix, Net& n, int layers);
-    void load_all(const SafeTensorsDir& st);
-    void* dev_upload(const void* src, size_t bytes);
+    void load_net(const SafeTensorsDir& st, QlmLoader& wl, const std::string& prefix, Net& n, int layers);
+    void load_all(const SafeTensorsDir& st, QlmLoader& wl);
     void prefill(const std::vector<TtsRow>& rows, bool build_only = false);
     int plan_row(const TtsRow& r, std::vector<int>& tp_ids, int tp_row0, int* pt, int* pc, int* tr, int& nt, float* xv, int* ref) const;
     void packed_prompt(int B, int Pmax);
@@ -127,13 +122,10 @@ class TtsTalker {
     void issue_frame(int B, bool forced_mode);
     void run_frame(int B);
     void set_knobs(const qasr_tts_sampling& s, unsigned long long seed);
-    void drop_graphs();
 
     qasr_tts_config cfg_;
-    bool dry_ = false;                   // load_all checks on the host only
     hipStream_t stream_ = nullptr;
-    size_t param_bytes_ = 0, device_bytes_ = 0;
-    std::vector<std::unique_ptr<DevBuf>> bufs_;
+    std::unique_ptr<QlmLoader> wl_;      // the weights' and workspaces' arena
     Net tk_, cp_;
     QLin head_, fc1_, fc2_, proj_, lm_[TTS_GROUPS - 1];
     const bf16_t *codec_emb_ = nullptr, *text_emb_ = nullptr, *cp_emb_[TTS_GROUPS - 1] = {};
@@ -162,9 +154,7 @@ class TtsTalker {
     int* d_f_codes_ = nullptr;
     int forced_T_host_ = 0;
     std::unique_ptr<DevBuf> forced_buf_[4];
-    std::map<int, hipGraphExec_t> graphs_;                    // the frame's launch sequence per batch size
-    std::set<int> warmed_;                                     // batch sizes whose first frame ran eagerly (kernel attributes are set outside a capture)
-    unsigned graph_epoch_ = 0;
+    StepGraphs graphs_;                                        // the frame's launch sequence per batch size
 };
 
 }  // namespace qasr

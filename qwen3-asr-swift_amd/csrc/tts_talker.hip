@@ -7,6 +7,7 @@
 // the pick), the embedding sum that builds the next Talker input, the prefill embedding builder, and a wave-per-column quantised
 // GEMV with f32 output for the heads and the biased projections.  The layer GEMVs and the Talker's attention are the decode step's.
 #include "tts_talker.h"
+#include "sample_dev.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -183,30 +184,6 @@ struct TtsSampleArgs {
     const bf16_t* hn; bf16_t* hn_out;   // [B][E] or null
 };
 
-__device__ __forceinline__ unsigned tts_order_key(float v) {
-    const unsigned u = __float_as_uint(v + 0.0f);                      // -0 -> +0: the host compares values
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// first maximum of the workgroup's (value, index) pairs; every thread passes its own best with the lowest index among equals
-__device__ __forceinline__ int tts_block_argmax(float v, int i, float* r_v, int* r_i) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o, 64);
-        const int oi = __shfl_xor(i, o, 64);
-        if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-    }
-    __syncthreads();
-    if ((tid & 63) == 0) { r_v[tid >> 6] = v; r_i[tid >> 6] = i; }
-    __syncthreads();
-    float bv = r_v[0];
-    int bi = r_i[0];
-    for (int w = 1; w < 16; ++w)
-        if (r_v[w] > bv || (r_v[w] == bv && r_i[w] < bi)) { bv = r_v[w]; bi = r_i[w]; }
-    return bi;
-}
-
 __global__ __launch_bounds__(1024) void tts_sample_kernel(TtsSampleArgs a) {
     __shared__ float s_v[TTS_MAX_VOCAB];
     __shared__ float r_v[16];
@@ -235,7 +212,7 @@ __global__ __launch_bounds__(1024) void tts_sample_kernel(TtsSampleArgs a) {
         int bi = 0x7fffffff;
         for (int i = tid; i < V; i += 1024)
             if (s_v[i] > bv || bi == 0x7fffffff) { bv = s_v[i]; bi = i; }
-        tok = tts_block_argmax(bv, bi, r_v, r_i);
+        tok = sample_block_argmax(bv, bi, r_v, r_i);
     } else {
         float val[TTS_MAX_VOCAB / 1024];
         unsigned key[TTS_MAX_VOCAB / 1024];
@@ -243,7 +220,7 @@ __global__ __launch_bounds__(1024) void tts_sample_kernel(TtsSampleArgs a) {
         for (int e = 0; e < TTS_MAX_VOCAB / 1024; ++e) {
             const int i = tid + e * 1024;
             val[e] = i < V ? s_v[i] / p.temperature : 0.0f;                                                            // 4
-            key[e] = i < V ? tts_order_key(val[e]) : 0u;                // 0 is below every real key
+            key[e] = i < V ? sample_order_key(val[e]) : 0u;                // 0 is below every real key
         }
         const bool eos_ok = talker && p.eos < V;
         const float eos_saved = eos_ok ? s_v[p.eos] / p.temperature : 0.0f;                                            // 5
@@ -278,7 +255,7 @@ __global__ __launch_bounds__(1024) void tts_sample_kernel(TtsSampleArgs a) {
             v = v - logf(-logf(tts_uniform(skey, i)));                                                                 // 8
             if (v > bv || bi == 0x7fffffff) { bv = v; bi = i; }
         }
-        tok = tts_block_argmax(bv, bi, r_v, r_i);
+        tok = sample_block_argmax(bv, bi, r_v, r_i);
     }
     if (tok < 0 || tok >= V) tok = 0;                                   // all-NaN logits: keep the gather inside its table
     if (tid == 0 && !fin) {
@@ -443,205 +420,51 @@ void TtsTalker::check_geometry(const qasr_tts_config& c) {
     if (c.max_instruct < 0 || c.max_instruct > 8192) bad("max_instruct in 0..8192");
 }
 
-void* TtsTalker::dev_upload(const void* src, size_t bytes) {
-    auto buf = std::make_unique<DevBuf>();
-    buf->alloc(bytes);
-    device_bytes_ += buf->bytes;
-    if (src) QASR_HIP(hipMemcpyAsync(buf->p, src, bytes, hipMemcpyHostToDevice, stream_));
-    void* p = buf->p;
-    bufs_.push_back(std::move(buf));
-    if (src) QASR_HIP(hipStreamSynchronize(stream_));     // src may be a temporary
-    return p;
-}
-
-static const SafeEntry& need(const SafeTensorsDir& st, const std::string& key) {
-    auto it = st.entries.find(key);
-    if (it == st.entries.end()) throw WeightLoadError(QASR_ERR_IO, std::string(WHO) + ": missing tensor " + key);
-    return it->second;
-}
-static std::string shape_str(const std::vector<int64_t>& s) {
-    std::string r = "[";
-    for (size_t i = 0; i < s.size(); ++i) r += (i ? ", " : "") + std::to_string(s[i]);
-    return r + "]";
-}
-static bool is_float(const SafeEntry& e) { return e.dtype == "F32" || e.dtype == "F16" || e.dtype == "BF16"; }
-
-const bf16_t* TtsTalker::load_bf16(const SafeTensorsDir& st, const std::string& key, std::vector<int64_t> shape) {
-    const SafeEntry& e = need(st, key);
-    if (e.shape != shape)
-        throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": tensor " + key + " has shape " + shape_str(e.shape) + ", expected " + shape_str(shape));
-    if (!is_float(e)) throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": tensor " + key + " has dtype " + e.dtype + " (F32 / F16 / BF16)");
-    if (dry_) return nullptr;
-    param_bytes_ += e.bytes;
-    if (e.dtype == "BF16") return (const bf16_t*)dev_upload(e.data, e.bytes);
-    std::vector<bf16_t> h(e.numel());
-    for (size_t i = 0; i < h.size(); ++i) h[i] = f32_to_bf16_host(safe_elem_f32(e, i));
-    return (const bf16_t*)dev_upload(h.data(), h.size() * sizeof(bf16_t));
-}
-
-// One quantised Linear, or several fused row-wise: stems concatenated (q | k | v), or two stems interleaved in blocks of `interleave`
-// rows (gate | up, the layout the SWIGLU epilogue of decode_gemv_q_launch reads).
-TtsTalker::QLin TtsTalker::load_qlin(const SafeTensorsDir& st, const std::vector<std::string>& stems, int K, bool bias, int interleave) {
-    const int bits = cfg_.bits, wrow = K * bits / 32, G = K / 64;
-    struct Part { const SafeEntry *w, *s, *b; int N; };
-    std::vector<Part> parts;
-    std::string sdtype;
-    for (const auto& stem : stems) {
-        const SafeEntry& w = need(st, stem + ".weight");
-        if (is_float(w))
-            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": tensor " + stem + ".weight is float (" + w.dtype +
-                                                        "): a float (unquantised) checkpoint is not served, only MLX affine 4 / 8 bit");
-        if (w.dtype != "U32" || w.shape.size() != 2 || w.shape[1] != wrow)
-            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": tensor " + stem + ".weight has dtype " + w.dtype + " shape " +
-                                                        shape_str(w.shape) + ", expected U32 [N, " + std::to_string(wrow) + "] (bits / width mismatch)");
-        const SafeEntry &s = need(st, stem + ".scales"), &b = need(st, stem + ".biases");
-        for (const SafeEntry* t : {&s, &b}) {
-            if (t->shape != std::vector<int64_t>{w.shape[0], (int64_t)G})
-                throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": " + stem + " scales / biases have shape " + shape_str(t->shape) +
-                                                            ", expected " + shape_str({w.shape[0], (int64_t)G}));
-            if (!is_float(*t)) throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": " + stem + " scales / biases have dtype " + t->dtype);
-        }
-        if (s.dtype != b.dtype || (!sdtype.empty() && sdtype != s.dtype))
-            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": " + stem + " scales / biases differ in dtype");
-        sdtype = s.dtype;
-        parts.push_back({&w, &s, &b, (int)w.shape[0]});
-        if (!dry_) param_bytes_ += w.bytes + s.bytes + b.bytes;
-    }
-    // the order of source rows
-    std::vector<std::pair<int, int>> order;            // (part, row)
-    if (interleave) {
-        if (parts.size() != 2 || parts[0].N != parts[1].N || parts[0].N % interleave)
-            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": " + stems[0] + ": gate / up row counts do not interleave");
-        for (int blk = 0; blk < parts[0].N / interleave; ++blk)
-            for (int pi = 0; pi < 2; ++pi)
-                for (int r = 0; r < interleave; ++r) order.push_back({pi, blk * interleave + r});
-    } else {
-        for (size_t pi = 0; pi < parts.size(); ++pi)
-            for (int r = 0; r < parts[pi].N; ++r) order.push_back({(int)pi, r});
-    }
-    const int N = (int)order.size();
-    if (bias) {
-        const SafeEntry& e = need(st, stems[0] + ".bias");
-        if (e.shape != std::vector<int64_t>{N} || !is_float(e))
-            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": tensor " + stems[0] + ".bias has shape " + shape_str(e.shape) +
-                                                        " dtype " + e.dtype + ", expected float [" + std::to_string(N) + "]");
-    }
-    if (dry_) {
-        QLin D;
-        D.N = N; D.K = K;
-        return D;
-    }
-    const bool keep_bf16 = sdtype == "BF16";
-    const size_t sel = keep_bf16 ? 2 : 4;
-    std::vector<uint32_t> hw((size_t)N * wrow);
-    std::vector<uint8_t> hs((size_t)N * G * sel), hb((size_t)N * G * sel);
-    for (int n = 0; n < N; ++n) {
-        const Part& pt = parts[order[n].first];
-        const int r = order[n].second;
-        std::memcpy(&hw[(size_t)n * wrow], pt.w->data + (size_t)r * wrow * 4, (size_t)wrow * 4);
-        if (keep_bf16 || sdtype == "F32") {
-            std::memcpy(&hs[(size_t)n * G * sel], pt.s->data + (size_t)r * G * sel, G * sel);
-            std::memcpy(&hb[(size_t)n * G * sel], pt.b->data + (size_t)r * G * sel, G * sel);
-        } else {
-            for (int g = 0; g < G; ++g) {
-                reinterpret_cast<float*>(hs.data())[(size_t)n * G + g] = safe_elem_f32(*pt.s, (size_t)r * G + g);
-                reinterpret_cast<float*>(hb.data())[(size_t)n * G + g] = safe_elem_f32(*pt.b, (size_t)r * G + g);
-            }
-        }
-    }
-    QLin L;
-    L.N = N; L.K = K;
-    QuantRaw raw;
-    raw.wq = (const uint32_t*)dev_upload(hw.data(), hw.size() * 4);
-    raw.scales = dev_upload(hs.data(), hs.size());
-    raw.biases = dev_upload(hb.data(), hb.size());
-    raw.sb_f32 = keep_bf16 ? 0 : 1; raw.N = N; raw.K = K; raw.bits = bits;
-    L.img.raw = raw; L.img.bits = bits; L.img.sb_f32 = raw.sb_f32;
-    if (bias) {
-        const SafeEntry& e = need(st, stems[0] + ".bias");
-        std::vector<float> h(N);
-        for (int i = 0; i < N; ++i) h[i] = safe_elem_f32(e, i);
-        L.bias = (const float*)dev_upload(h.data(), h.size() * 4);
-        param_bytes_ += e.bytes;
-    }
-    return L;
-}
-
-void TtsTalker::load_net(const SafeTensorsDir& st, const std::string& prefix, Net& n, int layers) {
-    const int nq = n.heads * n.hd, nkv = n.kv * n.hd;
+void TtsTalker::load_net(const SafeTensorsDir& st, QlmLoader& wl, const std::string& prefix, Net& n, int layers) {
+    const QlmLayerGeom g{n.H, n.heads * n.hd, n.kv * n.hd, n.I, cfg_.bits};
     for (int l = 0; l < layers; ++l) {
         const std::string p = prefix + "model.layers." + std::to_string(l) + ".";
-        Layer L;
-        L.qkv = load_qlin(st, {p + "self_attn.q_proj", p + "self_attn.k_proj", p + "self_attn.v_proj"}, n.H, false, 0);
-        if (L.qkv.N != nq + 2 * nkv)
-            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": " + p + "self_attn q/k/v_proj hold " + std::to_string(L.qkv.N) +
-                                                        " rows, expected " + std::to_string(nq + 2 * nkv));
-        L.o = load_qlin(st, {p + "self_attn.o_proj"}, nq, false, 0);
-        L.gu = load_qlin(st, {p + "mlp.gate_proj", p + "mlp.up_proj"}, n.H, false, 16);
-        L.down = load_qlin(st, {p + "mlp.down_proj"}, n.I, false, 0);
-        if (L.o.N != n.H || L.gu.N != 2 * n.I || L.down.N != n.H)
-            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": " + p + " o_proj / mlp row counts do not match the geometry");
-        L.ln1 = load_bf16(st, p + "input_layernorm.weight", {n.H});
-        L.ln2 = load_bf16(st, p + "post_attention_layernorm.weight", {n.H});
-        L.qn = load_bf16(st, p + "self_attn.q_norm.weight", {n.hd});
-        L.kn = load_bf16(st, p + "self_attn.k_norm.weight", {n.hd});
+        Layer L{qlm_load_layer(wl, st, p, g, QlmBias::NONE)};
+        L.qn = wl.bf16(st, p + "self_attn.q_norm.weight", {n.hd});
+        L.kn = wl.bf16(st, p + "self_attn.k_norm.weight", {n.hd});
         // the packed images of the tuned decode GEMVs (dec_quant.h) next to the triplets the generic kernel reads
-        for (QLin* q : {&L.qkv, &L.o, &L.gu, &L.down}) {
-            const QuantRaw& raw = q->img.raw;
-            if (dry_ || raw.N % 16 != 0 || raw.K % 128 != 0) continue;
-            uint32_t* qp = (uint32_t*)dev_upload(nullptr, quant_q_bytes(raw.N, raw.K, raw.bits));
-            void* sb = dev_upload(nullptr, quant_sb_bytes(raw.N, raw.K, raw.sb_f32));
-            quant_pack_launch(raw, qp, sb, stream_);
-            q->img.qp = qp; q->img.sb = sb;
-        }
+        for (QLin* q : {&L.qkv, &L.o, &L.gu, &L.down})
+            if (q->N % 16 == 0 && q->K % 128 == 0) wl.pack(*q);
         n.layers.push_back(L);
     }
-    n.norm = load_bf16(st, prefix + "model.norm.weight", {n.H});
+    n.norm = wl.bf16(st, prefix + "model.norm.weight", {n.H});
 }
 
-static void rope_tables(float theta, int half, int n_pos, std::vector<float>& c, std::vector<float>& sn) {
-    // theta_i = base^(-i/half), f32 like MLXNN.RoPE(traditional: false): the Engine's tables (decoder.hip)
-    c.resize((size_t)n_pos * half); sn.resize((size_t)n_pos * half);
-    const float k = (float)(-std::log((double)theta) / (double)half);
-    for (int i = 0; i < half; ++i) {
-        const float inv = expf((float)i * k);
-        for (int p = 0; p < n_pos; ++p) {
-            const float ang = (float)p * inv;
-            c[(size_t)p * half + i] = cosf(ang);
-            sn[(size_t)p * half + i] = sinf(ang);
-        }
-    }
-}
-
-// every tensor of both networks; with dry_ set: the host checks alone (presence, shape, dtype of every key), no HIP call
-void TtsTalker::load_all(const SafeTensorsDir& st) {
+// every tensor of both networks; a dry loader: the host checks alone (presence, shape, dtype of every key), no HIP call.  Keys the two
+// networks do not name are not refused: the checkpoint holds other sub-models.
+void TtsTalker::load_all(const SafeTensorsDir& st, QlmLoader& wl) {
     const auto& c = cfg_;
+    const int bits = c.bits;
     tk_ = Net{}; cp_ = Net{};
     tk_.H = c.hidden; tk_.heads = c.heads; tk_.kv = c.kv_heads; tk_.hd = c.head_dim; tk_.I = c.inter; tk_.eps = c.rms_eps;
     cp_.H = c.cp_hidden; cp_.heads = c.cp_heads; cp_.kv = c.cp_kv_heads; cp_.hd = c.cp_head_dim; cp_.I = c.cp_inter; cp_.eps = c.cp_rms_eps;
     const std::string T = "talker.", P = "talker.code_predictor.";
-    codec_emb_ = load_bf16(st, T + "model.codec_embedding.weight", {c.codec_vocab, c.hidden});
-    text_emb_ = load_bf16(st, T + "model.text_embedding.weight", {c.text_vocab, c.text_hidden});
-    fc1_ = load_qlin(st, {T + "text_projection.linear_fc1"}, c.text_hidden, true, 0);
-    fc2_ = load_qlin(st, {T + "text_projection.linear_fc2"}, c.text_hidden, true, 0);
-    head_ = load_qlin(st, {T + "codec_head"}, c.hidden, false, 0);
+    codec_emb_ = wl.bf16(st, T + "model.codec_embedding.weight", {c.codec_vocab, c.hidden});
+    text_emb_ = wl.bf16(st, T + "model.text_embedding.weight", {c.text_vocab, c.text_hidden});
+    // the heads and the biased projections stay raw triplets (tts_gemv_rows_kernel); their bias is read as plain f32
+    fc1_ = wl.qlin(st, {T + "text_projection.linear_fc1"}, c.text_hidden, bits, QlmBias::F32);
+    fc2_ = wl.qlin(st, {T + "text_projection.linear_fc2"}, c.text_hidden, bits, QlmBias::F32);
+    head_ = wl.qlin(st, {T + "codec_head"}, c.hidden, bits);
     if (fc1_.N != c.text_hidden || fc2_.N != c.hidden || head_.N != c.codec_vocab)
-        throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": text_projection / codec_head row counts do not match the geometry");
-    load_net(st, T, tk_, c.layers);
-    load_net(st, P, cp_, c.cp_layers);
+        wl.refuse("text_projection / codec_head row counts do not match the geometry");
+    load_net(st, wl, T, tk_, c.layers);
+    load_net(st, wl, P, cp_, c.cp_layers);
     std::vector<const bf16_t*> tables;
     for (int g = 0; g < TTS_GROUPS - 1; ++g) {
-        cp_emb_[g] = load_bf16(st, P + "model.codec_embedding." + std::to_string(g) + ".weight", {c.cp_vocab, c.cp_embedding_dim});
+        cp_emb_[g] = wl.bf16(st, P + "model.codec_embedding." + std::to_string(g) + ".weight", {c.cp_vocab, c.cp_embedding_dim});
         tables.push_back(cp_emb_[g]);
-        lm_[g] = load_qlin(st, {P + "lm_head." + std::to_string(g)}, c.cp_hidden, false, 0);
-        if (lm_[g].N != c.cp_vocab)
-            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": lm_head." + std::to_string(g) + " does not hold cp_vocab rows");
+        lm_[g] = wl.qlin(st, {P + "lm_head." + std::to_string(g)}, c.cp_hidden, bits);
+        if (lm_[g].N != c.cp_vocab) wl.refuse("lm_head." + std::to_string(g) + " does not hold cp_vocab rows");
     }
-    if (!dry_) d_cp_emb_ = (const bf16_t**)dev_upload(tables.data(), tables.size() * sizeof(void*));
+    if (!wl.dry()) d_cp_emb_ = (const bf16_t**)wl.upload(tables.data(), tables.size() * sizeof(void*));
     if (c.cp_embedding_dim != c.cp_hidden) {
-        proj_ = load_qlin(st, {P + "small_to_mtp_projection"}, c.cp_embedding_dim, true, 0);
-        if (proj_.N != c.cp_hidden)
-            throw WeightLoadError(QASR_ERR_INVALID, std::string(WHO) + ": small_to_mtp_projection does not hold cp_hidden rows");
+        proj_ = wl.qlin(st, {P + "small_to_mtp_projection"}, c.cp_embedding_dim, bits, QlmBias::F32);
+        if (proj_.N != c.cp_hidden) wl.refuse("small_to_mtp_projection does not hold cp_hidden rows");
     }
 }
 
@@ -664,13 +487,15 @@ TtsTalker::TtsTalker(const qasr_tts_config& cfg, const SafeTensorsDir& st, int m
     const auto& c = cfg_;
     const bool icl = max_ref_frames_ > 0;
     const int icl_ctx = icl ? icl_context(c, max_ref_frames_, max_ref_text_) : 0;
-    dry_ = true;
-    load_all(st);                                                          // throws before any HIP call
-    dry_ = false;
+    {
+        QlmLoader dry(WHO, nullptr, true);
+        load_all(st, dry);                                                 // throws before any HIP call
+    }
     QASR_HIP(hipSetDevice(c.device));
     QASR_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     try {
-        load_all(st);
+        wl_ = std::make_unique<QlmLoader>(WHO, stream_, false);
+        load_all(st, *wl_);
         // ---- tables, caches, workspaces -------------------------------------------------------------------------------------
         const int B = c.max_batch, H = c.hidden, half = c.head_dim / 2;
         max_prefill_ = c.max_instruct + 11;                                 // instruct + role 3 + codec prefix (<= 8) - 1 + first text
@@ -678,84 +503,79 @@ TtsTalker::TtsTalker(const qasr_tts_config& cfg, const SafeTensorsDir& st, int m
         max_ctx_ = icl ? icl_ctx : ((max_prefill_ + c.max_frames + 1 + 31) / 32) * 32;
         max_tp_ = 3 + B * (c.max_text + c.max_instruct + max_ref_text_);
         std::vector<float> rc, rs;
-        rope_tables(c.rope_theta, half, max_ctx_, rc, rs);
-        d_rope_cos_ = (float*)dev_upload(rc.data(), rc.size() * 4);
-        d_rope_sin_ = (float*)dev_upload(rs.data(), rs.size() * 4);
-        rope_tables(c.cp_rope_theta, c.cp_head_dim / 2, TTS_GROUPS, rc, rs);
-        d_cp_cos_ = (float*)dev_upload(rc.data(), rc.size() * 4);
-        d_cp_sin_ = (float*)dev_upload(rs.data(), rs.size() * 4);
-        d_rope_rows_ = (float*)dev_upload(nullptr, (size_t)2 * B * half * 4);
+        rope_tables_host(c.rope_theta, half, max_ctx_, rc, rs);
+        d_rope_cos_ = (float*)wl_->upload(rc.data(), rc.size() * 4);
+        d_rope_sin_ = (float*)wl_->upload(rs.data(), rs.size() * 4);
+        rope_tables_host(c.cp_rope_theta, c.cp_head_dim / 2, TTS_GROUPS, rc, rs);
+        d_cp_cos_ = (float*)wl_->upload(rc.data(), rc.size() * 4);
+        d_cp_sin_ = (float*)wl_->upload(rs.data(), rs.size() * 4);
+        d_rope_rows_ = (float*)wl_->upload(nullptr, (size_t)2 * B * half * 4);
         const size_t kv_bytes = (size_t)c.layers * B * c.kv_heads * max_ctx_ * c.head_dim * 2;
-        d_k_ = (bf16_t*)dev_upload(nullptr, kv_bytes);
-        d_vf_ = (bf16_t*)dev_upload(nullptr, kv_bytes);
+        d_k_ = (bf16_t*)wl_->upload(nullptr, kv_bytes);
+        d_vf_ = (bf16_t*)wl_->upload(nullptr, kv_bytes);
         QASR_HIP(hipMemsetAsync(d_k_, 0, kv_bytes, stream_));               // the attention sweep reads whole 32-key chunks and masks: finite values
         QASR_HIP(hipMemsetAsync(d_vf_, 0, kv_bytes, stream_));
         const size_t cpkv = (size_t)c.cp_layers * B * c.cp_kv_heads * TTS_GROUPS * c.cp_head_dim * 2;
-        d_cpk_ = (bf16_t*)dev_upload(nullptr, cpkv);
-        d_cpv_ = (bf16_t*)dev_upload(nullptr, cpkv);
+        d_cpk_ = (bf16_t*)wl_->upload(nullptr, cpkv);
+        d_cpv_ = (bf16_t*)wl_->upload(nullptr, cpkv);
         const int nqkv = std::max((c.heads + 2 * c.kv_heads) * c.head_dim, (c.cp_heads + 2 * c.cp_kv_heads) * c.cp_head_dim);
         const int nattn = std::max(c.heads * c.head_dim, c.cp_heads * c.cp_head_dim);
         const int wmax = std::max({H, c.cp_hidden, c.inter, c.cp_inter, nattn});
-        d_x_ = (bf16_t*)dev_upload(nullptr, (size_t)B * H * 2);
-        d_hn_ = (bf16_t*)dev_upload(nullptr, (size_t)B * H * 2);
-        d_qkv_ = (bf16_t*)dev_upload(nullptr, (size_t)B * nqkv * 2);
-        d_attn_ = (bf16_t*)dev_upload(nullptr, (size_t)B * nattn * 2);
-        d_act_ = (bf16_t*)dev_upload(nullptr, (size_t)B * std::max(c.inter, c.cp_inter) * 2);
-        d_scratch_ = (bf16_t*)dev_upload(nullptr, (size_t)B * wmax * 2);
-        d_cpa_ = (bf16_t*)dev_upload(nullptr, (size_t)B * H * 2);
-        d_cpb_ = (bf16_t*)dev_upload(nullptr, (size_t)B * H * 2);
-        d_cx_ = (bf16_t*)dev_upload(nullptr, (size_t)B * c.cp_hidden * 2);
-        d_chn_ = (bf16_t*)dev_upload(nullptr, (size_t)B * c.cp_hidden * 2);
-        d_tp_in_ = (bf16_t*)dev_upload(nullptr, (size_t)max_tp_ * c.text_hidden * 2);
-        d_tp_mid_ = (bf16_t*)dev_upload(nullptr, (size_t)max_tp_ * c.text_hidden * 2);
-        d_tp_ = (bf16_t*)dev_upload(nullptr, (size_t)max_tp_ * H * 2);
-        d_pf_ = (bf16_t*)dev_upload(nullptr, (size_t)B * max_prefill_ * H * 2);
-        d_logits_ = (float*)dev_upload(nullptr, (size_t)B * c.codec_vocab * 4);
-        d_cp_logits_ = (float*)dev_upload(nullptr, (size_t)B * c.cp_vocab * 4);
-        d_xvec_ = (float*)dev_upload(nullptr, (size_t)B * H * 4);
-        d_state_ = (int*)dev_upload(nullptr, (size_t)6 * B * 4);
-        d_codes_ = (int*)dev_upload(nullptr, (size_t)B * TTS_GROUPS * c.max_frames * 4);
-        d_tp_ids_ = (int*)dev_upload(nullptr, (size_t)max_tp_ * 4);
-        d_pf_text_ = (int*)dev_upload(nullptr, (size_t)B * max_prefill_ * 4);
-        d_pf_codec_ = (int*)dev_upload(nullptr, (size_t)B * max_prefill_ * 4);
-        d_trail_ = (int*)dev_upload(nullptr, (size_t)B * c.max_text * 4);
-        d_row_index_ = (long long*)dev_upload(nullptr, (size_t)B * 8);
-        d_seen_ = (unsigned char*)dev_upload(nullptr, (size_t)B * c.codec_vocab);
-        d_knobs_ = (Knobs*)dev_upload(nullptr, sizeof(Knobs));
+        d_x_ = (bf16_t*)wl_->upload(nullptr, (size_t)B * H * 2);
+        d_hn_ = (bf16_t*)wl_->upload(nullptr, (size_t)B * H * 2);
+        d_qkv_ = (bf16_t*)wl_->upload(nullptr, (size_t)B * nqkv * 2);
+        d_attn_ = (bf16_t*)wl_->upload(nullptr, (size_t)B * nattn * 2);
+        d_act_ = (bf16_t*)wl_->upload(nullptr, (size_t)B * std::max(c.inter, c.cp_inter) * 2);
+        d_scratch_ = (bf16_t*)wl_->upload(nullptr, (size_t)B * wmax * 2);
+        d_cpa_ = (bf16_t*)wl_->upload(nullptr, (size_t)B * H * 2);
+        d_cpb_ = (bf16_t*)wl_->upload(nullptr, (size_t)B * H * 2);
+        d_cx_ = (bf16_t*)wl_->upload(nullptr, (size_t)B * c.cp_hidden * 2);
+        d_chn_ = (bf16_t*)wl_->upload(nullptr, (size_t)B * c.cp_hidden * 2);
+        d_tp_in_ = (bf16_t*)wl_->upload(nullptr, (size_t)max_tp_ * c.text_hidden * 2);
+        d_tp_mid_ = (bf16_t*)wl_->upload(nullptr, (size_t)max_tp_ * c.text_hidden * 2);
+        d_tp_ = (bf16_t*)wl_->upload(nullptr, (size_t)max_tp_ * H * 2);
+        d_pf_ = (bf16_t*)wl_->upload(nullptr, (size_t)B * max_prefill_ * H * 2);
+        d_logits_ = (float*)wl_->upload(nullptr, (size_t)B * c.codec_vocab * 4);
+        d_cp_logits_ = (float*)wl_->upload(nullptr, (size_t)B * c.cp_vocab * 4);
+        d_xvec_ = (float*)wl_->upload(nullptr, (size_t)B * H * 4);
+        d_state_ = (int*)wl_->upload(nullptr, (size_t)6 * B * 4);
+        d_codes_ = (int*)wl_->upload(nullptr, (size_t)B * TTS_GROUPS * c.max_frames * 4);
+        d_tp_ids_ = (int*)wl_->upload(nullptr, (size_t)max_tp_ * 4);
+        d_pf_text_ = (int*)wl_->upload(nullptr, (size_t)B * max_prefill_ * 4);
+        d_pf_codec_ = (int*)wl_->upload(nullptr, (size_t)B * max_prefill_ * 4);
+        d_trail_ = (int*)wl_->upload(nullptr, (size_t)B * c.max_text * 4);
+        d_row_index_ = (long long*)wl_->upload(nullptr, (size_t)B * 8);
+        d_seen_ = (unsigned char*)wl_->upload(nullptr, (size_t)B * c.codec_vocab);
+        d_knobs_ = (Knobs*)wl_->upload(nullptr, sizeof(Knobs));
         if (icl) {
             const int nq = c.heads * c.head_dim, nkv = c.kv_heads * c.head_dim, I = c.inter;
-            d_ref_codes_ = (int*)dev_upload(nullptr, (size_t)B * TTS_GROUPS * max_ref_frames_ * 4);
+            d_ref_codes_ = (int*)wl_->upload(nullptr, (size_t)B * TTS_GROUPS * max_ref_frames_ * 4);
             max_pos_ = B * (max_prefill_ - 1);
             vt_stride_ = (max_prefill_ + 63) / 64 * 64;
-            d_w_ = (bf16_t*)dev_upload(nullptr, ((size_t)(nq + 2 * nkv) * H + (size_t)H * nq + (size_t)2 * I * H + (size_t)H * I) * 2);
+            d_w_ = (bf16_t*)wl_->upload(nullptr, ((size_t)(nq + 2 * nkv) * H + (size_t)H * nq + (size_t)2 * I * H + (size_t)H * I) * 2);
             const size_t vt_bytes = (size_t)B * c.kv_heads * c.head_dim * vt_stride_ * 2;
-            d_vt_ = (bf16_t*)dev_upload(nullptr, vt_bytes);
+            d_vt_ = (bf16_t*)wl_->upload(nullptr, vt_bytes);
             QASR_HIP(hipMemsetAsync(d_vt_, 0, vt_bytes, stream_));          // masked keys multiply stale bytes by P = 0
-            d_px_ = (bf16_t*)dev_upload(nullptr, (size_t)max_pos_ * H * 2);
-            d_ph_ = (bf16_t*)dev_upload(nullptr, (size_t)max_pos_ * H * 2);
-            d_pqkv_ = (bf16_t*)dev_upload(nullptr, (size_t)max_pos_ * (nq + 2 * nkv) * 2);
-            d_pqr_ = (bf16_t*)dev_upload(nullptr, (size_t)max_pos_ * nq * 2);
-            d_pattn_ = (bf16_t*)dev_upload(nullptr, (size_t)max_pos_ * nq * 2);
-            d_pact_ = (bf16_t*)dev_upload(nullptr, (size_t)max_pos_ * I * 2);
-            d_pmeta_ = (int*)dev_upload(nullptr, ((size_t)2 * max_pos_ + 2 * B + 1) * 4);
+            d_px_ = (bf16_t*)wl_->upload(nullptr, (size_t)max_pos_ * H * 2);
+            d_ph_ = (bf16_t*)wl_->upload(nullptr, (size_t)max_pos_ * H * 2);
+            d_pqkv_ = (bf16_t*)wl_->upload(nullptr, (size_t)max_pos_ * (nq + 2 * nkv) * 2);
+            d_pqr_ = (bf16_t*)wl_->upload(nullptr, (size_t)max_pos_ * nq * 2);
+            d_pattn_ = (bf16_t*)wl_->upload(nullptr, (size_t)max_pos_ * nq * 2);
+            d_pact_ = (bf16_t*)wl_->upload(nullptr, (size_t)max_pos_ * I * 2);
+            d_pmeta_ = (int*)wl_->upload(nullptr, ((size_t)2 * max_pos_ + 2 * B + 1) * 4);
         }
         QASR_HIP(hipStreamSynchronize(stream_));
     } catch (...) {
-        bufs_.clear();
+        wl_.reset();
         (void)hipStreamDestroy(stream_);
         throw;
     }
 }
 
-void TtsTalker::drop_graphs() {
-    for (auto& kv : graphs_) (void)hipGraphExecDestroy(kv.second);
-    graphs_.clear();
-}
-
 TtsTalker::~TtsTalker() {
     if (stream_) (void)hipStreamSynchronize(stream_);
-    drop_graphs();
-    bufs_.clear();
+    graphs_.drop();
+    wl_.reset();
     for (auto& f : forced_buf_) f.reset();
     if (stream_) (void)hipStreamDestroy(stream_);
 }
@@ -846,22 +666,7 @@ void TtsTalker::issue_frame(int B, bool forced_mode) {
 }
 
 void TtsTalker::run_frame(int B) {
-    if (graph_epoch_ != tuning().epoch) { drop_graphs(); graph_epoch_ = tuning().epoch; }
-    if (warmed_.insert(B).second) { issue_frame(B, false); return; }
-    auto it = graphs_.find(B);
-    if (it == graphs_.end()) {
-        hipGraph_t g = nullptr;
-        hipGraphExec_t ge = nullptr;
-        QASR_HIP(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
-        try { issue_frame(B, false); }
-        catch (...) { (void)hipStreamEndCapture(stream_, &g); if (g) (void)hipGraphDestroy(g); throw; }
-        QASR_HIP(hipStreamEndCapture(stream_, &g));
-        hipError_t e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        QASR_HIP(e);
-        it = graphs_.emplace(B, ge).first;
-    }
-    QASR_HIP(hipGraphLaunch(it->second, stream_));
+    graphs_.run(B, stream_, [&] { issue_frame(B, false); });
 }
 
 // The prompt plan of one row: buildPrefillEmbeddings (Qwen3TTS.swift:1313-1390), for an ICL row buildICLPrefillEmbeddings.  pt / pc

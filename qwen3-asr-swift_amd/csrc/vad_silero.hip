@@ -514,18 +514,7 @@ void SileroVad::run(int B, int total_chunks, size_t samples, bool tick) {
     if (tick) {
         // a tick of B streams: same addresses, sizes and launches every time, only the staged samples / stream ids differ -> one graph per B
         auto it = graphs_.find(B);
-        if (it == graphs_.end()) {
-            hipGraph_t g = nullptr;
-            hipGraphExec_t ge = nullptr;
-            QASR_HIP(hipStreamBeginCapture(own_, hipStreamCaptureModeThreadLocal));
-            try { issue(B, total_chunks, samples, own_); }
-            catch (...) { (void)hipStreamEndCapture(own_, &g); if (g) (void)hipGraphDestroy(g); throw; }
-            QASR_HIP(hipStreamEndCapture(own_, &g));
-            hipError_t e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(g);
-            QASR_HIP(e);
-            it = graphs_.emplace(B, ge).first;
-        }
+        if (it == graphs_.end()) it = graphs_.emplace(B, capture_graph(own_, [&] { issue(B, total_chunks, samples, own_); })).first;
         QASR_HIP(hipGraphLaunch(it->second, work_));
         last_graph_ = true;
     } else {
