@@ -326,6 +326,71 @@ int qasr_syn_attn_case_probe(qasr_engine* e, int op, const qasr_syn_attn_case* g
                              const uint16_t* qn_w, const uint16_t* kn_w, const float* cos, const float* sin, uint16_t* kcache, uint16_t* vcache,
                              uint16_t* qr, void* out);
 
+/* Diagnostic: the f32 kernels the waveform codecs share or keep outside their GEMM, by themselves, on host data; needs no weights.  Nothing
+ * is restated: one call of the launch entry the three codec classes call (csrc/codec_launch.h).  All arrays are f32 but loc_a / loc_b.
+ * `A` holds a_rows rows, which is everything a locator may reach; `out` (and R) hold M + out_extra rows, of which the launch is told
+ * about M; the caller fills what lies beyond with NaN patterns / a sentinel.  `out` is uploaded before the launch and downloaded after
+ * it, so an untouched byte comes back as it went in.
+ *   TILE     codec_tile_launch(rows, snake, epi).  A [a_rows][Cin]; Wt [K][N], K = taps * Cin; bias [bmod] under WINDOW / TAIL
+ *            (bias[n % bmod]), [N] under CLIP / VAE_STRIDE, or null; sa / sb [Cin] under snake, [N] under E_RESMAP; ls [N] under E_LSRES,
+ *            [2 N] or null under E_RESMAP; R and out [M + out_extra][ldc] (R: E_RES, E_LSRES; optional under E_RESMAP), or in_place = 1:
+ *            R is out itself, as the product runs E_RES / E_LSRES.  E_SWIGLU writes N / 2 columns.  Locators (csrc/codec_shared.h):
+ *              WINDOW      loc_a = fstart [ceil(M / rate)]: fstart[f] is f or fstart[f - 1]; input row = output row
+ *              TAIL        WINDOW, and loc_b = kept [as fstart]: a frame row of its own window, one value per window; lead >= 0
+ *              CLIP        loc_a = ostart, loc_b = istart [n_clips + 1]: ostart from 0 to M, strictly increasing; istart not decreasing;
+ *                          output row t of a clip reads input row istart + t * stride.  Both null (taps 1): row m reads row m
+ *              VAE_STRIDE  loc_a = fstart [ceil(M / rate)] as WINDOW; output row m reads input rows up to (m + 1) * stride - 1
+ *   RMS      codec_rms_launch.  A = x [a_rows >= M][C], Wt = w [C], eps; out [M + out_extra][C].
+ *   DWLN     codec_dwln_launch under WINDOW or CLIP (loc_b = loc_a, stride 1).  A = x [a_rows >= M][C], Wt = w [7][C], bias = b [C], sa / sb
+ *            = the LayerNorm's weight / bias [C]; out [M + out_extra][C].
+ *   GATHER   codec_gather_launch.  loc_a = codes [M][Q] (n_loc = M Q), Wt = codebook 0 [S0][C], then Q - 1 codebooks [S1][C]; out
+ *            [M + out_extra][2 C].  A is not used.
+ *   OUT      codec_out_launch, TAIL under rows_kind TAIL (loc_b = kept), else WINDOW.  A = x [a_rows >= M][C], sa / sb [C], Wt = w [7][C],
+ *            bias = b [1], clip 0 / 1; out [M + out_extra].
+ *   CENC_IN  cenc_in_launch.  A = pcm [a_rows >= M], loc_a = clip starts [n_clips + 1] from 0 to M, Wt = w [7][C], bias = b [C]; out
+ *            [M + out_extra][C].
+ *   VQ       cenc_vq_launch.  out = r [M + out_extra][2 C] (read and written), loc_b = codes [M + out_extra][Q] (written; uploaded first, so
+ *            rows past M come back as they went in), Wt / bias / sa = cb0 [S0][C], its transpose [C][S0] and |c|^2 [S0]; sb / ls / R = cb1
+ *            [Q - 1][S1][C], the transposes [Q - 1][C][S1] and |c|^2 [Q - 1][S1] (null for Q = 1).  A is not used.
+ *   ATTN_DEC codec_attn_launch.  A = qkv [a_rows >= M][3 heads 64], loc_a = n_clips windows (frames, first row) back to back from row 0 to M
+ *            (n_loc = 2 n_clips), Wt = rope [n_table][32] pairs (cos, sin); out [M + out_extra][heads 64].
+ *   ATTN_ENC cenc_attn_launch.  As ATTN_DEC with loc_a = n_clips tiles (the clip's first row, its frames, the tile's first query, 0): one per
+ *            32 queries of each clip, clips back to back (n_loc = 4 n_clips).
+ *   VAE_DW   vae_dw_launch under WINDOW (loc_a = fstart), both snakes (snake = 1: sa / sb = a1, 1 / a1, ls / R = a2, 1 / a2, each [C]) or
+ *            neither.  A = x [a_rows >= M][C], Wt = w [7][C], bias = b [C], dil; out [M + out_extra][C].
+ *   VAE_UNIT vae_unit_launch under WINDOW (loc_a = fstart), RPT by the product's rule.  A = x [a_rows >= M][C]; Wt = the unit's parameters packed
+ *            as w1 [7][C] | b1 | a1 | 1 / a1 | a2 | 1 / a2 [C each] | conv2's Wt [C][C] | b2 [C]; sa / sb = the reader's map a, 1 / a [C] (both
+ *            null: none), ls = its affine [2 C] or null; out [M + out_extra][C].  bias and R are not used.
+ * Refused with QASR_ERR_INVALID before anything is launched: an unknown op; a missing array; a (rows, snake, epi) outside
+ * CODEC_TILE_COMBOS (csrc/codec_launch.h); another locator than WINDOW / CLIP for DWLN, than WINDOW / TAIL for OUT; M outside 1 .. 2^20,
+ * a_rows or out_extra above 2^20, Cin, N, C outside 1 .. 65536 (RMS too: codec_rms_kernel holds no row in LDS; DWLN, GATHER, VQ: C above
+ * 4096; VAE_UNIT: C above AV_FUSE_MAX = 128 or no multiple of 4, dil above 9, a map with one array, an affine without the map), taps outside 1 .. 64, dil, rate, stride
+ * outside 1 .. 64, Q outside 1 .. 64, S0 / S1 outside 1 .. 65536; K != taps * Cin; an odd N under E_SWIGLU; ldc below the columns written;
+ * bmod outside 1 .. N; n_loc that is not the count stated above; an fstart, kept, ostart, istart or clip start that is not monotone as
+ * stated above or points outside; a code outside its codebook (GATHER); any output row whose `last` input row is not inside
+ * 0 .. a_rows - 1 or whose `first` is negative; a_rows below M where input and output rows are the same; in_place without a residual
+ * epilogue, or with R; a residual epilogue without either; hd other than 64, heads outside 1 .. 64, a window above CODEC_MAX_T frames or
+ * the rope table, windows, clips or tiles that do not lie back to back from row 0 to M (attention); dil above 27 or another locator than
+ * WINDOW (VAE_DW).  tests/test_gpu_codec_cases.py. */
+enum { QASR_CODEC_TILE = 0, QASR_CODEC_RMS = 1, QASR_CODEC_DWLN = 2, QASR_CODEC_GATHER = 3, QASR_CODEC_OUT = 4, QASR_CODEC_CENC_IN = 5,
+       QASR_CODEC_VQ = 6, QASR_CODEC_ATTN_DEC = 7, QASR_CODEC_ATTN_ENC = 8, QASR_CODEC_VAE_DW = 9,
+       QASR_CODEC_VAE_UNIT = 10 };
+enum { QASR_CODEC_ROWS_WINDOW = 0, QASR_CODEC_ROWS_TAIL = 1, QASR_CODEC_ROWS_CLIP = 2, QASR_CODEC_ROWS_VAE_STRIDE = 3 };
+typedef struct qasr_codec_case {
+    int32_t rows_kind, snake, epi;    /* TILE: QASR_CODEC_ROWS_*, 0 / 1, 0 .. 5 = E_LIN, E_GELU, E_RES, E_LSRES, E_SWIGLU, E_RESMAP */
+    int32_t M, a_rows, out_extra;
+    int32_t Cin, taps, dil, K, N, bmod, ldc;
+    int32_t rate, stride, lead, n_clips, n_loc;
+    int32_t in_place;
+    int32_t C;                        /* RMS, DWLN, GATHER (D), OUT, CENC_IN */
+    int32_t Q, S0, S1;                /* GATHER, VQ */
+    int32_t clip;                     /* OUT */
+    int32_t heads, hd, n_table;       /* ATTN_DEC, ATTN_ENC: hd must be 64; rope positions */
+    float eps;                        /* RMS */
+} qasr_codec_case;
+int qasr_codec_case_probe(qasr_engine* e, int op, const qasr_codec_case* g, const float* A, const float* Wt, const float* bias, const float* sa,
+                          const float* sb, const float* ls, const float* R, const int32_t* loc_a, int32_t* loc_b, float* out);
+
 /* Diagnostic: the encoder-side kernels that are not the GEMM, one launch of the product's own entry (csrc/enc_kernels.h, csrc/ctc_kernels.h)
  * on host data; needs no weights.  Nothing is restated.  `in` and `out` hold in_extra / out_extra ROWS beyond what the launch is told about
  * (the caller fills them with NaN patterns / a sentinel); `out` is uploaded before the launch and downloaded after it, so an untouched byte

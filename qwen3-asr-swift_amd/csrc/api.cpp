@@ -3,6 +3,8 @@
 #include "engine.h"
 #include "ctc_engine.h"
 #include "tuning.h"
+#include "codec_launch.h"
+#include "codec_qwen3tts.h"
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -162,6 +164,173 @@ static const char* syn_attn_case_refusal(int op, const qasr_syn_attn_case& g, co
     if (g.n_seq < 1 || (int64_t)g.n_seq * g.S != g.rows) return "syn attn case: rows must equal n_seq * S";
     if (g.qkv_elems != g.rows * nh * 128 || g.out_elems != (int64_t)g.out_rows * g.heads * 128 || g.table_elems != (int64_t)g.n_table * 128)
         return "syn attn case: an array's size contradicts the geometry";
+    return nullptr;
+}
+
+// qasr_codec_case_probe: why the arguments are refused, or null.  The locator arrays are held to their contracts (codec_shared.h), then every
+// output row's span is formed as the locator forms it and must lie inside A.
+static const char* codec_case_refusal(int op, const qasr_codec_case& g, const float* A, const float* Wt, const float* bias, const float* sa,
+                                      const float* sb, const float* ls, const float* R, const int32_t* la, const int32_t* lb, const float* out) {
+    if (op < QASR_CODEC_TILE || op > QASR_CODEC_VAE_UNIT) return "codec case: unknown operation";
+    if ((!A && op != QASR_CODEC_GATHER && op != QASR_CODEC_VQ) || !Wt || !out) return "codec case: A, Wt or out is missing";
+    const int lim = 1 << 20;
+    if (g.M < 1 || g.M > lim || g.a_rows < 1 || g.a_rows > lim || g.out_extra < 0 || g.out_extra > lim)
+        return "codec case: M, a_rows in [1, 2^20], out_extra in [0, 2^20]";
+    const int kind = g.rows_kind;
+    if (op == QASR_CODEC_RMS) {
+        if (g.C < 1 || g.C > 65536 || g.a_rows < g.M) return "codec case: rms needs C in [1, 65536] and a_rows >= M";
+        if (!(g.eps > 0.0f) || !(g.eps < 1.0f)) return "codec case: eps in (0, 1)";
+        return nullptr;
+    }
+    if (op == QASR_CODEC_GATHER) {
+        if (g.Q < 1 || g.Q > 64 || g.C < 1 || g.C > 4096 || g.S0 < 1 || g.S0 > 65536 || g.S1 < 1 || g.S1 > 65536)
+            return "codec case: gather needs Q in [1, 64], C in [1, 4096], S0 and S1 in [1, 65536]";
+        if (!la || (long)g.n_loc != (long)g.M * g.Q) return "codec case: gather needs codes [M][Q]";
+        for (long m = 0; m < g.M; ++m)
+            for (int q = 0; q < g.Q; ++q) {
+                const int code = la[m * g.Q + q];
+                if (code < 0 || code >= (q == 0 ? g.S0 : g.S1)) return "codec case: a code is outside its codebook";
+            }
+        return nullptr;
+    }
+    if (op == QASR_CODEC_ATTN_DEC || op == QASR_CODEC_ATTN_ENC) {
+        if (g.hd != 64) return "codec case: the codec attention kernels serve head_dim 64";
+        if (g.heads < 1 || g.heads > 64 || g.n_table < 1 || g.n_table > 65536 || g.a_rows < g.M) return "codec case: heads in [1, 64], n_table in [1, 65536], a_rows >= M";
+        const int per = op == QASR_CODEC_ATTN_DEC ? 2 : 4;
+        if (!la || g.n_clips < 1 || g.n_clips > g.M || g.n_loc != per * g.n_clips) return "codec case: attention needs its windows / tiles";
+        long row = 0;                                  // windows / clips lie back to back from row 0 to M
+        if (op == QASR_CODEC_ATTN_DEC) {
+            for (int w = 0; w < g.n_clips; ++w) {
+                const int T = la[2 * w], off = la[2 * w + 1];
+                if (T < 1 || T > qasr::CODEC_MAX_T || T > g.n_table) return "codec case: a window holds 1 .. CODEC_MAX_T frames inside the rope table";
+                if (off != row) return "codec case: windows must lie back to back from row 0";
+                row += T;
+            }
+        } else {
+            int w = 0;
+            while (w < g.n_clips) {                    // a clip's tiles: first query 0, 32, .. below its frames
+                const int row0 = la[4 * w], F = la[4 * w + 1];
+                if (row0 != row || F < 1 || F > g.n_table || row + F > g.M) return "codec case: clips must lie back to back from row 0, inside M and the rope table";
+                for (int q0 = 0; q0 < F; q0 += 32, ++w)
+                    if (w >= g.n_clips || la[4 * w] != row0 || la[4 * w + 1] != F || la[4 * w + 2] != q0)
+                        return "codec case: a clip needs one tile per 32 queries, in order";
+                row += F;
+            }
+        }
+        if (row != g.M) return "codec case: the windows / clips must end at M";
+        return nullptr;
+    }
+    if (op == QASR_CODEC_VQ) {
+        if (g.Q < 1 || g.Q > 64 || g.C < 1 || g.C > 4096 || g.S0 < 1 || g.S0 > 65536 || g.S1 < 1 || g.S1 > 65536)
+            return "codec case: the quantiser needs Q in [1, 64], C in [1, 4096], S0 and S1 in [1, 65536]";
+        if (!bias || !sa || !lb) return "codec case: the quantiser needs the first codebook's transpose and norms, and codes";
+        if (g.Q > 1 && (!sb || !ls || !R)) return "codec case: the quantiser needs the later codebooks, their transposes and norms";
+        if ((long)g.n_loc != ((long)g.M + g.out_extra) * g.Q) return "codec case: codes must hold [M + out_extra][Q]";
+        return nullptr;
+    }
+    if (op == QASR_CODEC_CENC_IN) {
+        if (g.C < 1 || g.C > 65536 || g.a_rows < g.M) return "codec case: the input conv needs C in [1, 65536] and a_rows >= M";
+        if (!la || !bias || g.n_clips < 1 || g.n_clips > g.M || g.n_loc != g.n_clips + 1) return "codec case: the input conv needs its bias and n_clips + 1 clip starts";
+        if (la[0] != 0 || la[g.n_clips] != g.M) return "codec case: the clip starts must run from 0 to M";
+        for (int c = 0; c < g.n_clips; ++c)
+            if (la[c + 1] <= la[c]) return "codec case: the clip starts must increase";
+        return nullptr;
+    }
+    if (kind < QASR_CODEC_ROWS_WINDOW || kind > QASR_CODEC_ROWS_VAE_STRIDE) return "codec case: unknown row locator";
+    if (op == QASR_CODEC_OUT) {
+        if (kind != QASR_CODEC_ROWS_WINDOW && kind != QASR_CODEC_ROWS_TAIL) return "codec case: the output conv runs under WindowRows or TailRows";
+        if (g.C < 1 || g.C > 65536 || g.a_rows < g.M || (g.clip != 0 && g.clip != 1)) return "codec case: the output conv needs C in [1, 65536], a_rows >= M, clip 0 or 1";
+        if (!bias || !sa || !sb) return "codec case: the output conv needs its bias and snake";
+    }
+    if (g.rate < 1 || g.rate > 64 || g.stride < 1 || g.stride > 64) return "codec case: rate and stride in [1, 64]";
+    // the locator's arrays
+    const bool frames = kind != QASR_CODEC_ROWS_CLIP;
+    if (frames) {
+        const int nf = (g.M + g.rate - 1) / g.rate;
+        if (!la || g.n_loc != nf) return "codec case: fstart must hold ceil(M / rate) entries";
+        for (int f = 0; f < nf; ++f)
+            if (la[f] != f && (f == 0 || la[f] != la[f - 1])) return "codec case: fstart[f] must be f or fstart[f - 1]";
+        if (kind == QASR_CODEC_ROWS_TAIL) {
+            if (!lb || g.lead < 0 || g.lead > lim) return "codec case: TailRows needs kept and lead in [0, 2^20]";
+            int end = nf - 1;                          // the last frame row of f's window, walking backwards
+            for (int f = nf - 1; f >= 0; --f) {
+                if (f + 1 < nf && la[f + 1] != la[f]) end = f;
+                if (lb[f] < la[f] || lb[f] > end) return "codec case: kept must lie inside its window's frame rows";
+                if (f > 0 && la[f] == la[f - 1] && lb[f] != lb[f - 1]) return "codec case: kept must be one value per window";
+            }
+        }
+    } else if (la || lb) {
+        if (!la || !lb || g.n_clips < 1 || g.n_clips > g.M || g.n_loc != g.n_clips + 1) return "codec case: ClipRows needs ostart, istart and n_loc = n_clips + 1";
+        if (la[0] != 0 || la[g.n_clips] != g.M) return "codec case: ostart must run from 0 to M";
+        if (lb[0] < 0) return "codec case: istart points outside";
+        for (int c = 0; c < g.n_clips; ++c) {
+            if (la[c + 1] <= la[c]) return "codec case: ostart must increase";
+            if (lb[c + 1] < lb[c] || lb[c + 1] > g.a_rows) return "codec case: istart must not decrease and must stay inside A";
+        }
+    } else if (g.n_loc != 0) {
+        return "codec case: n_loc without locator arrays";
+    }
+    // every output row's span, as the locator forms it
+    auto span_ok = [&](long m) {
+        long last, first;
+        if (kind == QASR_CODEC_ROWS_WINDOW || kind == QASR_CODEC_ROWS_TAIL) { last = m; first = (long)la[m / g.rate] * g.rate; }
+        else if (kind == QASR_CODEC_ROWS_VAE_STRIDE) { last = (m + 1) * g.stride - 1; first = (long)la[m / g.rate] * g.rate * g.stride; }
+        else if (!la) { last = m; first = 0; }
+        else {
+            int c = 0;
+            while (c + 1 < g.n_clips && la[c + 1] <= m) ++c;
+            first = lb[c];
+            last = first + (m - la[c]) * g.stride;
+        }
+        return first >= 0 && last >= 0 && last < g.a_rows;
+    };
+    for (long m = 0; m < g.M; ++m)
+        if (!span_ok(m)) return "codec case: an output row would read outside A";
+    if (op == QASR_CODEC_OUT) return nullptr;
+    if (op == QASR_CODEC_VAE_UNIT) {
+        if (kind != QASR_CODEC_ROWS_WINDOW) return "codec case: the AudioVAE's fused unit runs under WindowRows";
+        if (g.C < 4 || g.C > 128 || (g.C & 3)) return "codec case: the fused unit holds C a multiple of 4 up to AV_FUSE_MAX";
+        if (g.dil < 1 || g.dil > 9 || g.a_rows < g.M) return "codec case: the fused unit needs dil in [1, 9] and a_rows >= M";
+        if ((sa == nullptr) != (sb == nullptr)) return "codec case: the map needs both a and 1 / a";
+        if (ls && !sa) return "codec case: an affine without the map";
+        if (bias || R) return "codec case: the fused unit takes its parameters packed in Wt";
+        return nullptr;
+    }
+    if (op == QASR_CODEC_VAE_DW) {
+        if (kind != QASR_CODEC_ROWS_WINDOW) return "codec case: the AudioVAE's depthwise conv runs under WindowRows";
+        if (g.C < 1 || g.C > 65536 || g.dil < 1 || g.dil > 27 || g.a_rows < g.M) return "codec case: the AudioVAE's depthwise conv needs C in [1, 65536], dil in [1, 27], a_rows >= M";
+        if (!bias || (g.snake != 0 && g.snake != 1)) return "codec case: the AudioVAE's depthwise conv needs its bias; snake is 0 or 1";
+        if (g.snake && (!sa || !sb || !ls || !R)) return "codec case: the snakes need a1, 1 / a1, a2, 1 / a2";
+        return nullptr;
+    }
+    if (op == QASR_CODEC_DWLN) {
+        if (kind != QASR_CODEC_ROWS_WINDOW && kind != QASR_CODEC_ROWS_CLIP) return "codec case: the depthwise conv runs under WindowRows or ClipRows";
+        if (kind == QASR_CODEC_ROWS_CLIP && (!la || g.stride != 1)) return "codec case: the depthwise conv under ClipRows needs clip starts and stride 1";
+        if (kind == QASR_CODEC_ROWS_CLIP)
+            for (int c = 0; c <= g.n_clips; ++c)
+                if (la[c] != lb[c]) return "codec case: the depthwise conv's input and output rows are the same";
+        if (g.C < 1 || g.C > 4096) return "codec case: the depthwise conv holds a row of at most 4096 channels";
+        if (!bias || !sa || !sb) return "codec case: the depthwise conv needs its bias and the LayerNorm's weight and bias";
+        return nullptr;
+    }
+    if (!qasr::codec_tile_served(kind, g.snake != 0, g.epi) || (g.snake != 0 && g.snake != 1))
+        return "codec case: no codec_gemm_kernel for this (row locator, snake, epilogue)";
+    if (g.Cin < 1 || g.Cin > 65536 || g.N < 1 || g.N > 65536 || g.taps < 1 || g.taps > 64 || g.dil < 1 || g.dil > 64)
+        return "codec case: Cin, N in [1, 65536], taps, dil in [1, 64]";
+    if ((long)g.K != (long)g.taps * g.Cin) return "codec case: K must be taps * Cin";
+    if (kind == QASR_CODEC_ROWS_CLIP && !la && g.taps != 1) return "codec case: independent rows take one tap";
+    const int epi = g.epi;
+    if (epi == qasr::E_SWIGLU && (g.N & 1)) return "codec case: E_SWIGLU needs an even N";
+    if (g.ldc < (epi == qasr::E_SWIGLU ? g.N / 2 : g.N) || g.ldc > 65536) return "codec case: ldc below the columns written";
+    if (bias && (g.bmod < 1 || g.bmod > g.N)) return "codec case: bmod in [1, N]";
+    if (g.snake && (!sa || !sb)) return "codec case: the snake load needs its a and b";
+    if (epi == qasr::E_RESMAP && (!sa || !sb)) return "codec case: E_RESMAP needs the map's a and b";
+    if (epi == qasr::E_LSRES && !ls) return "codec case: E_LSRES needs ls";
+    const bool residual = epi == qasr::E_RES || epi == qasr::E_LSRES || epi == qasr::E_RESMAP;
+    if (g.in_place != 0 && g.in_place != 1) return "codec case: in_place is 0 or 1";
+    if (g.in_place && (!residual || R)) return "codec case: in_place needs a residual epilogue and no R";
+    if ((epi == qasr::E_RES || epi == qasr::E_LSRES) && !g.in_place && !R) return "codec case: a residual epilogue needs R or in_place";
+    if (!residual && R) return "codec case: R without a residual epilogue";
     return nullptr;
 }
 
@@ -504,6 +673,13 @@ int qasr_syn_attn_case_probe(qasr_engine* e, int op, const qasr_syn_attn_case* g
     if (const char* why = syn_attn_case_refusal(op, *g, qkv, slot, pos, qn_w, kn_w, cos, sin, kcache, vcache, qr, out))
         return fail(e, QASR_ERR_INVALID, why);
     return on_device(e, [&] { e->impl->syn_attn_case_probe(op, *g, qkv, slot, pos, qn_w, kn_w, cos, sin, kcache, vcache, qr, out); });
+}
+
+int qasr_codec_case_probe(qasr_engine* e, int op, const qasr_codec_case* g, const float* A, const float* Wt, const float* bias, const float* sa,
+                          const float* sb, const float* ls, const float* R, const int32_t* loc_a, int32_t* loc_b, float* out) {
+    if (!e || !g) return QASR_ERR_INVALID;
+    if (const char* why = codec_case_refusal(op, *g, A, Wt, bias, sa, sb, ls, R, loc_a, loc_b, out)) return fail(e, QASR_ERR_INVALID, why);
+    return on_device(e, [&] { e->impl->codec_case_probe(op, *g, A, Wt, bias, sa, sb, ls, R, loc_a, loc_b, out); });
 }
 
 int qasr_enc_case_probe(qasr_engine* e, int op, const qasr_enc_case* g, const void* in, const int32_t* idx, const int64_t* off, const float* pf,

@@ -108,6 +108,11 @@ __global__ __launch_bounds__(ROW_THREADS) void cenc_in_kernel(const float* __res
     y[e] = acc + b[c];
 }
 
+// the kernel's launch entry (codec_launch.h): CodecEncQwen3TTS::dev_convs and qasr_codec_case_probe call this
+void cenc_in_launch(const float* pcm, long M, int C, const int* start, int nclips, const float* w, const float* b, float* y, hipStream_t s) {
+    hipLaunchKernelGGL(cenc_in_kernel, dim3((unsigned)cdiv(M * C, ROW_THREADS)), dim3(ROW_THREADS), 0, s, pcm, M, C, start, nclips, w, b, y);
+}
+
 // qkv [M][3 A] (A = heads x 64); tiles[b] = (the clip's first row, its frames, the tile's first query); rope [positions][32] (cos, sin);
 // out [M][A].  grid (query tiles, heads).  Thread (i = tid / 8, g = tid % 8) owns outputs 8 g .. 8 g + 7 of query i: per K / V tile the
 // 32 x 32 scores go through LDS, then the row's running max m, sum l and accumulators are updated over the tile's keys in order (the
@@ -273,6 +278,19 @@ __global__ __launch_bounds__(CG_THREADS) void cenc_vq_kernel(float* r, long M, i
     }
 }
 
+// the kernel's launch entry (codec_launch.h): CodecEncQwen3TTS::dev_transformer and qasr_codec_case_probe call this
+void cenc_attn_launch(const float* qkv, const int* tiles, int n_tiles, const float* rope, int heads, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(cenc_attn_kernel, dim3((unsigned)n_tiles, (unsigned)heads), dim3(ROW_THREADS), 0, s, qkv, reinterpret_cast<const int4*>(tiles),
+                       reinterpret_cast<const float2*>(rope), heads, out);
+}
+
+// the kernel's launch entry (codec_launch.h): CodecEncQwen3TTS::dev_rvq and qasr_codec_case_probe call this
+void cenc_vq_launch(float* r, long M, int ldr, int D, int Q, const float* cb0, const float* cbt0, const float* csq0, int S0, const float* cb1,
+                    const float* cbt1, const float* csq1, int S1, int* codes, hipStream_t s) {
+    hipLaunchKernelGGL(cenc_vq_kernel, dim3((unsigned)cdiv(M, CG_T), 2), dim3(CG_THREADS), 0, s, r, M, ldr, D, Q, cb0, cbt0, csq0, S0, cb1, cbt1,
+                       csq1, S1, codes);
+}
+
 // ---- weights ------------------------------------------------------------------------------------------------------------------------
 CodecEncQwen3TTS::CodecEncQwen3TTS(int device, const CheckedWeights& cw, const CodecGeom& g, const std::vector<bool>& embed_stored,
                                    long max_samples, hipStream_t work)
@@ -433,11 +451,14 @@ void CodecEncQwen3TTS::plan(const CodecEncClip* c, int n) {
 template <bool SNAKE, int EPI>
 void CodecEncQwen3TTS::gemm(const Gemm& gm, const float* A, long M, int dil, int stride, int level, int in_level, const Snake* sn,
                             const float* ls, const float* R, float* C, int ldc) {
-    const dim3 grid((unsigned)cdiv(M, CG_T), (unsigned)cdiv(gm.N, CG_T));
-    const ClipRows rows{level < 0 ? nullptr : starts(level), level < 0 ? nullptr : starts(in_level), n_clips_, stride};
-    hipLaunchKernelGGL((codec_gemm_kernel<ClipRows, SNAKE, EPI>), grid, dim3(CG_THREADS), 0, work_, A, M, gm.Cin, gm.taps, dil, rows,
-                       W(gm.wt), gm.K, gm.N, gm.has_bias ? W(gm.bias) : (const float*)nullptr, gm.N, sn ? W(sn->a) : (const float*)nullptr,
-                       sn ? W(sn->b) : (const float*)nullptr, ls, R, C, ldc);
+    CodecRowsArg rows;
+    rows.kind = CODEC_ROWS_CLIP;
+    rows.a = level < 0 ? nullptr : starts(level);
+    rows.b = level < 0 ? nullptr : starts(in_level);
+    rows.n_clips = n_clips_;
+    rows.stride = stride;
+    codec_tile_launch(rows, SNAKE, EPI, A, M, gm.Cin, gm.taps, dil, W(gm.wt), gm.K, gm.N, gm.has_bias ? W(gm.bias) : (const float*)nullptr, gm.N,
+                      sn ? W(sn->a) : (const float*)nullptr, sn ? W(sn->b) : (const float*)nullptr, ls, R, C, ldc, work_);
 }
 
 // d_pcm_ -> conv_out_ [frames][latent]; records ev_[1] .. ev_[6]
@@ -445,8 +466,7 @@ void CodecEncQwen3TTS::dev_convs() {
     const int L = g_.latent;
     float *a = d_big_[0].as<float>(), *t = d_big_[1].as<float>(), *o = d_big_[2].as<float>();
     int C = width_[0];
-    hipLaunchKernelGGL(cenc_in_kernel, dim3((unsigned)cdiv(M_[0] * C, ROW_THREADS)), dim3(ROW_THREADS), 0, work_, d_pcm_.as<float>(), M_[0],
-                       C, starts(0), n_clips_, W(in_w_), W(in_b_), a);
+    cenc_in_launch(d_pcm_.as<float>(), M_[0], C, starts(0), n_clips_, W(in_w_), W(in_b_), a, work_);
     QASR_HIP(hipEventRecord(ev_[1], work_));
     const int dil[3] = {1, 3, 9};
     for (int k = 0; k < 4; ++k) {                      // three residual units, SnakeBeta, strided conv (:63-70)
@@ -465,8 +485,11 @@ void CodecEncQwen3TTS::dev_convs() {
     for (int i = 0; i < 2; ++i) {                      // ConvNeXt, strided conv (:233-236)
         const Down& u = down_[i];
         const int lv = 4 + i;
-        hipLaunchKernelGGL(codec_dwln_kernel<ClipRows>, dim3((unsigned)M_[lv]), dim3(ROW_THREADS), 0, work_, a, L,
-                           ClipRows{starts(lv), starts(lv), n_clips_, 1}, W(u.dw), W(u.dwb), W(u.lnw), W(u.lnb), t);
+        CodecRowsArg rows;
+        rows.kind = CODEC_ROWS_CLIP;
+        rows.a = rows.b = starts(lv);
+        rows.n_clips = n_clips_;
+        codec_dwln_launch(rows, a, M_[lv], L, W(u.dw), W(u.dwb), W(u.lnw), W(u.lnb), t, work_);
         gemm<false, E_GELU>(u.pw1, t, M_[lv], 1, 1, -1, -1, nullptr, nullptr, nullptr, o, 4 * L);
         gemm<false, E_LSRES>(u.pw2, o, M_[lv], 1, 1, -1, -1, nullptr, W(u.gamma), a, a, L);
         gemm<false, E_LIN>(u.sconv, a, M_[lv + 1], 1, stride_[lv], lv + 1, lv, nullptr, nullptr, nullptr, t, L);
@@ -485,16 +508,15 @@ void CodecEncQwen3TTS::dev_transformer() {
     float *x = d_x_.as<float>(), *h = d_h_.as<float>(), *qkv = d_qkv_.as<float>(), *att = d_att_.as<float>(), *gg = d_g_.as<float>();
     gemm<false, E_LIN>(in_proj_, conv_out_, M, 1, 1, -1, -1, nullptr, nullptr, nullptr, x, H);
     for (const CodecLayer& ly : layers_) {
-        hipLaunchKernelGGL(codec_rms_kernel<>, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(ly.n1), g_.eps, h);
+        codec_rms_launch(x, M, H, W(ly.n1), g_.eps, h, work_);
         gemm<false, E_LIN>(ly.qkv, h, M, 1, 1, -1, -1, nullptr, nullptr, nullptr, qkv, 3 * A);
-        hipLaunchKernelGGL(cenc_attn_kernel, dim3((unsigned)n_tiles_, (unsigned)g_.heads), dim3(ROW_THREADS), 0, work_, qkv,
-                           d_tiles_.as<int4>(), reinterpret_cast<const float2*>(W(rope_)), g_.heads, att);
+        cenc_attn_launch(qkv, d_tiles_.as<int>(), n_tiles_, W(rope_), g_.heads, att, work_);
         gemm<false, E_LSRES>(ly.o, att, M, 1, 1, -1, -1, nullptr, W(ly.ls1), x, x, H);
-        hipLaunchKernelGGL(codec_rms_kernel<>, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(ly.n2), g_.eps, h);
+        codec_rms_launch(x, M, H, W(ly.n2), g_.eps, h, work_);
         gemm<false, E_SWIGLU>(ly.gu, h, M, 1, 1, -1, -1, nullptr, nullptr, nullptr, gg, 2 * H);
         gemm<false, E_LSRES>(ly.down, gg, M, 1, 1, -1, -1, nullptr, W(ly.ls2), x, x, H);
     }
-    hipLaunchKernelGGL(codec_rms_kernel<>, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(norm_), g_.eps, h);
+    codec_rms_launch(x, M, H, W(norm_), g_.eps, h, work_);
     QASR_HIP(hipEventRecord(ev_[7], work_));
     QASR_HIP(hipGetLastError());
 }
@@ -503,9 +525,8 @@ void CodecEncQwen3TTS::dev_transformer() {
 void CodecEncQwen3TTS::dev_rvq(long F) {
     const int D = g_.codebook_dim;
     gemm<false, E_LIN>(rvq_, d_h_.as<float>(), F, 1, 1, -1, -1, nullptr, nullptr, nullptr, d_r_.as<float>(), 2 * D);
-    hipLaunchKernelGGL(cenc_vq_kernel, dim3((unsigned)cdiv(F, CG_T), 2), dim3(CG_THREADS), 0, work_, d_r_.as<float>(), F, 2 * D, D,
-                       g_.quantizers, W(cb_[0]), W(cbt_[0]), W(csq_[0]), g_.semantic_size, W(cb_[1]), W(cbt_[1]), W(csq_[1]),
-                       g_.acoustic_size, d_codes_.as<int>());
+    cenc_vq_launch(d_r_.as<float>(), F, 2 * D, D, g_.quantizers, W(cb_[0]), W(cbt_[0]), W(csq_[0]), g_.semantic_size, W(cb_[1]), W(cbt_[1]),
+                   W(csq_[1]), g_.acoustic_size, d_codes_.as<int>(), work_);
     QASR_HIP(hipEventRecord(ev_[8], work_));
     QASR_HIP(hipGetLastError());
 }

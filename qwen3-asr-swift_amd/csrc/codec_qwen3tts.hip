@@ -178,6 +178,23 @@ __global__ __launch_bounds__(ROW_THREADS) void codec_out_kernel(const float* __r
     wave[m] = acc;
 }
 
+// the launch entries of the kernels above (codec_launch.h): CodecQwen3TTS and qasr_codec_case_probe call these
+void codec_attn_launch(const float* qkv, const int* win, int n_win, const float* rope, int heads, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(codec_attn_kernel, dim3((unsigned)n_win, (unsigned)heads), dim3(ROW_THREADS), 0, s, qkv, reinterpret_cast<const int2*>(win),
+                       reinterpret_cast<const float2*>(rope), heads, out);
+}
+
+void codec_gather_launch(const int* codes, long M, int Q, int D, long S0, long S1, const float* cb, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(codec_gather_kernel, dim3((unsigned)M), dim3(ROW_THREADS), 0, s, codes, Q, D, S0, S1, cb, out);
+}
+
+void codec_out_launch(bool tail, const float* x, long M, int C, int rate, const int* fstart, const int* kept, const float* sa, const float* sb,
+                      const float* w, const float* b, int clip, float* wave, hipStream_t s) {
+    const dim3 grid((unsigned)cdiv(M, ROW_THREADS));
+    if (tail) hipLaunchKernelGGL(codec_out_kernel<true>, grid, dim3(ROW_THREADS), 0, s, x, M, C, rate, fstart, kept, sa, sb, w, b, clip, wave);
+    else hipLaunchKernelGGL(codec_out_kernel<false>, grid, dim3(ROW_THREADS), 0, s, x, M, C, rate, fstart, kept, sa, sb, w, b, clip, wave);
+}
+
 // ---- weights ------------------------------------------------------------------------------------------------------------------------
 CodecQwen3TTS::CodecQwen3TTS(int device, const CheckedWeights& cw, const CodecGeom& g, const std::vector<bool>& embed_stored,
                              int max_windows, hipStream_t work)
@@ -351,24 +368,23 @@ void CodecQwen3TTS::plan(const CodecWin* w, int n, bool with_codes) {
 template <bool SNAKE, int EPI>
 void CodecQwen3TTS::gemm(const Gemm& gm, const float* A, long M, int dil, int rate, const Snake* sn, const float* ls, const float* R, float* C,
                          int ldc, int bmod, int lead) {
-    const dim3 grid((unsigned)cdiv(M, CG_T), (unsigned)cdiv(gm.N, CG_T));
+    CodecRowsArg rows;
+    rows.a = d_fstart_.as<int>();
+    rows.rate = rate;
     if constexpr (EPI == E_LIN || (SNAKE && EPI == E_RES)) {           // the vocoder's launches from decoder.decoder.0 on
         if (lead >= 0) {
-            hipLaunchKernelGGL((codec_gemm_kernel<TailRows, SNAKE, EPI>), grid, dim3(CG_THREADS), 0, work_, A, M, gm.Cin, gm.taps, dil,
-                               TailRows{d_fstart_.as<int>(), d_kept_.as<int>(), rate, lead}, W(gm.wt), gm.K, gm.N,
-                               gm.has_bias ? W(gm.bias) : (const float*)nullptr, bmod, sn ? W(sn->a) : (const float*)nullptr,
-                               sn ? W(sn->b) : (const float*)nullptr, ls, R, C, ldc);
-            return;
+            rows.kind = CODEC_ROWS_TAIL;
+            rows.b = d_kept_.as<int>();
+            rows.lead = lead;
         }
     }
-    hipLaunchKernelGGL((codec_gemm_kernel<WindowRows, SNAKE, EPI>), grid, dim3(CG_THREADS), 0, work_, A, M, gm.Cin, gm.taps, dil,
-                       WindowRows{d_fstart_.as<int>(), rate}, W(gm.wt), gm.K, gm.N, gm.has_bias ? W(gm.bias) : (const float*)nullptr, bmod,
-                       sn ? W(sn->a) : (const float*)nullptr, sn ? W(sn->b) : (const float*)nullptr, ls, R, C, ldc);
+    codec_tile_launch(rows, SNAKE, EPI, A, M, gm.Cin, gm.taps, dil, W(gm.wt), gm.K, gm.N, gm.has_bias ? W(gm.bias) : (const float*)nullptr, bmod,
+                      sn ? W(sn->a) : (const float*)nullptr, sn ? W(sn->b) : (const float*)nullptr, ls, R, C, ldc, work_);
 }
 
 void CodecQwen3TTS::dev_rvq() {
-    hipLaunchKernelGGL(codec_gather_kernel, dim3((unsigned)M1_), dim3(ROW_THREADS), 0, work_, d_codes_.as<int>(), g_.quantizers,
-                       g_.codebook_dim, (long)g_.semantic_size, (long)g_.acoustic_size, W(cb_first_), d_emb_.as<float>());
+    codec_gather_launch(d_codes_.as<int>(), M1_, g_.quantizers, g_.codebook_dim, (long)g_.semantic_size, (long)g_.acoustic_size, W(cb_first_),
+                        d_emb_.as<float>(), work_);
     gemm<false, E_LIN>(rvq_, d_emb_.as<float>(), M1_, 1, 1, nullptr, nullptr, nullptr, d_q_.as<float>(), g_.hidden, g_.hidden);
     QASR_HIP(hipGetLastError());
 }
@@ -380,16 +396,15 @@ void CodecQwen3TTS::dev_pre_transformer() {
     float *x = d_x_.as<float>(), *h = d_h_.as<float>(), *qkv = d_qkv_.as<float>(), *att = d_att_.as<float>(), *gg = d_g_.as<float>();
     gemm<false, E_LIN>(in_proj_, d_lat_[0].as<float>(), M, 1, 1, nullptr, nullptr, nullptr, x, H, H);
     for (const CodecLayer& ly : layers_) {
-        hipLaunchKernelGGL(codec_rms_kernel<>, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(ly.n1), g_.eps, h);
+        codec_rms_launch(x, M, H, W(ly.n1), g_.eps, h, work_);
         gemm<false, E_LIN>(ly.qkv, h, M, 1, 1, nullptr, nullptr, nullptr, qkv, 3 * A, 3 * A);
-        hipLaunchKernelGGL(codec_attn_kernel, dim3((unsigned)n_win_, (unsigned)g_.heads), dim3(ROW_THREADS), 0, work_, qkv,
-                           d_win_.as<int2>(), reinterpret_cast<const float2*>(W(rope_)), g_.heads, att);
+        codec_attn_launch(qkv, d_win_.as<int>(), n_win_, W(rope_), g_.heads, att, work_);
         gemm<false, E_LSRES>(ly.o, att, M, 1, 1, nullptr, W(ly.ls1), x, x, H, H);
-        hipLaunchKernelGGL(codec_rms_kernel<>, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(ly.n2), g_.eps, h);
+        codec_rms_launch(x, M, H, W(ly.n2), g_.eps, h, work_);
         gemm<false, E_SWIGLU>(ly.gu, h, M, 1, 1, nullptr, nullptr, nullptr, gg, 2 * H, 2 * H);
         gemm<false, E_LSRES>(ly.down, gg, M, 1, 1, nullptr, W(ly.ls2), x, x, H, H);
     }
-    hipLaunchKernelGGL(codec_rms_kernel<>, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, x, H, W(norm_), g_.eps, h);
+    codec_rms_launch(x, M, H, W(norm_), g_.eps, h, work_);
     gemm<false, E_LIN>(out_proj_, h, M, 1, 1, nullptr, nullptr, nullptr, d_lat_[1].as<float>(), L, L);
     QASR_HIP(hipGetLastError());
 }
@@ -410,8 +425,10 @@ void CodecQwen3TTS::dev_vocoder(bool clip, bool tail) {
         gemm<false, E_LIN>(u.tconv, x, M1_ * rate, 1, rate, nullptr, nullptr, nullptr, y, u.tconv.N, L);
         rate *= g_.ratios[i];
         const long M = M1_ * rate;
-        hipLaunchKernelGGL(codec_dwln_kernel<WindowRows>, dim3((unsigned)M), dim3(ROW_THREADS), 0, work_, y, L,
-                           WindowRows{d_fstart_.as<int>(), rate}, W(u.dw), W(u.dwb), W(u.lnw), W(u.lnb), h);
+        CodecRowsArg rows;
+        rows.a = d_fstart_.as<int>();
+        rows.rate = rate;
+        codec_dwln_launch(rows, y, M, L, W(u.dw), W(u.dwb), W(u.lnw), W(u.lnb), h, work_);
         gemm<false, E_GELU>(u.pw1, h, M, 1, rate, nullptr, nullptr, nullptr, mid, 4 * L, 4 * L);
         gemm<false, E_LSRES>(u.pw2, mid, M, 1, rate, nullptr, W(u.gamma), y, y, L, L);
         x = y;
@@ -444,14 +461,8 @@ void CodecQwen3TTS::dev_vocoder(bool clip, bool tail) {
         QASR_HIP(hipEventRecord(ev_[4 + k], work_));
     }
     const long M = M1_ * rate;
-    if (tail)
-        hipLaunchKernelGGL(codec_out_kernel<true>, dim3((unsigned)cdiv(M, ROW_THREADS)), dim3(ROW_THREADS), 0, work_, buf[cur], M, C, rate,
-                           d_fstart_.as<int>(), d_kept_.as<int>(), W(final_snake_.a), W(final_snake_.b), W(final_w_), W(final_b_), clip ? 1 : 0,
-                           d_wave_.as<float>());
-    else
-        hipLaunchKernelGGL(codec_out_kernel<false>, dim3((unsigned)cdiv(M, ROW_THREADS)), dim3(ROW_THREADS), 0, work_, buf[cur], M, C, rate,
-                           d_fstart_.as<int>(), d_kept_.as<int>(), W(final_snake_.a), W(final_snake_.b), W(final_w_), W(final_b_), clip ? 1 : 0,
-                           d_wave_.as<float>());
+    codec_out_launch(tail, buf[cur], M, C, rate, d_fstart_.as<int>(), d_kept_.as<int>(), W(final_snake_.a), W(final_snake_.b), W(final_w_),
+                     W(final_b_), clip ? 1 : 0, d_wave_.as<float>(), work_);
     QASR_HIP(hipEventRecord(ev_[8], work_));
     QASR_HIP(hipGetLastError());
 }

@@ -10,6 +10,7 @@
 // sequential partial over c = tid, tid + 256, .. then a fixed tree.
 #pragma once
 #include "engine.h"
+#include "codec_launch.h"
 #include "safetensors.h"
 #include <algorithm>
 #include <string>
@@ -69,8 +70,7 @@ CodecLayer codec_pack_layer(Builder& b, const std::string& p, int H, int A);
 size_t codec_pack_rope(Builder& b, long n);
 
 // ---- kernels ------------------------------------------------------------------------------------------------------------------------
-constexpr int CG_THREADS = 256, CG_T = 64, CG_K = 16, ROW_THREADS = 256;
-enum { E_LIN = 0, E_GELU = 1, E_RES = 2, E_LSRES = 3, E_SWIGLU = 4, E_RESMAP = 5 };
+constexpr int CG_THREADS = 256, CG_T = 64, CG_K = 16, ROW_THREADS = 256;      // the epilogues E_* are in codec_launch.h
 
 // x + (1 / exp(beta)) sin^2(exp(alpha) x) with a = exp(alpha), b = 1 / exp(beta) formed at load (SpeechTokenizerDecoder.swift:105-110)
 __device__ __forceinline__ float codec_snake(float x, float a, float b) {
@@ -142,6 +142,18 @@ struct ClipRows {
         const int clip = clip_of(ostart, nclips, m);
         const long first = istart[clip];
         return {first + (m - ostart[clip]) * stride, first};
+    }
+};
+
+// the AudioVAE's strided conv (k = 2 s, stride s): output row m (rate rows per frame) reads input rows (m - 1) s .. (m + 1) s - 1 of its
+// own clip
+struct VaeStrideRows {
+    static constexpr bool BIAS_REPEATS = false;
+    static constexpr bool SKIPS = false;
+    const int* fstart;
+    int rate, stride;
+    __device__ __forceinline__ RowSpan operator()(long m) const {
+        return {(m + 1) * stride - 1, (long)fstart[m / rate] * rate * stride};
     }
 };
 

@@ -159,6 +159,10 @@ public:
     void attn_case_probe(int op, const qasr_attn_case& g, uint16_t* qkv, const uint16_t* x, const uint16_t* W, const int32_t* cu,
                          const int32_t* slot_of_clip, const int32_t* pos, const int32_t* slot, const uint16_t* qn_w, const uint16_t* kn_w,
                          uint16_t* kcache, uint16_t* vfrag, const uint16_t* vt, uint16_t* qr, uint16_t* out);
+    // qasr_codec_case_probe (csrc/codec_cases.hip): one launch of a codec_launch.h entry (every f32 kernel of the waveform codecs but the AudioVAE's
+    // one-thread-per-output conv_in and output kernels)
+    void codec_case_probe(int op, const qasr_codec_case& g, const float* A, const float* Wt, const float* bias, const float* sa, const float* sb,
+                          const float* ls, const float* R, const int32_t* loc_a, int32_t* loc_b, float* out);
     // qasr_syn_attn_case_probe (csrc/syn_attn_cases.hip): one launch of a synthesis stack's attention entry (CosyVoice LLM, code predictor, VoxCPM2)
     void syn_attn_case_probe(int op, const qasr_syn_attn_case& g, const void* qkv, const int32_t* slot, const int32_t* pos, const uint16_t* qn_w,
                              const uint16_t* kn_w, const float* cos, const float* sin, uint16_t* kcache, uint16_t* vcache, uint16_t* qr, void* out);

@@ -20,17 +20,6 @@
 namespace qasr {
 
 // ---- kernels ------------------------------------------------------------------------------------------------------------------------
-// a strided conv's rows: output row m (rate rows per frame) reads input rows (m - 1) s .. (m + 1) s - 1 of its own clip
-struct VaeStrideRows {
-    static constexpr bool BIAS_REPEATS = false;
-    static constexpr bool SKIPS = false;
-    const int* fstart;
-    int rate, stride;
-    __device__ __forceinline__ RowSpan operator()(long m) const {
-        return {(m + 1) * stride - 1, (long)fstart[m / rate] * rate * stride};
-    }
-};
-
 // y = [snake2](b + sum_j w[j][c] [snake1](x[m - (6 - j) dil][c])), j = 0..6 in order.  grid (row slabs of 64, channel tiles of 64),
 // LDS (64 + 6 dil) x 64 floats.
 template <bool SIN, bool SOUT>
@@ -517,44 +506,66 @@ bool AudioVaeVoxcpm::stage_shape(bool decoder, int k, int* rows_per_frame, int* 
 }
 
 // ---- launches -----------------------------------------------------------------------------------------------------------------------
+// vae_dw_kernel's launch entry (codec_launch.h): AudioVaeVoxcpm and qasr_codec_case_probe call this.  The two forms the model has: both
+// snakes (a residual unit's depthwise conv) or neither (the decoder's conv_in)
+void vae_dw_launch(bool snakes, const float* x, long M, int C, int dil, const int* fstart, int rate, const float* w, const float* b, const float* a1,
+                   const float* i1, const float* a2, const float* i2, float* y, hipStream_t s) {
+    const dim3 grid((unsigned)cdiv(M, (long)AV_SLAB), (unsigned)cdiv(C, 64));
+    const size_t lds = (size_t)(AV_SLAB + 6 * dil) * 64 * sizeof(float);
+    if (snakes) hipLaunchKernelGGL((vae_dw_kernel<true, true>), grid, dim3(256), lds, s, x, M, C, dil, fstart, rate, w, b, a1, i1, a2, i2, y);
+    else hipLaunchKernelGGL((vae_dw_kernel<false, false>), grid, dim3(256), lds, s, x, M, C, dil, fstart, rate, w, b, a1, i1, a2, i2, y);
+}
+
+// vae_unit_kernel's launch entry (codec_launch.h): AudioVaeVoxcpm::unit and qasr_codec_case_probe call this.  A thread owns RPT rows x 4
+// columns: 256 / (C / 4) threads share a column group, RPT is the power of two that lets them cover the slab's 64 rows
+void vae_unit_launch(const float* x, long M, int C, int dil, const int* fstart, int rate, const float* w1, const float* b1, const float* a1,
+                     const float* i1, const float* a2, const float* i2, const float* Wt, const float* b2, const float* ma, const float* mi,
+                     const float* aff, float* y, hipStream_t s) {
+    if (C < 4 || C > AV_FUSE_MAX || (C & 3) || dil < 1 || dil > 9)
+        throw std::invalid_argument("vae_unit_launch: C a multiple of 4 in [4, AV_FUSE_MAX], dil in [1, 9]");
+    const dim3 slabs((unsigned)cdiv(M, (long)AV_SLAB));
+    const int per = 256 / (C / 4), need = (AV_SLAB + per - 1) / per, rpt = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : 8;
+    const size_t lds = vae_unit_lds(C, dil);
+#define AV_UNIT(R)                                                                                                                    \
+    do {                                                                                                                              \
+        unit_lds_limit<R>();                                                                                                          \
+        hipLaunchKernelGGL((vae_unit_kernel<R>), slabs, dim3(256), lds, s, x, M, C, dil, fstart, rate, w1, b1, a1, i1, a2, i2, Wt, b2, ma, mi, \
+                           aff, y);                                                                                                   \
+    } while (0)
+    if (rpt == 1) AV_UNIT(1); else if (rpt == 2) AV_UNIT(2); else if (rpt == 4) AV_UNIT(4); else AV_UNIT(8);
+#undef AV_UNIT
+}
+
 void AudioVaeVoxcpm::gemm(const Gemm& g, int epi, long rows, int rate, int stride, const float* A, const float* R, float* C, const Map& map) {
-    const dim3 grid((unsigned)cdiv(rows, (long)CG_T), (unsigned)cdiv(g.N, CG_T)), block(CG_THREADS);
-    const int* fs = d_fstart_.as<int>();
+    CodecRowsArg ra;
+    ra.a = d_fstart_.as<int>();
+    ra.rate = rate;
     const float* none = nullptr;
     if (stride > 0) {
-        hipLaunchKernelGGL((codec_gemm_kernel<VaeStrideRows, false, E_LIN>), grid, block, 0, work_, A, rows, g.Cin, g.taps, 1, VaeStrideRows{fs, rate, stride},
-                           W(g.wt), g.K, g.N, W(g.bias), g.bmod, none, none, none, none, C, g.N);
+        ra.kind = CODEC_ROWS_VAE_STRIDE;
+        ra.stride = stride;
+        codec_tile_launch(ra, false, E_LIN, A, rows, g.Cin, g.taps, 1, W(g.wt), g.K, g.N, W(g.bias), g.bmod, none, none, none, none, C, g.N, work_);
         return;
     }
-    const WindowRows wr{fs, rate};
     if (epi == E_LIN)
-        hipLaunchKernelGGL((codec_gemm_kernel<WindowRows, false, E_LIN>), grid, block, 0, work_, A, rows, g.Cin, g.taps, 1, wr, W(g.wt), g.K, g.N, W(g.bias),
-                           g.bmod, none, none, none, none, C, g.N);
+        codec_tile_launch(ra, false, E_LIN, A, rows, g.Cin, g.taps, 1, W(g.wt), g.K, g.N, W(g.bias), g.bmod, none, none, none, none, C, g.N, work_);
     else if (epi == E_RES)
-        hipLaunchKernelGGL((codec_gemm_kernel<WindowRows, false, E_RES>), grid, block, 0, work_, A, rows, g.Cin, g.taps, 1, wr, W(g.wt), g.K, g.N, W(g.bias),
-                           g.bmod, none, none, none, R, C, g.N);
+        codec_tile_launch(ra, false, E_RES, A, rows, g.Cin, g.taps, 1, W(g.wt), g.K, g.N, W(g.bias), g.bmod, none, none, none, R, C, g.N, work_);
     else
-        hipLaunchKernelGGL((codec_gemm_kernel<WindowRows, false, E_RESMAP>), grid, block, 0, work_, A, rows, g.Cin, g.taps, 1, wr, W(g.wt), g.K, g.N,
-                           W(g.bias), g.bmod, map.a, map.inv, map.affine, R, C, g.N);
+        codec_tile_launch(ra, false, E_RESMAP, A, rows, g.Cin, g.taps, 1, W(g.wt), g.K, g.N, W(g.bias), g.bmod, map.a, map.inv, map.affine, R, C, g.N,
+                          work_);
 }
 
 // y = map(x + conv2(snake2(conv1(snake1(x))))); t is scratch of the wide path; y is not x
 void AudioVaeVoxcpm::unit(const Unit& u, long rows, int rate, const float* x, float* t, float* y, const Map& map) {
     const int* fs = d_fstart_.as<int>();
     const int fuse = tuning().vae_fuse_c, C = u.C;
-    const dim3 slabs((unsigned)cdiv(rows, (long)AV_SLAB));
     if (C <= fuse && C <= AV_FUSE_MAX && (C & 3) == 0) {
-        const int per = 256 / (C / 4), need = (AV_SLAB + per - 1) / per, rpt = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : 8;
-        const size_t lds = vae_unit_lds(C, u.dil);
-#define AV_UNIT(R)                                                                                                                           \
-    hipLaunchKernelGGL((vae_unit_kernel<R>), slabs, dim3(256), lds, work_, x, rows, C, u.dil, fs, rate, W(u.w1), W(u.b1), W(u.s1.a), W(u.s1.inv), \
-                       W(u.s2.a), W(u.s2.inv), W(u.c2.wt), W(u.c2.bias), map.a, map.inv, map.affine, y)
-        if (rpt == 1) AV_UNIT(1); else if (rpt == 2) AV_UNIT(2); else if (rpt == 4) AV_UNIT(4); else AV_UNIT(8);
-#undef AV_UNIT
+        vae_unit_launch(x, rows, C, u.dil, fs, rate, W(u.w1), W(u.b1), W(u.s1.a), W(u.s1.inv), W(u.s2.a), W(u.s2.inv), W(u.c2.wt), W(u.c2.bias), map.a,
+                        map.inv, map.affine, y, work_);
         return;
     }
-    hipLaunchKernelGGL((vae_dw_kernel<true, true>), dim3(slabs.x, (unsigned)cdiv(C, 64)), dim3(256), (size_t)(AV_SLAB + 6 * u.dil) * 64 * sizeof(float), work_,
-                       x, rows, C, u.dil, fs, rate, W(u.w1), W(u.b1), W(u.s1.a), W(u.s1.inv), W(u.s2.a), W(u.s2.inv), t);
+    vae_dw_launch(true, x, rows, C, u.dil, fs, rate, W(u.w1), W(u.b1), W(u.s1.a), W(u.s1.inv), W(u.s2.a), W(u.s2.inv), t, work_);
     gemm(u.c2, map.a ? E_RESMAP : E_RES, rows, rate, 0, t, x, y, map);
 }
 
@@ -608,9 +619,7 @@ void AudioVaeVoxcpm::run_decoder(int idx, int stage) {
     int C = cfg_.decoder_dim, e = 0;
     long rpf = 1;
     QASR_HIP(hipEventRecord(ev_[e++], work_));
-    hipLaunchKernelGGL((vae_dw_kernel<false, false>), dim3((unsigned)cdiv(frames_, (long)AV_SLAB), (unsigned)cdiv(cfg_.latent_dim, 64)), dim3(256),
-                       (size_t)(AV_SLAB + 6) * 64 * sizeof(float), work_, d_z_.as<float>(), frames_, cfg_.latent_dim, 1, fs, 1, W(dec_in_w_), W(dec_in_b_),
-                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, T);
+    vae_dw_launch(false, d_z_.as<float>(), frames_, cfg_.latent_dim, 1, fs, 1, W(dec_in_w_), W(dec_in_b_), nullptr, nullptr, nullptr, nullptr, T, work_);
     gemm(dec_in1_, stage == 0 ? E_LIN : E_RESMAP, frames_, 1, 0, T, nullptr, A, reader(0));
     QASR_HIP(hipEventRecord(ev_[e++], work_));
     for (int i = 0; i < nb && stage != i; ++i, C /= 2) {

@@ -175,6 +175,11 @@ class QasrSynAttnCase(C.Structure):
                [(n, C.c_int64) for n in ("qkv_elems", "cache_elems", "out_elems", "table_elems")] + [("eps", C.c_float)]
 
 
+class QasrCodecCase(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("rows_kind", "snake", "epi", "M", "a_rows", "out_extra", "Cin", "taps", "dil", "K", "N", "bmod", "ldc",
+                                         "rate", "stride", "lead", "n_clips", "n_loc", "in_place", "C", "Q", "S0", "S1", "clip", "heads", "hd", "n_table")] + [("eps", C.c_float)]
+
+
 class QasrEncCase(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("rows", "n_clips", "in_extra", "out_extra", "heads", "hd", "max_len", "D", "ld", "n_in", "n_mels",
                                          "mel_stride", "H1", "W1", "stride")] + [("eps", C.c_float)]
@@ -233,6 +238,7 @@ SIGNATURES = {
     "qasr_attn_case_probe": (C.c_int, [_E, C.c_int, _P(QasrAttnCase)] + [_P(C.c_uint16)] * 3 + [_I] * 4 + [_P(C.c_uint16)] * 7),
     "qasr_syn_attn_case_probe": (C.c_int, [_E, C.c_int, _P(QasrSynAttnCase), C.c_void_p, _I, _I, _P(C.c_uint16), _P(C.c_uint16), _F, _F] +
                                  [_P(C.c_uint16)] * 3 + [C.c_void_p]),
+    "qasr_codec_case_probe": (C.c_int, [_E, C.c_int, _P(QasrCodecCase)] + [_F] * 7 + [_I, _I, _F]),
     "qasr_enc_case_probe": (C.c_int, [_E, C.c_int, _P(QasrEncCase), C.c_void_p, _I, _P(C.c_int64), _F, _P(C.c_uint16), C.c_void_p]),
     "qasr_dec_case_probe": (C.c_int, [_E, C.c_int, _P(QasrDecCase), _P(C.c_uint16)] + [C.c_void_p] * 3 + [_P(C.c_uint16)] * 2 + [_F, _F, _I, _I, _F, _F]),
     "qasr_set_shared_device": (C.c_int, [_E, C.c_int]),
